@@ -13,9 +13,16 @@ N > 1: the path shards over independent init times exactly as the reference's ro
 (rollout_to_netcdf.py:259 `i % world_size == rank`): every rank advances its own forecast, no
 data-path collective, weak scaling; value = N*K steps / max-over-ranks time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; the secondary measurements
+run only with --full, each as its own object of the line (null otherwise), e.g.
   roofline     - the dominant kernel (the implicit-GEMM MFMA conv kernel), algorithmic FLOPs / HIP-event time
   cpu_baseline - the CPU oracle (oracle/wxformer_oracle.py, torch CPU fp32) timed on this box's host cores
+and fp32 / fp32_split / host_delivery / concurrent_forecasts / config2 / config5 (the --no-* options still drop single legs).
+
+--dump-outputs DIR writes what the timed path handed back after its last step (rank 0: the de-normalised output y_phys and
+the next model input; the normalised output too with --latband) as DIR/<name>.npy, float32.  An array above DUMP_MAX_ELEMS
+elements is written as a fixed sample (DUMP_SEED): sorted flat indices drawn without replacement, the same for every run and
+build with the same arguments, whose inputs are seeded too -- so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -41,6 +48,19 @@ METRICS = {
     "T1": "forecast-steps/sec (rollout) tiny 61x120 test model (NOT the headline grid)",
 }
 PEAK_TFLOPS = {"bf16": 2500.0, "fp32": 157.3, "fp32s": 2500.0 / 3.0}   # fp32s: three bf16 MFMAs per product  # dense MFMA peaks, /opt/skills/guides/MI355X_MICROARCH.md
+DUMP_MAX_ELEMS = 1 << 22   # per array: 16 MB of float32, at most three arrays -> well under 64 MB per dump
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> device tensor.  Writes out_dir/<name>.npy (float32): the whole array, or its fixed seeded sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -50,6 +70,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32", "fp32s"])
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements after the timed steps (roofline, cpu_baseline, "
+                                                        "fp32, fp32_split, host_delivery, concurrent_forecasts, config2, config5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path computed in its last step to DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU-oracle forwards of the cpu_baseline leg (after one warm-up)")
@@ -64,6 +87,8 @@ def main():
                     help="opt-in: ONE forecast sharded over the N ranks by latitude (SURVEY 8(e) mode 2, strong scaling) instead "
                          "of N independent forecasts; exchanges go through torch.distributed P2P (RCCL)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the HIP engine has no CPU fallback")
@@ -131,9 +156,11 @@ def main():
     elapsed = grp.timed(timed_work, torch.cuda.synchronize)
     x_cur, x_nxt = state["x"]
     finite = bool(torch.isfinite(y_phys).all().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y_phys": y_phys, "x_next": x_cur})
 
     host_delivery = None
-    if rank == 0 and world == 1 and not args.no_host_delivery:
+    if args.full and rank == 0 and world == 1 and not args.no_host_delivery:
         # What the reference's loop does with every step's output (rollout_to_netcdf.py:289-301: y_pred_phys.cpu().numpy() handed to the
         # writer pool): the PCIe-INCLUSIVE rate, never `value`.  Pinned ring + copy stream (wxengine.output.HostDelivery: step t computes
         # while step t-1 crosses PCIe), and beside it the reference's own form -- a blocking pageable copy per step on the same engine.
@@ -190,7 +217,7 @@ def main():
         del hd
 
     concurrent = None
-    if rank == 0 and world == 1 and args.config == "C3" and not args.no_concurrent:
+    if args.full and rank == 0 and world == 1 and args.config == "C3" and not args.no_concurrent:
         # Serving option, never `value`: TWO forecasts (init times) in flight on the one GPU, each on its own engine + stream
         # (wxengine.replicas.ForecastPool) -- the reference walks a rank's init times one at a time (rollout_to_netcdf.py:259-262).
         from wxengine.replicas import ForecastPool
@@ -223,7 +250,7 @@ def main():
         del pool, jobs
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         eng.profile(True)
         eng.profile_reset()
         nprof = 3
@@ -297,7 +324,7 @@ def main():
                                            "tflops": round(blk[0]["flops"] / (blk[0]["ms"] * 1e-3) / 1e12, 1)}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import wxformer_oracle as O  # checker/baseline only; never on the product path
         # torch's CPU conv path degrades badly when oversubscribed (256 threads: 281 s/step on the GPU box vs
         # 62 s with 8 threads in the dev container), so the baseline uses the PHYSICAL cores, at most 32, and says so.
@@ -338,7 +365,7 @@ def main():
                                   f"fp32 oracle on {physical} physical cores ({logical} logical CPUs), {cpu_s:.1f} s per step"}
 
     fp32 = fp32_split = None
-    if rank == 0 and world == 1 and args.precision == "bf16" and not args.no_fp32:
+    if args.full and rank == 0 and world == 1 and args.precision == "bf16" and not args.no_fp32:
         # the mode whose outputs meet the stated fp32 tolerance against the reference (exact-f32 MFMA, tests/test_engine_gpu.py):
         # same workload, same loop, fewer steps (it is ~8x slower); reported beside the headline, never as `value`
         del eng
@@ -393,7 +420,7 @@ def main():
         del engs
 
     config2 = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.precision == "bf16" and not args.no_config2:
+    if args.full and rank == 0 and world == 1 and args.config == "C3" and args.precision == "bf16" and not args.no_config2:
         # BASELINE config 2 beside the headline: the 1-degree model, 24-step rollout (the launch-latency regime); never `value`
         cfg1 = named_config("C1")
         e1 = WXEngine(cfg1, "bf16", local_rank)
@@ -426,7 +453,7 @@ def main():
         del e1
 
     config5 = None
-    if rank == 0 and world == 1 and args.config == "C3" and args.precision == "bf16" and not args.no_config2:
+    if args.full and rank == 0 and world == 1 and args.config == "C3" and args.precision == "bf16" and not args.no_config2:
         # BASELINE config 5 (second architecture): the FuXi-6h 0.25-degree forward (the model section of the reference's fuxi_6h_single_step.yml:
         # 640 x 1280, patch 4, 2 frames, 74 channels in / 71 out, dim 1024, 8 heads, 7 x 7 windows, depth 16; 266 M parameters) through wx_fuxi_*: CubeEmbedding, DownBlock, the Swin
         # stage on 84 x 161 padded tokens, UpBlock, fc, patch -> pixel.  Keyed synthetic weights.  The stage is made of timm's Swin V2 block
@@ -525,6 +552,8 @@ def bench_latband(args, cfg, eng, grp, dev, n_dyn):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # rank 0's latitude band
+        dump_outputs(args.dump_outputs, {"y": y, "y_phys": y_phys, "x_next": x_cur})
     sent_per_step = float(db.sent_bytes_per_step) if db.transport == "rccl" else float(db.exchanged_bytes) / args.steps
     stats = torch.tensor([elapsed, sent_per_step, float(torch.isfinite(y_phys).all().item())],
                          dtype=torch.float64, device=dev if (not dist or dist.get_backend() == "nccl") else "cpu")

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ def _bench(args, **env):
 
 
 def test_one_gpu_line_carries_roofline_and_host_delivery():
-    r, lines = _bench(QUICK)
+    r, lines = _bench(["--full", *QUICK])
     assert r.returncode == 0, r.stderr[-3000:]
     assert len(lines) == 1
     out = json.loads(lines[0])
@@ -28,6 +29,26 @@ def test_one_gpu_line_carries_roofline_and_host_delivery():
     assert out["roofline"]["bound"] == "mfma" and out["roofline"]["achieved"] > 0
     hd = out["host_delivery"]   # every step's output delivered to pinned host memory (rollout_to_netcdf.py:289-301)
     assert hd["value"] > 0 and hd["d2h_GBps"] > 0 and hd["finite_outputs"] and hd["blocking_copy_per_step"]["value"] > 0
+
+
+def test_plain_run_times_the_steps_only_and_dumps_repeatable_outputs(tmp_path):
+    """Without --full the line carries the headline alone; --dump-outputs writes the last timed step's outputs (float32), the same
+    bits from run to run with the same arguments."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r, lines = _bench(["--config", "T1", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 4 and out["value"] > 0 and out["ms_per_step"] > 0 and out["config"]["finite_outputs"]
+        assert all(out[k] is None for k in ("roofline", "cpu_baseline", "fp32", "fp32_split", "host_delivery", "concurrent_forecasts",
+                                            "config2", "config5"))
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    assert sorted(dumps[0]) == ["x_next.npy", "y_phys.npy"]
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, dumps[1][name])
 
 
 def test_gpus_2_without_torchrun_runs_two_ranks():

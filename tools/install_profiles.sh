@@ -1,8 +1,8 @@
 #!/bin/bash
-# Build container: copy ONE collection call's outputs (gpurun_out/<tag>_*, tools/collect_r06.sh) under the names profiles/ keeps.
+# Build container: copy ONE collection call's outputs ($out/<tag>_*, tools/collect_r06.sh) under the names profiles/ keeps.
 #   bash tools/install_profiles.sh r06
 tag=${1:-r06}
-g=gpurun_out
+g=${OUT_DIR:-prof_out}   # the collection scripts' output folder
 cp $g/${tag}_bench.json profiles/bench_${tag}.json
 cp $g/${tag}_bench_config2_1deg.json profiles/bench_${tag}_config2_1deg.json
 cp $g/${tag}_bench_events_off.json profiles/bench_${tag}_events_off.json

@@ -888,9 +888,55 @@ def fixers_sigma_golden():
     np.savez_compressed(os.path.join(GOLD, "fixers_sigma.npz"), **out)
 
 
+def blocks_golden(stride=4):
+    """T1 (T0's full maps are in model_T0.npz): every sub-module output (module-name depth <= 4, cube embedding aside) that
+    oracle/wxformer_oracle.py also captures, as a stride-`stride` sample of each map plus full-map per-channel sums and max|.|, and
+    the dynamic position bias of the first attention -> reference_blocks_T1.npz (tests/test_oracle_vs_reference.py)."""
+    from oracle import wxformer_oracle as O
+    cfg = named_config("T1")
+    m = reference_model(cfg)
+    x = torch.from_numpy(synth_input(cfg))
+    caps = {}
+    hooks = [mod.register_forward_hook(lambda _m, _i, o, n=n: caps.__setitem__(n, o.detach().clone()))
+             for n, mod in m.named_modules() if n.count(".") <= 4 and n and not n.startswith("cube")]
+    with torch.no_grad():
+        m(x)
+    for h in hooks:
+        h.remove()
+    mine = {}
+    O.forward(cfg, synth_state_dict(cfg), x, capture=mine)
+    out = {"stride": np.int64(stride)}
+    for n, v in caps.items():
+        if n in mine and tuple(mine[n].shape) == tuple(v.shape):
+            v = v[0].double()
+            out["cap/" + n] = v[:, ::stride, ::stride].numpy().astype(np.float32)
+            out["ch_sum/" + n] = v.sum(dim=(1, 2)).numpy()
+            out["ch_maxabs/" + n] = v.abs().amax(dim=(1, 2)).numpy()
+    att = m.layers[0][1].layers[0][0]
+    wsz = att.window_size
+    pos = torch.arange(-wsz, wsz + 1)
+    rel = torch.stack(torch.meshgrid(pos, pos, indexing="ij")).reshape(2, -1).t().float()
+    with torch.no_grad():
+        out["dpb/layers.0.1.layers.0.0.dpb"] = att.dpb(rel)[att.rel_pos_indices].numpy().astype(np.float32)
+    out["dpb_window"] = np.int64(wsz)
+    np.savez_compressed(os.path.join(GOLD, "reference_blocks_T1.npz"), **out)
+    print(f"[golden] blocks T1: {len([k for k in out if k.startswith('cap/')])} module outputs, stride {stride}")
+
+
+def state_specs_golden():
+    """Parameter / buffer names and shapes of the reference class per config -> reference_state_specs.json (tests/test_abi_cpu.py)."""
+    import json
+    specs = {}
+    for name in ("T0", "T1", "T0W", "T0U", "T0M", "T0F"):
+        specs[name] = {k: list(v.shape) for k, v in reference_model(named_config(name)).state_dict().items()}
+    with open(os.path.join(GOLD, "reference_state_specs.json"), "w") as f:   # one line per config
+        f.write("{\n" + ",\n".join(f"{json.dumps(n)}: {json.dumps(specs[n], sort_keys=True)}" for n in sorted(specs)) + "\n}\n")
+    print(f"[golden] state specs of {sorted(specs)}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="pad,T0,T1,glue,swin,swinblock,fuxi,attend,rollC1,rollC3S,rollC3,T0M,layout,fixers,sigma,updown,pre,gen2,rec,asm,gen2loop,fuxi_timm,C1,C3S,C3,T0W,C1W,T0U,T0F,RT,stress")
+    ap.add_argument("--only", default="pad,T0,T1,blocks,specs,glue,swin,swinblock,fuxi,attend,rollC1,rollC3S,rollC3,T0M,layout,fixers,sigma,updown,pre,gen2,rec,asm,gen2loop,fuxi_timm,C1,C3S,C3,T0W,C1W,T0U,T0F,RT,stress")
     args = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(os.cpu_count() or 1)
@@ -937,6 +983,10 @@ def main():
             fuxi_timm_golden()
         elif item in ("T0", "T1", "T0W", "T0U", "T0M", "T0F", "T0H", "T1H", "T0X"):
             model_golden(item, 1, capture_layers=(item in ("T0", "T0W", "T0U")))
+        elif item == "blocks":
+            blocks_golden()
+        elif item == "specs":
+            state_specs_golden()
         elif item == "RT":   # the model of the reference's own tests/test_crossformer.py
             model_golden(item, 2, False)
         elif item == "C1W":
