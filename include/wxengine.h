@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define WX_ABI_VERSION 2
+#define WX_ABI_VERSION 3
 
 typedef struct wx_engine* wx_handle;
 
@@ -80,6 +80,11 @@ typedef struct wx_config {
   int32_t precision;                /* enum wx_precision */
   int32_t max_batch;                /* largest B accepted by wx_forward (>= 1) */
   int32_t arch;                     /* enum wx_arch: which reference class the state dict belongs to */
+  /* the noise-injection ensemble (model.type crossformer-ensemble: credit/models/wxformer/crossformer_ensemble.py CrossFormerWithNoise,
+     a subclass of the legacy CrossFormer; arch WX_ARCH_CROSSFORMER or WX_ARCH_CROSSFORMER_UPCONV only, not in lat-band mode) */
+  int32_t noise_latent_dim;         /* 0 = deterministic model (no noise layers, no extra launches); > 0: Linear(noise_latent_dim, C) styles */
+  int32_t encoder_noise;            /* noise layers after encoder stages 0, 1, 2 (keys encoder_noise_layers.{0,1,2}.*) */
+  int32_t noise_correlated;         /* one latent z per forward shared by every layer, else a fresh z per layer */
 } wx_config;
 
 /* ---- lifecycle -----------------------------------------------------------
@@ -147,6 +152,24 @@ int wx_step(wx_handle h, const float* x_dev, const float* frc_dev, float* y_dev,
  *     between dependent kernels is the device-side dispatch boundary, not host launch time), so it is off by default. */
 int wx_rollout(wx_handle h, const float* x0_dev, const float* const* frc_dev, int n_steps, float* const* y_phys_dev,
                float* x_final_dev, void* stream);
+
+/* ---- the ensemble's noise (CrossFormerWithNoise; the generator's exact recipe: csrc/wx_noise.h) ------------------------------
+ * Six StochasticDecompositionLayers (stochastic_decomposition_layer.py): y = x + ((noise_factor * r) * style) * modulation,
+ * style = noise_transform(z), r ~ N(0,1) per element, z ~ N(0,1) per member; after encoder stages 0..2 (in place on the stage
+ * output, which is both the skip and the next stage's input) and after up_block1..3 (before the concat).  The engine draws r and z
+ * from a counter-based Philox4x32-10 generator keyed by (seed; element, layer, member, step), so every member and step has its own
+ * reproducible noise whatever the batch split, precision or launch geometry.
+ * wx_set_noise       seed, member of batch row 0 (row b of wx_forward is member member0 + b; wx_step / wx_rollout run member0) and
+ *                    the step coordinate of the next forward.  The step lives in device memory and advances by one after every
+ *                    wx_forward, wx_step and rollout step (also inside the WX_GRAPH=1 replays).  Defaults: 0, 0, 0.
+ * wx_set_noise_tape  replays given draws instead of the generator, in the reference's draw order: per active layer (encoder 0..2, then
+ *                    decoder 1..3) the latent z [B][noise_latent_dim] then the pixel noise [B][C][H][W] (with noise_correlated: one
+ *                    latent first, then the pixel draws); `draws` is a HOST array of n DEVICE pointers (float32), each covering the
+ *                    batch of the next wx_forward.  draws = NULL returns to the generator.  The pointers must stay valid while set.
+ * Both reject a model without noise layers.  Debug captures "encoder_noise_layers.K" / "noise_injectN" hold the noisy maps
+ * ("layers.K.1" / "up_blockN" stay the pre-noise ones). */
+int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step);
+int wx_set_noise_tape(wx_handle h, const float* const* draws, int n);
 
 /* ---- window attention as an operator of its own (second architecture) --------------------------------
  * The attention CORE of a windowed transformer block on a token-major map: out = softmax(scores + bias [+ mask]) v per window

@@ -34,6 +34,7 @@
 #include "wx_fuxi.h"
 #include "wx_post.h"
 #include "wx_pre.h"
+#include "wx_noise.h"
 
 namespace wx {
 
@@ -149,6 +150,8 @@ class EngineBase {
   virtual void* band_comm_stream(void* adopt) = 0;
   virtual void band_rccl_init(const ncclUniqueId& id) = 0;
   virtual void band_step_rccl(const float* x_own, const float* frc_own, float* y, float* y_phys, float* x_next, hipStream_t s) = 0;
+  virtual void set_noise(uint64_t seed, int member0, int step) = 0;
+  virtual void set_noise_tape(const float* const* draws, int n) = 0;
   int device = 0;
 };
 
@@ -202,6 +205,9 @@ class Engine : public EngineBase {
           throw ConfigError("dim_head != 32 needs windows of at most 128 tokens (the general attention kernel's limit)");
     if (cfg.arch != WX_ARCH_CROSSFORMER && cfg.arch != WX_ARCH_WXFORMER && cfg.arch != WX_ARCH_CROSSFORMER_UPCONV)
       throw ConfigError("unknown wx_config.arch");
+    if (cfg.noise_latent_dim < 0 || cfg.noise_latent_dim > 4096) throw ConfigError("noise_latent_dim must be in 0 .. 4096");
+    if (cfg.noise_latent_dim > 0 && cfg.arch == WX_ARCH_WXFORMER)
+      throw ConfigError("noise layers belong to crossformer-ensemble (a legacy CrossFormer subclass): not with the wxformer decoder");
     C_in = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.input_only_channels) * cfg.frames;
     C_out = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.output_only_channels) * cfg.output_frames;
     Hp = cfg.image_height + (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);
@@ -346,7 +352,23 @@ class Engine : public EngineBase {
     } else {
       add_conv("up_block4", {2 * (last / 8), C_out, 4, 4}, true, true);
     }
+    // CrossFormerWithNoise (crossformer_ensemble.py): created after apply_spectral_norm, so noise_transform keeps a plain `weight`
+    for (int l = 0; l < 6; ++l) {
+      if (!noise_slot_on(l)) continue;
+      const std::string p = noise_prefix(l);
+      const int c = noise_channels(l);
+      add_key(p + ".modulation", {1, c, 1, 1});
+      add_key(p + ".noise_factor", {1});
+      add_key(p + ".noise_transform.weight", {c, cfg.noise_latent_dim});
+      add_key(p + ".noise_transform.bias", {c});
+    }
   }
+  // noise slots: 0 - 2 encoder_noise_layers.{0,1,2} (after stage k, width dim[k]); 3 - 5 noise_inject{1,2,3} (after up_block n, width dim[3 - n])
+  bool noise_slot_on(int l) const { return cfg.noise_latent_dim > 0 && (l >= 3 || cfg.encoder_noise); }
+  std::string noise_prefix(int l) const {
+    return l < 3 ? "encoder_noise_layers." + std::to_string(l) : "noise_inject" + std::to_string(l - 2);
+  }
+  int noise_channels(int l) const { return l < 3 ? cfg.dim[l] : cfg.dim[5 - l]; }
   std::string embed_key(int s, int b) const {
     return "layers." + std::to_string(s) + ".0.convs." + std::to_string(b) + (cfg.arch == WX_ARCH_WXFORMER ? ".1" : "");
   }
@@ -407,6 +429,12 @@ class Engine : public EngineBase {
   StageL stages[4];
   UpL ups[3];
   ConvW up4[4];
+  struct NoiseL { int64_t w = -1, b = -1, mod = -1, nf = -1; };
+  NoiseL nz[6];       // float-arena offsets of the six noise layers (slots as noise_slot_on)
+  NoiseState* d_noise = nullptr;   // seed / member0 / step (device: advanced inside captured graphs)
+  float* d_style = nullptr;        // [6][dim[3]] styles of the batch row being computed
+  std::vector<const float*> noise_tape;   // wx_set_noise_tape: device pointers in the reference's draw order (empty: generator)
+  int cur_row = 0;                 // batch row of the forward item being computed
   ConvW ps4, fin4;   // wxformer head: sub-pixel conv (shuffled rows) and the final 3x3 conv
   int cpad4 = 0;
   T* ps4_buf = nullptr;
@@ -933,6 +961,16 @@ class Engine : public EngineBase {
       make_convt4("up_block4", 2 * (last / 8), C_out);
     }
 
+    for (int l = 0; l < 6; ++l) {
+      nz[l] = NoiseL{};
+      if (!noise_slot_on(l)) continue;
+      const std::string p = noise_prefix(l);
+      nz[l].w = push_f(need(p + ".noise_transform.weight").data);
+      nz[l].b = push_f(need(p + ".noise_transform.bias").data);
+      nz[l].mod = push_f(need(p + ".modulation").data);
+      nz[l].nf = push_f(need(p + ".noise_factor").data);
+    }
+
     // upload
     if (wt_dev) { (void)hipFree(wt_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)wt_dev)); wt_dev = nullptr; }
     if (f_dev) { (void)hipFree(f_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)f_dev)); f_dev = nullptr; }
@@ -1169,6 +1207,11 @@ class Engine : public EngineBase {
     d_std = (float*)dalloc(C_out * sizeof(float));
     d_lo = (float*)dalloc(C_out * sizeof(float));
     d_hi = (float*)dalloc(C_out * sizeof(float));
+    if (cfg.noise_latent_dim > 0) {
+      d_noise = (NoiseState*)dalloc(sizeof(NoiseState));
+      WX_HIP(hipMemset(d_noise, 0, sizeof(NoiseState)));
+      d_style = (float*)dalloc((size_t)6 * cfg.dim[3] * sizeof(float));
+    }
     acts_ready = true;
   }
 
@@ -2294,6 +2337,79 @@ class Engine : public EngineBase {
     attention(a, s, "", df, false);
     feedforward(f, s, "", df ? &a : nullptr);
   }
+  // ------------------------------------------------------------------ ensemble noise (wx_noise.h)
+  // tape entries of slot l in the reference's draw order: per active layer (latent, pixel), or one latent first when correlated
+  int tape_index(int l, bool latent) const {
+    int e = 0;
+    for (int k = 0; k < l; ++k) e += noise_slot_on(k);
+    if (cfg.noise_correlated) return latent ? 0 : 1 + e;
+    return 2 * e + (latent ? 0 : 1);
+  }
+  int tape_count() const {
+    int e = 0;
+    for (int k = 0; k < 6; ++k) e += noise_slot_on(k);
+    return cfg.noise_correlated ? 1 + e : 2 * e;
+  }
+  void noise_styles() {
+    NoiseStyleParams p{};
+    for (int l = 0; l < 6; ++l) {
+      if (!noise_slot_on(l)) continue;
+      p.w[l] = f_dev + nz[l].w;
+      p.bias[l] = f_dev + nz[l].b;
+      p.C[l] = noise_channels(l);
+      if (!noise_tape.empty()) p.tape_z[l] = noise_tape[tape_index(l, true)] + (int64_t)cur_row * cfg.noise_latent_dim;
+    }
+    p.style = d_style; p.cstride = cfg.dim[3]; p.Dn = cfg.noise_latent_dim; p.correlated = cfg.noise_correlated; p.row = cur_row;
+    p.st = d_noise;
+    const size_t lds = (size_t)((cfg.noise_latent_dim + 3) / 4) * 4 * sizeof(float);
+    timed("noise_style", 2.0 * cfg.noise_latent_dim * (2 * cfg.dim[0] + 2 * cfg.dim[1] + 2 * cfg.dim[2]), 0.0, [&] {
+      hipLaunchKernelGGL(noise_style_kernel, dim3(6), dim3(256), lds, cur_stream, p);
+      WX_HIP(hipGetLastError());
+    });
+  }
+  void noise_inject(int l, T* x, int64_t ld, int h, int w) {
+    const int c = noise_channels(l);
+    constexpr int VEC = 16 / (int)sizeof(T);
+    if (c % VEC || ld % VEC) throw ConfigError("noise layer width must be a multiple of the 16-byte vector");
+    if ((int64_t)c * h * w >= (int64_t)1 << 34) throw ConfigError("noise layer larger than 2^34 elements (32-bit quad counter)");
+    NoiseInjectParams<T> p{};
+    p.x = x; p.ld = ld; p.HW = h * w; p.C = c;
+    p.style = d_style + l * cfg.dim[3]; p.nf = f_dev + nz[l].nf; p.mod = f_dev + nz[l].mod;
+    p.tape = noise_tape.empty() ? nullptr : noise_tape[tape_index(l, false)] + (int64_t)cur_row * c * h * w;
+    p.st = d_noise; p.slot = l; p.row = cur_row;
+    const int64_t total = (int64_t)cdiv((int64_t)h * w, 4) * (c / VEC);
+    const int blocks = (int)std::min<int64_t>(cdiv(total, 256), 8192);
+    timed("noise_inject", 0.0, 2.0 * (double)h * w * c * sizeof(T), [&] {
+      hipLaunchKernelGGL(noise_inject_kernel<T>, dim3(blocks), dim3(256), 0, cur_stream, p);
+      WX_HIP(hipGetLastError());
+    });
+  }
+  void noise_next_step() {   // after every forward / step: the next one draws new noise (a captured graph replays this too)
+    if (cfg.noise_latent_dim <= 0) return;
+    timed("noise_step", 0.0, 0.0, [&] {
+      hipLaunchKernelGGL(noise_step_kernel, dim3(1), dim3(64), 0, cur_stream, d_noise);
+      WX_HIP(hipGetLastError());
+    });
+  }
+  void set_noise(uint64_t seed, int member0, int step) override {
+    if (cfg.noise_latent_dim <= 0) throw ConfigError("wx_set_noise: the model has no noise layers (noise_latent_dim = 0)");
+    if (!acts_ready) throw StateError("wx_set_noise: finalize the weights first");
+    if (member0 < 0 || step < 0) throw ConfigError("wx_set_noise: member0 and step must be >= 0");
+    WX_HIP(hipSetDevice(device));
+    const NoiseState st{(uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), member0, step};
+    WX_HIP(hipDeviceSynchronize());   // forwards / graph replays in flight read the state
+    WX_HIP(hipMemcpy(d_noise, &st, sizeof(st), hipMemcpyHostToDevice));
+  }
+  void set_noise_tape(const float* const* draws, int n) override {
+    if (cfg.noise_latent_dim <= 0) throw ConfigError("wx_set_noise_tape: the model has no noise layers (noise_latent_dim = 0)");
+    roll_invalidate();   // captured graphs bake the draw pointers in
+    if (!draws) { noise_tape.clear(); return; }
+    if (n != tape_count())
+      throw ConfigError("wx_set_noise_tape: expected " + std::to_string(tape_count()) + " draw tensors, got " + std::to_string(n));
+    for (int i = 0; i < n; ++i)
+      if (!draws[i]) throw ConfigError("wx_set_noise_tape: NULL draw pointer");
+    noise_tape.assign(draws, draws + n);
+  }
   void core(const float* x_item) {
     n_two_stream_stages = 0;
     n_gemm8p = 0;
@@ -2307,6 +2423,7 @@ class Engine : public EngineBase {
     // a1: pack + earth halo
     pack_input(x_item, xin, xin_planar, Hp + 2 * halo, 0, Hp, halo, 0, cfg.image_height);
     capture("pad", xin + ((int64_t)halo * (Wp + 2 * halo) + halo) * cpad0, Hp, Wp, C_in, cpad0, Wp + 2 * halo);
+    if (cfg.noise_latent_dim > 0) noise_styles();
     // encoder
     for (int s = 0; s < 4; ++s) {
       cur_stage = s;
@@ -2317,6 +2434,10 @@ class Engine : public EngineBase {
       capture(sp + ".0", stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
       stage_blocks(s);
       capture(sp + ".1", stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
+      if (s < 3 && noise_slot_on(s)) {   // in place: the noisy map is both the skip and the next stage's input
+        noise_inject(s, stream_ptr(s), stream_ld(s), sh[s], sw[s]);
+        capture(noise_prefix(s), stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
+      }
     }
     // decoder
     stat_tiles_ready = 0;
@@ -2348,6 +2469,10 @@ class Engine : public EngineBase {
                 0, 0, 0, 0, false, true);
       group_norm_silu(ta, u.cout, mo, u.g2, u.b2, scut, u.cout, cat[so], 2 * cfg.dim[so], gp);
       capture("up_block" + std::to_string(i + 1), cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
+      if (noise_slot_on(3 + i)) {       // before the concat: the up block's half of cat[so]
+        noise_inject(3 + i, cat[so], 2 * cfg.dim[so], sh[so], sw[so]);
+        capture(noise_prefix(3 + i), cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
+      }
     }
     cur_stage = 7;
     if (cfg.arch == WX_ARCH_WXFORMER) {
@@ -2484,6 +2609,7 @@ class Engine : public EngineBase {
       throw ConfigError("lat-band mode: the upsample_v_conv decoder variant is not wired (crossformer and wxformer are)");
     if (e.cfg.frames != 1 || e.cfg.output_frames != 1) throw ConfigError("lat-band mode needs frames == output_frames == 1");
     if (e.cfg.dim_head != 32) throw ConfigError("lat-band mode needs dim_head == 32");
+    if (e.cfg.noise_latent_dim > 0) throw ConfigError("lat-band mode: the noise-injection ensemble (noise_latent_dim > 0) is not supported");
   }
 
   void band_enable(int rank, int n) override {
@@ -3072,9 +3198,12 @@ class Engine : public EngineBase {
     const int64_t in_item = (int64_t)C_in * cfg.image_height * cfg.image_width;
     const int64_t out_item = (int64_t)C_out * Ho * Wo;
     for (int b = 0; b < batch; ++b) {
+      cur_row = b;
       core(x + b * in_item);
       finish_item(x + b * in_item, y + b * out_item, nullptr, nullptr);
     }
+    cur_row = 0;
+    noise_next_step();
     if (prof_on) drain();
   }
   void step(const float* x, const float* frc, float* y, float* y_phys, float* x_next, hipStream_t s) override {
@@ -3091,6 +3220,7 @@ class Engine : public EngineBase {
     cur_stream = s;
     core(x);
     finish_item(x, y, y_phys, x_next);
+    noise_next_step();
     if (x_next) {
       const int64_t plane = (int64_t)cfg.image_height * cfg.image_width;
       copy_layout_groups(x, frc, x_next, plane, s);
@@ -3128,6 +3258,7 @@ class Engine : public EngineBase {
     cur_stream = s;
     core(x);
     finish_item(x, nullptr, y_phys, x_next);
+    noise_next_step();
     if (x_next) copy_layout_groups(x, frc, x_next, (int64_t)cfg.image_height * cfg.image_width, s, with_static);
   }
   void rollout(const float* x0, const float* const* frc, int n, float* const* y_phys, float* x_final, hipStream_t s) override {
@@ -3395,6 +3526,12 @@ int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts) {
     const std::vector<int>& v = which < 4 ? p->plan.g.ps[which] : which < 8 ? p->plan.g.pl[which - 4] : p->plan.g.po;
     for (size_t i = 0; i < v.size(); ++i) starts[i] = v[i];
   });
+}
+int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step) {
+  return guarded([&] { WX_NEED(h); h->impl->set_noise(seed, member0, step); });
+}
+int wx_set_noise_tape(wx_handle h, const float* const* draws, int n) {
+  return guarded([&] { WX_NEED(h); h->impl->set_noise_tape(draws, n); });
 }
 int wx_set_debug(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->set_debug(enable); }); }
 int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]) {

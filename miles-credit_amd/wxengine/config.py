@@ -53,6 +53,13 @@ class WXConfig:
     # credit/models/crossformer.py — the class every BASELINE YAML selects) or "wxformer"
     # (credit/models/wxformer/crossformer.py: same encoder, sub-pixel conv + PixelShuffle decoder).
     arch: str = "crossformer"
+    # CrossFormerWithNoise (model.type crossformer-ensemble, credit/models/wxformer/crossformer_ensemble.py): 0 = deterministic.
+    # The two factors only initialise the noise_factor parameters (a checkpoint overrides them); `freeze` is training-only.
+    noise_latent_dim: int = 0
+    encoder_noise: bool = True
+    correlated: bool = False
+    encoder_noise_factor: float = 0.05
+    decoder_noise_factor: float = 0.275
 
     # ------------------------------------------------------------------ #
     @classmethod
@@ -65,6 +72,7 @@ class WXConfig:
             "image_height", "image_width", "patch_height", "patch_width", "frames", "output_frames",
             "channels", "surface_channels", "input_only_channels", "output_only_channels", "levels",
             "dim_head", "use_spectral_norm", "interp", "upsample_v_conv", "attention_type",
+            "noise_latent_dim", "encoder_noise", "correlated", "encoder_noise_factor", "decoder_noise_factor",
         }
         kw = {k: mc[k] for k in known if k in mc}
         for k in ("dim", "depth", "global_window_size", "cross_embed_strides"):
@@ -93,6 +101,10 @@ class WXConfig:
             raise ValueError("patch_height/patch_width > 1 (CubeEmbedding path) is not supported by the engine")
         if self.upsample_v_conv and self.arch != "crossformer":
             raise ValueError("upsample_v_conv belongs to model.type crossformer only (credit/models/crossformer.py:397)")
+        if self.noise_latent_dim < 0:
+            raise ValueError("noise_latent_dim must be >= 0")
+        if self.noise_latent_dim > 0 and self.arch != "crossformer":
+            raise ValueError("noise layers (crossformer-ensemble) subclass the legacy CrossFormer: not with arch 'wxformer'")
         if self.attention_type is not None:
             raise ValueError("decoder attention_type is not supported by the engine")
         if len(self.dim) != 4 or len(self.depth) != 4:
@@ -280,6 +292,24 @@ class WXConfig:
             conv("up_block4.1", (self.output_channels, 2 * (last // 8), 3, 3))
         else:
             conv("up_block4", (2 * (last // 8), self.output_channels, 4, 4), transposed=True)
+        spec.update(self.noise_spec())
+        return spec
+
+    def noise_layers(self) -> List[Tuple[str, int]]:
+        """[(prefix, channels)] of the StochasticDecompositionLayers in the reference's draw order (encoder 0..2, decoder 1..3)."""
+        if self.noise_latent_dim <= 0:
+            return []
+        enc = [(f"encoder_noise_layers.{k}", self.dim[k]) for k in range(3)] if self.encoder_noise else []
+        return enc + [(f"noise_inject{n}", self.dim[3 - n]) for n in (1, 2, 3)]
+
+    def noise_spec(self) -> "OrderedDict[str, Tuple[int, ...]]":
+        """State keys of the noise layers: created after apply_spectral_norm, so noise_transform has a plain weight."""
+        spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+        for p, c in self.noise_layers():
+            spec[p + ".modulation"] = (1, c, 1, 1)
+            spec[p + ".noise_factor"] = (1,)
+            spec[p + ".noise_transform.weight"] = (c, self.noise_latent_dim)
+            spec[p + ".noise_transform.bias"] = (c,)
         return spec
 
     def num_params(self) -> int:

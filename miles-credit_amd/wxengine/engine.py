@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # WX_LIBRARY: an alternate build of the SAME sources (A/B timing of compile-time switches); the source-hash check still applies
 LIB_PATH = os.environ.get("WX_LIBRARY") or os.path.join(_HERE, "libwxengine.so")
 
-WX_ABI_VERSION = 2
+WX_ABI_VERSION = 3
 ARCH = {"crossformer": 0, "wxformer": 1, "crossformer_upconv": 2}
 PREC = {"fp32": 0, "bf16": 1, "fp32s": 2}   # fp32s: fp32 storage, split-bf16 GEMM arithmetic (WX_PREC_FP32_SPLIT)
 
@@ -36,6 +36,7 @@ class wx_config(C.Structure):
         ("pad_activate", C.c_int32), ("pad_lat", C.c_int32 * 2), ("pad_lon", C.c_int32 * 2),
         ("interp", C.c_int32), ("use_spectral_norm", C.c_int32), ("precision", C.c_int32), ("max_batch", C.c_int32),
         ("arch", C.c_int32),
+        ("noise_latent_dim", C.c_int32), ("encoder_noise", C.c_int32), ("noise_correlated", C.c_int32),
     ]
 
 
@@ -85,6 +86,8 @@ _PROTOTYPES = {
     "wx_band_plan_messages": ([C.c_void_p, C.c_int, C.c_int, C.POINTER(wx_band_msg), C.c_int, C.POINTER(C.c_int), C.POINTER(wx_band_msg),
                                C.c_int, C.POINTER(C.c_int)], C.c_int),
     "wx_band_plan_partition": ([C.c_void_p, C.c_int, C.POINTER(C.c_int32)], C.c_int),
+    "wx_set_noise": ([C.c_void_p, C.c_uint64, C.c_int, C.c_int], C.c_int),
+    "wx_set_noise_tape": ([C.c_void_p, C.POINTER(C.c_void_p), C.c_int], C.c_int),
     "wx_set_debug": ([C.c_void_p, C.c_int], C.c_int),
     "wx_debug_read": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)], C.c_int),
     "wx_query": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)], C.c_int),
@@ -208,6 +211,9 @@ def make_c_config(cfg: WXConfig, precision: str = "bf16", max_batch: int = 1) ->
     if arch == "crossformer" and getattr(cfg, "upsample_v_conv", False):
         arch = "crossformer_upconv"
     c.arch = ARCH[arch]
+    c.noise_latent_dim = int(getattr(cfg, "noise_latent_dim", 0))
+    c.encoder_noise = int(bool(getattr(cfg, "encoder_noise", True)))
+    c.noise_correlated = int(bool(getattr(cfg, "correlated", False)))
     return c
 
 
@@ -377,6 +383,26 @@ class WXEngine:
         _check(self.lib.wx_rollout(self._h, C.c_void_p(x0.data_ptr()), fa, n, ya,
                                    None if x_final is None else C.c_void_p(x_final.data_ptr()), self._stream()))
         return phys_out, x_final
+
+    # ---- ensemble noise (CrossFormerWithNoise) ----------------------------------------------
+    def set_noise(self, seed: int = 0, member0: int = 0, step: int = 0) -> None:
+        """Generator coordinates: batch row b of the next forward is member member0 + b; `step` is the step coordinate of the
+        next forward / step, advanced by one on the device after each (include/wxengine.h wx_set_noise)."""
+        _check(self.lib.wx_set_noise(self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(member0), int(step)))
+
+    def set_noise_tape(self, draws=None) -> None:
+        """Replay `draws` (float32 CUDA tensors in the reference's torch.randn order, each covering the whole batch) instead of
+        the generator; None returns to the generator."""
+        if draws is None:
+            _check(self.lib.wx_set_noise_tape(self._h, None, 0))
+            self._tape = None
+            return
+        draws = list(draws)
+        for i, t in enumerate(draws):
+            self._chk_in(t, f"draws[{i}]")
+        arr = (C.c_void_p * len(draws))(*[t.data_ptr() for t in draws])
+        _check(self.lib.wx_set_noise_tape(self._h, arr, len(draws)))
+        self._tape = draws   # the engine keeps the raw pointers: keep the tensors alive
 
     # ---- introspection -----------------------------------------------------------------
     def set_debug(self, on: bool) -> None:

@@ -296,6 +296,51 @@ class WXFormerPSHIP(WXFormerHIP):
         super().__init__(precision=precision, arch="wxformer", **model_conf)
 
 
+class WXFormerEnsembleHIP(WXFormerHIP):
+    """`model.type: crossformer-ensemble` / `crossformer-style` (credit/models/wxformer/crossformer_ensemble.py CrossFormerWithNoise):
+    the legacy CrossFormer with six noise-injection layers.  Same kwargs as the reference class (noise_latent_dim, encoder_noise,
+    correlated, encoder_noise_factor, decoder_noise_factor, freeze) plus `precision` and `seed`.
+
+    forward(x, noise=None, forecast_step=None): the B rows of x are ensemble members 0 .. B-1 (the reference's callers
+    repeat_interleave the initial state ensemble_size times).  The noise comes from the engine's counter-based generator keyed by
+    (seed, layer, member, step, element): `forecast_step` selects the step coordinate when given, else an internal counter advances
+    by one per call.  `noise` is ignored, as in the reference (which always overwrites it)."""
+
+    def __init__(self, precision: str = "bf16", seed: int = 0, **model_conf):
+        model_conf.pop("arch", None)
+        model_conf.pop("freeze", None)   # requires_grad bookkeeping of training: nothing to do at inference
+        model_conf.setdefault("noise_latent_dim", 128)   # the reference's defaults (crossformer_ensemble.py:21-30)
+        super().__init__(precision=precision, arch="crossformer", **model_conf)
+        if self.cfg.noise_latent_dim <= 0:
+            raise ValueError("crossformer-ensemble needs noise_latent_dim > 0")
+        self.noise_latent_dim = self.cfg.noise_latent_dim
+        self.encoder_noise = self.cfg.encoder_noise
+        self.correlated = self.cfg.correlated
+        self.seed = int(seed)
+        self._step = 0
+        with torch.no_grad():   # the reference's initial values (a checkpoint overrides them)
+            for p, _ in self.cfg.noise_layers():
+                self._store[_mangle(p + ".modulation")].fill_(1.0)
+                nf = self.cfg.encoder_noise_factor if p.startswith("encoder") else self.cfg.decoder_noise_factor
+                self._store[_mangle(p + ".noise_factor")].fill_(float(nf))
+
+    def forward(self, x: torch.Tensor, noise=None, forecast_step: Optional[int] = None) -> torch.Tensor:
+        if not x.is_cuda:
+            raise WXEngineError("WXFormerEnsembleHIP runs only on the GPU (no CPU fallback); move the input to cuda")
+        eng = self._sync_engine(x.device)
+        step = self._step if forecast_step is None else int(forecast_step)
+        eng.set_noise(self.seed, 0, step)
+        y = eng.forward(x.contiguous().float())
+        self._step = step + 1
+        return y
+
+
+def register_ensemble(model_type: str = "crossformer-ensemble_hip"):
+    """Register the ensemble engine class with the reference's registry (credit.models.register_model)."""
+    from credit.models import register_model  # type: ignore
+    return register_model(model_type, "Loading the MI355X-native noise-injection ensemble CrossFormer engine ...")(WXFormerEnsembleHIP)
+
+
 def register(model_type: str = "crossformer_hip", wxformer_type: str = "wxformer_hip"):
     """Register both engine classes with the reference's registry (credit.models.register_model)."""
     from credit.models import register_model  # type: ignore

@@ -99,3 +99,20 @@ def rollout(engine: WXEngine, x0: torch.Tensor, forcings: Sequence[Optional[torc
         if xn is not None:
             x = xn
     return ys, phys
+
+
+def ensemble_rollout(engine: WXEngine, x0: torch.Tensor, forcings: Sequence[Optional[torch.Tensor]], n_members: int,
+                     seed: int = 0, step0: int = 0, member0: int = 0):
+    """A noise-injection ensemble (CrossFormerWithNoise engine) as one wx_rollout per member: member m runs the generator's
+    member coordinate member0 + m from step step0, so every member is its own reproducible trajectory.
+
+    Returns [member][step] de-normalised outputs (engine.set_denorm must have been called)."""
+    cfg = engine.cfg
+    oh, ow = cfg.out_hw
+    out = []
+    for m in range(n_members):
+        engine.set_noise(seed, member0 + m, step0)
+        phys = [torch.empty((1, cfg.base_output_channels, oh, ow), dtype=torch.float32, device=x0.device) for _ in forcings]
+        engine.rollout(x0, forcings, phys_out=phys)
+        out.append(phys)
+    return out

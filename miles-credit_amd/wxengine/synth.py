@@ -113,6 +113,12 @@ def synth_state_dict(cfg, seed: int = 0, family: str = "base") -> "OrderedDict[s
         if key.endswith((".weight_u", ".weight_v")):
             continue  # filled below with their weight_orig
         z = keyed_normal(key, shape, seed)
+        if key.endswith(".noise_factor"):   # noise layers: magnitudes that matter against the activations
+            sd[key] = (0.3 * (1.0 + 0.1 * z)).astype(np.float32)
+            continue
+        if key.endswith(".modulation"):
+            sd[key] = (1.0 + 0.5 * np.tanh(z)).astype(np.float32)
+            continue
         if key.endswith(".weight_orig") or (key.endswith(".weight") and len(shape) >= 2):
             fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else shape[0]
             sd[key] = (z / np.sqrt(max(fan_in, 1))).astype(np.float32)
