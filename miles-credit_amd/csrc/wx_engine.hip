@@ -7,6 +7,7 @@
 #include "../../include/wxengine.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -1028,7 +1029,6 @@ class Engine : public EngineBase {
   char* zero_page = nullptr;
   bool use_dma = true;
   bool merge_parity = !getenv("WX_NO_MERGE_PARITY");
-  const ConvW* gemm_par = nullptr;   // set around a gemm() call: the four parity weight sets of a ConvTranspose k4
   bool split_k = !getenv("WX_NO_SPLIT_K");
   bool embed_merge = !getenv("WX_NO_EMBED_MERGE");
   bool ff_small_px64 = !(getenv("WX_FF_PX64") && getenv("WX_FF_PX64")[0] == '0');   // C = 128 plain block on 64-pixel tiles when the map yields < 128 tiles of 128 (1-degree stage 1: 21.5 -> 15.5 us)
@@ -1085,8 +1085,6 @@ class Engine : public EngineBase {
   int stream_min_rows = 4096;
   bool use_stream_lc = !(getenv("WX_NO_STREAM_LC") && getenv("WX_NO_STREAM_LC")[0] == '1');   // loader / consumer form of the persistent GEMM (one-tile-per-CU residual layers)
   bool use_gemm8p = !(getenv("WX_NO_GEMM8P") && getenv("WX_NO_GEMM8P")[0] == '1');   // eight-phase 160 x 256 kernel (wx_gemm8p.h) for the deep-K stride-1 k x k convs of the decoder
-  bool gemm8p_ff2 = getenv("WX_GEMM8P_FF2") && getenv("WX_GEMM8P_FF2")[0] == '1';   // OFF: a tie inside the step (7.809 vs 7.802 ms/step same box) although
-                                                                                     // the stand-alone launch is 5 % faster (43.7 vs 45.9 us); bit-identical
   int64_t gemm8p_min_rows = getenv("WX_GEMM8P_MIN_ROWS") ? atoll(getenv("WX_GEMM8P_MIN_ROWS")) : 16384;
   int64_t n_gemm8p = 0;              // launches of the last forward that took it
   bool use_wreg = !(getenv("WX_NO_WREG") && getenv("WX_NO_WREG")[0] == '1');   // weight-stationary GEMM (wx_gemm_wreg.h) for K = 512 layers on mid-sized maps
@@ -1114,13 +1112,8 @@ class Engine : public EngineBase {
   }
   float2* gnpart = nullptr;     // [m_tiles][C] GroupNorm partials written by the 3x3 conv epilogue
   int64_t gnpart_elems = 0;
-  bool blk_attn = false;        // set around an attention sub-block's to_qkv / window attention / to_out (round 6): q|k|v and the attention output
-                                // are k-blocked [C/32][M][32] = [head][token][32] at dim_head 32 -- to_qkv stores, the attention's loads and
-                                // stores and to_out's operand DMA all move full cache lines (row-major: 64-byte halves of lines 3C x 2 bytes apart)
-  bool attn_blk_on = !(getenv("WX_NO_ATTN_BLK") && getenv("WX_NO_ATTN_BLK")[0] == '1');
+  bool attn_blk_on = !(getenv("WX_NO_ATTN_BLK") && getenv("WX_NO_ATTN_BLK")[0] == '1');   // attention sub-blocks on the k-blocked layouts (KBlk::attn)
   int64_t n_attn_blk = 0;       // attention sub-blocks of the last forward that ran on the k-blocked layouts
-  bool blk_hidden = false;      // set around a FeedForward's two gemm() calls: the hidden tensor is k-blocked [4C/32][M][32] (layer 1 writes
-                                // it, layer 2 reads it: full cache lines per LDS-DMA piece; ff2 47.9 -> 45.0 us, ff1 56.6 -> 53.8 us)
   // Row window (round 5): attention() / feedforward() / gemm() work on map rows [rw0, rw0 + rwn) of the current stage instead of the whole
   // map when rwn >= 0 -- the half-maps of the two-stream schedule below.  Every buffer a sub-block touches is indexed by token, so a
   // window is a pointer offset: the stream, q|k|v and the hidden tensor (scratch, 4 C per token: the halves' regions are disjoint),
@@ -1130,7 +1123,6 @@ class Engine : public EngineBase {
   int64_t rule_rows = 0;
   int64_t rw_tok0(int s) const { return rwn >= 0 ? (int64_t)rw0 * sw[s] : 0; }
   int rw_rows(int s) const { return rwn >= 0 ? rwn : sh[s]; }
-  int last_stat_slots = 0;      // partial slots per row the last statistics-producing gemm() wrote
   int stat_tiles_ready = 0;     // > 0: `statpart` holds partials of the current stream contents (that many per row)
   bool use_patch = true, planar_xin = true;
   double* gn_acc = nullptr;
@@ -1449,7 +1441,6 @@ class Engine : public EngineBase {
   }
 
   // ------------------------------------------------------------------ launch helpers
-  // returns true when the launch also produced LayerNorm partials for its output rows (want_stats)
   // K ranges of the plain split-K rule (gemm() below) for a bias-only convolution of `rows` output pixels; 1 = not split
   int plain_split_ways(const ConvW& w, int64_t rows) const {
     if (!split_k || !use_dma || w.n % 128 != 0 || (w.cin * (int)sizeof(T)) % 128 != 0) return 1;
@@ -1459,214 +1450,214 @@ class Engine : public EngineBase {
     S = std::min(S, nk / 16);   // at least 16 K steps per range
     return (tiles <= 200 && S >= 2) ? S : 1;
   }
-  bool gemm(const char* cls, const ConvW& w, const T* in, int in_h, int in_w, int64_t in_ld, int stride, int pad_y,
-            int pad_x, int out_h, int out_w, T* out, int64_t out_ld, const float2* rs, int act, const T* res,
-            int64_t res_ld, int out_mode = 0, int cout = 0, int py = 0, int px = 0, bool want_stats = false,
-            bool want_gn = false) {
+  // One gemm() call: `in` convolved with a layer's weights into `out`.  The defaults are a stride-1 "same" convolution with a bias-only
+  // epilogue, so a call names only what differs from that.
+  static constexpr int same_pad = INT_MIN;   // pad_y / pad_x: (k - 1) / 2
+  // k-blocked [K/32][M][32] exchange of a sub-block chain (bf16, persistent GEMMs): the LayerNorm-folded producer writes its output
+  // k-blocked and the residual layer behind it reads its operand k-blocked -- full cache lines per LDS-DMA piece.
+  //   hidden: the FeedForward hidden tensor [4C/32][M][32] (ff2 47.9 -> 45.0 us, ff1 56.6 -> 53.8 us)
+  //   attn:   q|k|v and the attention output [C/32][M][32] = [head][token][32] at dim_head 32 (to_qkv's stores, the attention's loads and
+  //           stores and to_out's operand DMA move full cache lines; row-major: 64-byte halves of lines 3C x 2 bytes apart)
+  enum class KBlk { none, hidden, attn };
+  struct GemmReq {
+    const T* in = nullptr; int in_h = 0, in_w = 0; int64_t in_ld = 0;
+    T* out = nullptr; int64_t out_ld = 0;
+    int stride = 1, pad_y = same_pad, pad_x = same_pad;
+    int out_h = -1, out_w = -1;                   // -1: in_h, in_w
+    const float2* rs = nullptr;                   // LayerNorm-folded layer: the statistics of the input rows (stream_stats)
+    int act = 0;                                  // 1: GELU
+    const T* res = nullptr; int64_t res_ld = 0;   // residual added by the epilogue
+    int out_mode = 0, cout = 0;                   // 1: PixelShuffle / ConvTranspose k2 scatter of cout channels; 2: a ConvTranspose k4 ...
+    const ConvW* par = nullptr;                   // ... whose four parity weight sets gemm() runs (in one launch when it can) ...
+    int py = 0, px = 0;                           // ... each as one parity (py, px) of the output
+    KBlk blk = KBlk::none;
+    bool want_stats = false;                      // LayerNorm partials of the output rows into `statpart` ...
+    int stat_stride = 0, stat_slot0 = 0;          // ... as slots stat_slot0.. of rows of stat_stride slots that several launches share (0: own rows)
+    bool want_gn = false;                         // GroupNorm tile partials into `gnpart` ...
+    int gn_off = 0;                               // ... after the gn_off tiles earlier launches of the same conv wrote
+  };
+  struct GemmOut {
+    int stat_slots = 0;   // LayerNorm partial slots per row it wrote (0: none)
+    int gn_tiles = 0;     // GroupNorm tiles it wrote (0: none)
+  };
+  enum class Route { gemm8p_conv, gemm8p_convt2, wreg, stream_res, stream_res_lc, stream_ln, conv128 };
+  // the kernel a (normalised) request runs on; conv128 is the 128 x 128 implicit-GEMM kernel, every shape's fall-back
+  Route gemm_route(const ConvW& w, const GemmReq& r) const {
+    if (sizeof(T) != 2 || !use_dma || dbg_flags) return Route::conv128;
+    const int64_t rows = (int64_t)r.out_h * r.out_w;
+    const int64_t sel_rows = rule_rows > 0 ? rule_rows : rows;   // what the selection rules see (row windows: the whole map)
+    const bool same_map = r.stride == 1 && r.in_h == r.out_h && r.in_w == r.out_w;
+    const bool one = w.kh == 1 && w.kw == 1 && same_map && r.pad_y == 0 && r.pad_x == 0;
+    // stride-1 k x k convolutions with a deep K and >= 256 output channels on large maps (the two 3x3 convs of the decoder's first two
+    // UpBlocks at 0.25 degrees: K = 4608 / 2304): the eight-phase kernel's conv form (wx_gemm8p.h) -- 127.7 -> 90.1 us and 112.6 -> 102.0 us
+    // against the 128 x 128 kernel (tools/gemm8p_probe, profiles/r06_gemm8p_probe_b_conv_form.txt); bitwise the same outputs where the two
+    // walk K in the same order.  GroupNorm partials: one per (160-row tile, wave row) = 80 output rows, folded like the 128-row ones.
+    if (use_gemm8p && rwn < 0 && !band_on && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && same_map && r.pad_y == (w.kh - 1) / 2 &&
+        r.pad_x == (w.kw - 1) / 2 && !r.rs && r.act == 0 && r.out_mode == 0 && !r.want_stats && w.n % 256 == 0 && w.cin % 64 == 0 &&
+        (w.kh * w.kw * w.cin) % 128 == 0 && rows >= gemm8p_min_rows && rows * r.in_ld * 2 < (int64_t)0x7fffff00 && gemm8p_fits(rows, w.n, 2, 5, true) &&
+        (!r.want_gn || (fuse_ln && (int64_t)(r.gn_off + gemm8p_conv_gn_tiles(rows, w.n)) * w.n <= gnpart_elems)))
+      return Route::gemm8p_conv;
+    // ConvTranspose k2 s2 (a 1x1 GEMM with N = 4 cout whose epilogue scatters 2 x 2 pixels; the decoder's three UpBlocks): the same
+    // kernel's 1x1 form with the scatter in its epilogue -- 33.4 -> 24.6, 59.3 -> 41.9, 63.1 -> 47.3 us at 0.25 degrees, bitwise equal
+    if (use_gemm8p && rwn < 0 && !band_on && one && !r.rs && !r.res && r.act == 0 && r.out_mode == 1 && !r.want_stats && !r.want_gn &&
+        r.cout > 0 && w.n == 4 * r.cout && r.cout % 64 == 0 && w.cin % 128 == 0 && rows >= gemm8p_min_rows / 4 && gemm8p_fits(rows, w.n, 2, 5, true))
+      return Route::gemm8p_convt2;
+    // K = 512 layers on maps of a few thousand rows (a lat-band rank's share of the 0.25-degree stage 2: 2 000 - 4 000 tokens): the
+    // weight-stationary kernel (wx_gemm_wreg.h: the wave's weight slice in registers, activations streamed tile by tile, one barrier
+    // per tile).  tools/gemm_wreg_probe, M = 2500: to_qkv 11.5 us against 16.1 (persistent kernel) -- at M = 20 000 the two tie, so the
+    // unsharded model keeps the persistent kernel.  Bitwise the same outputs; row partials in N / 32 slots instead of N / 128.
+    const bool ln_v = r.rs && !r.res && !r.want_stats && w.colsum >= 0, res_v = !r.rs && r.res && r.want_stats && fuse_ln && r.act == 0;
+    if (use_wreg && w.wt_kb >= 0 && one && w.cin == 512 && w.n % WREG_BN == 0 && w.bias >= 0 && r.out_mode == 0 && !r.want_gn && r.blk == KBlk::none &&
+        rwn < 0 && rows >= wreg_min_rows && rows < wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
+        wreg_gemm_ok(rows, w.n, w.cin, r.rs ? stat_tiles_ready : 0, ln_v))
+      return Route::wreg;
+    // residual layers with N = 512 / 1024 (to_out, FeedForward layer 2 of stages 2 and 3): the persistent kernel on 160 x 128 tiles, two
+    // workgroups per CU (47.9 vs 58.3 us on layer 2, 21.0 vs 23.2 us on to_out; bitwise equal to the 128 x 128 kernel's output) -- with at
+    // most one tile per CU and a deep K (stage 3 of the 0.25-degree model) in its loader / consumer form
+    if (use_stream && w.wt_kb >= 0 && one && !r.rs && r.res && r.act == 0 && r.out_mode == 0 && r.want_stats && fuse_ln && !r.want_gn &&
+        (w.n == 512 || w.n == 1024) && w.bias >= 0 && sel_rows >= stream_min_rows && stream_gemm_ok(rows, w.n, w.cin, 128))
+      return use_stream_lc && stream_gemm_lc_pays(sel_rows, w.n, w.cin, 5) ? Route::stream_res_lc : Route::stream_res;
+    // LayerNorm-folded 1x1 layers with many rows and K >= 512 (to_qkv, FeedForward layer 1 of stages 2-3): the persistent
+    // 128 x 256-tile kernel; measured per shape against the 128 x 128 kernel in tools/gemm_stream_probe
+    if (use_stream && w.wt_kb >= 0 && w.n % 256 == 0 && one && r.rs && !r.res && r.out_mode == 0 && !r.want_stats && !r.want_gn &&
+        sel_rows >= stream_min_rows && stream_gemm_ok(rows, w.n, w.cin))
+      return Route::stream_ln;
+    return Route::conv128;
+  }
+  GemmOut gemm(const char* cls, const ConvW& w, GemmReq r) {
+    if (r.out_h < 0) r.out_h = r.in_h;
+    if (r.out_w < 0) r.out_w = r.in_w;
+    if (r.pad_y == same_pad) r.pad_y = (w.kh - 1) / 2;
+    if (r.pad_x == same_pad) r.pad_x = (w.kw - 1) / 2;
     ConvGemmParams p;
     std::memset(&p, 0, sizeof(p));
-    p.in = in; p.in_h = in_h; p.in_w = in_w; p.in_ld = in_ld; p.cin = w.cin;
-    p.kh = w.kh; p.kw = w.kw; p.stride = stride; p.pad_y = pad_y; p.pad_x = pad_x;
-    p.out_h = out_h; p.out_w = out_w;
+    p.in = r.in; p.in_h = r.in_h; p.in_w = r.in_w; p.in_ld = r.in_ld; p.cin = w.cin;
+    p.kh = w.kh; p.kw = w.kw; p.stride = r.stride; p.pad_y = r.pad_y; p.pad_x = r.pad_x;
+    p.out_h = r.out_h; p.out_w = r.out_w;
     p.wt = wt_dev + w.wt; p.n = w.n; p.n_alloc = w.n;
     p.bias = w.bias >= 0 ? f_dev + w.bias : nullptr;
-    p.rowstat = rs; p.colsum = (rs && w.colsum >= 0) ? f_dev + w.colsum : nullptr;
-    p.stat_tiles = rs ? stat_tiles_ready : 0; p.stat_inv_c = 1.0f / (float)w.cin_true; p.stat_out = nullptr;
-    if (rs && w.colsum < 0) throw StateError("LayerNorm-folded GEMM without column sums");
-    p.act = act; p.res = res; p.res_ld = res_ld; p.out = out; p.out_ld = out_ld;
-    p.out_mode = out_mode; p.cout = cout; p.py = py; p.px = px; p.dbg = dbg_flags;
-    const double m = (double)out_h * out_w;
+    p.rowstat = r.rs; p.colsum = (r.rs && w.colsum >= 0) ? f_dev + w.colsum : nullptr;
+    p.stat_tiles = r.rs ? stat_tiles_ready : 0; p.stat_inv_c = 1.0f / (float)w.cin_true;
+    if (r.rs && w.colsum < 0) throw StateError("LayerNorm-folded GEMM without column sums");
+    p.act = r.act; p.res = r.res; p.res_ld = r.res_ld; p.out = r.out; p.out_ld = r.out_ld;
+    p.out_mode = r.out_mode; p.cout = r.cout; p.py = r.py; p.px = r.px; p.dbg = dbg_flags;
+    const bool dma = conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr);
+    const int64_t rows = (int64_t)r.out_h * r.out_w;
+    const double m = (double)rows;
     if constexpr (sizeof(T) == 4) {
-      if (split_mma && w.cin % 32 == 0 && !dbg_flags && conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr)) {
+      if (split_mma && w.cin % 32 == 0 && !dbg_flags && dma) {
         p.split = 1;
         p.wt = ws_dev + w.wt;
-        if (!gemm_par) ++n_split_gemms;   // a ConvTranspose's outer call only dispatches: its launches are counted where they happen
+        if (!r.par) ++n_split_gemms;   // a ConvTranspose's outer call only dispatches: its launches are counted where they happen
       }
-    }
-    if (gemm_par) {   // the four parity convs of a ConvTranspose k4 s2 p1 (out_mode 2): one launch when the fast path takes it
-      const ConvW* gp = gemm_par;
-      gemm_par = nullptr;
-      if (merge_parity && conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr) && !dbg_flags && w.n <= 128) {
-        p.n_par = 4;
-        for (int q = 0; q < 4; ++q) p.wt_par[q] = (p.split ? ws_dev : wt_dev) + gp[q].wt;
-        const double fl4 = 4.0 * 2.0 * m * w.n * w.kh * w.kw * w.cin_true;
-        const double by4 = (4.0 * m * w.n + (double)in_h * in_w * w.cin_true + 4.0 * w.n * w.kh * w.kw * w.cin) * sizeof(T);
-        if (p.split) ++n_split_gemms;   // the merged launch
-        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, gemm_cfg); });
-        return false;
-      }
-      for (int q = 0; q < 4; ++q)
-        gemm(cls, gp[q], in, in_h, in_w, in_ld, stride, pad_y - (q >> 1), pad_x - (q & 1), out_h, out_w, out, out_ld, rs, act, res, res_ld, out_mode,
-             cout, q >> 1, q & 1, want_stats, want_gn);
-      return false;
     }
     const double flops = 2.0 * m * w.n * w.kh * w.kw * w.cin_true * w.flop_frac;
-    const double bytes = (m * w.n * (res ? 2.0 : 1.0) + (double)in_h * in_w * w.cin_true + (double)w.n * w.kh * w.kw * w.cin) * sizeof(T);
-    bool made_stats = false;
-    if (want_stats && fuse_ln && conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr)) {
-      p.stat_out = statpart;
-      p.stat_stride = stat_share_stride; p.stat_slot0 = stat_share_slot0;
-      made_stats = true;
-    }
-    if (want_gn && fuse_ln && conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr)) {
-      p.gn_out = gnpart + (int64_t)gn_tile_off * w.n;   // gn_accum: several launches (interior / boundary rows) append their tiles
-      made_stats = true;
-      if (gn_accum) gn_tile_off += cdiv((int64_t)out_h * out_w, 128);
-    }
+    const double bytes = (m * w.n * (r.res ? 2.0 : 1.0) + (double)r.in_h * r.in_w * w.cin_true + (double)w.n * w.kh * w.kw * w.cin) * sizeof(T);
+    const Route route = gemm_route(w, r);
     if constexpr (sizeof(T) == 2) {
-      // stride-1 k x k convolutions with a deep K and >= 256 output channels on large maps (the two 3x3 convs of the decoder's first two
-      // UpBlocks at 0.25 degrees: K = 4608 / 2304): the eight-phase kernel's conv form (wx_gemm8p.h) -- 127.7 -> 90.1 us and 112.6 -> 102.0 us
-      // against the 128 x 128 kernel (tools/gemm8p_probe, profiles/r06_gemm8p_probe_b_conv_form.txt); bitwise the same outputs where the two
-      // walk K in the same order.  GroupNorm partials: one per (160-row tile, wave row) = 80 output rows, folded like the 128-row ones.
-      {
-        const int64_t rows = (int64_t)out_h * out_w;
-        const int kk = w.kh * w.kw * w.cin;
-        if (use_gemm8p && use_dma && !dbg_flags && !p.stat_out && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && stride == 1 &&
-            pad_y == (w.kh - 1) / 2 && pad_x == (w.kw - 1) / 2 && in_h == out_h && in_w == out_w && !rs && act == 0 && out_mode == 0 && !want_stats &&
-            w.n % 256 == 0 && w.cin % 64 == 0 && kk % 128 == 0 && (!want_gn || (fuse_ln && !gn_accum)) && rwn < 0 && !band_on && rows >= gemm8p_min_rows &&
-            rows * in_ld * 2 < (int64_t)0x7fffff00 && gemm8p_fits(rows, w.n, 2, 5, true)) {
-          Gemm8pParams q;
-          std::memset(&q, 0, sizeof(q));
-          q.a = reinterpret_cast<const bf16_t*>(in); q.lda = in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt);
-          q.M = (int)rows; q.N = w.n; q.K = kk; q.bias = p.bias;
-          q.res = reinterpret_cast<const bf16_t*>(res); q.res_ld = res_ld;
-          q.out = reinterpret_cast<bf16_t*>(out); q.out_ld = out_ld; q.sink = stream_sink; q.xcd_part = 1;
-          q.in_h = in_h; q.in_w = in_w; q.cin = w.cin; q.kh = w.kh; q.kw = w.kw; q.pad_y = pad_y; q.pad_x = pad_x;
-          q.gn_out = want_gn ? gnpart : nullptr;
-          if (want_gn && (int64_t)gemm8p_conv_gn_tiles(rows, w.n) * w.n > gnpart_elems) throw StateError("GroupNorm partials of the eight-phase conv exceed the reserved buffer");
-          cur_family = "gemm8p";
-          timed(cls, flops, bytes, [&] { launch_gemm8p_conv(q, cur_stream); });
-          ++n_gemm8p;
-          if (want_gn) gn_tile_off = gemm8p_conv_gn_tiles(rows, w.n);
-          return want_gn;
-        }
-      }
-      // ConvTranspose k2 s2 (a 1x1 GEMM with N = 4 cout whose epilogue scatters 2 x 2 pixels; the decoder's three UpBlocks): the same
-      // kernel's 1x1 form with the scatter in its epilogue -- 33.4 -> 24.6, 59.3 -> 41.9, 63.1 -> 47.3 us at 0.25 degrees, bitwise equal
-      {
-        const int64_t rows = (int64_t)out_h * out_w;
-        if (use_gemm8p && use_dma && !dbg_flags && !p.stat_out && !p.gn_out && w.kh == 1 && w.kw == 1 && stride == 1 && pad_y == 0 && pad_x == 0 &&
-            in_h == out_h && in_w == out_w && !rs && !res && act == 0 && out_mode == 1 && !want_stats && !want_gn && cout > 0 && w.n == 4 * cout &&
-            cout % 64 == 0 && w.cin % 128 == 0 && rwn < 0 && !band_on && rows >= gemm8p_min_rows / 4 && gemm8p_fits(rows, w.n, 2, 5, true)) {
-          Gemm8pParams q;
-          std::memset(&q, 0, sizeof(q));
-          q.a = reinterpret_cast<const bf16_t*>(in); q.lda = in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt);
-          q.M = (int)rows; q.N = w.n; q.K = w.cin; q.bias = p.bias;
-          q.out = reinterpret_cast<bf16_t*>(out); q.out_ld = out_ld; q.sink = stream_sink; q.xcd_part = 1;
-          q.scat_w = out_w; q.cout = cout;
-          cur_family = "gemm8p";
+      if (route == Route::gemm8p_conv || route == Route::gemm8p_convt2) {
+        Gemm8pParams q;
+        std::memset(&q, 0, sizeof(q));
+        q.a = reinterpret_cast<const bf16_t*>(r.in); q.lda = r.in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt);
+        q.M = (int)rows; q.N = w.n; q.K = w.kh * w.kw * w.cin; q.bias = p.bias;
+        q.res = reinterpret_cast<const bf16_t*>(r.res); q.res_ld = r.res_ld;
+        q.out = reinterpret_cast<bf16_t*>(r.out); q.out_ld = r.out_ld; q.sink = stream_sink; q.xcd_part = 1;
+        cur_family = "gemm8p";
+        ++n_gemm8p;
+        if (route == Route::gemm8p_convt2) {
+          q.scat_w = r.out_w; q.cout = r.cout;
           timed(cls, flops, bytes, [&] { launch_gemm8p_convt2<5>(q, cur_stream); });
-          ++n_gemm8p;
-          return false;
+          return {};
         }
+        q.in_h = r.in_h; q.in_w = r.in_w; q.cin = w.cin; q.kh = w.kh; q.kw = w.kw; q.pad_y = r.pad_y; q.pad_x = r.pad_x;
+        q.gn_out = r.want_gn ? gnpart + (int64_t)r.gn_off * w.n : nullptr;
+        timed(cls, flops, bytes, [&] { launch_gemm8p_conv(q, cur_stream); });
+        return {0, r.want_gn ? gemm8p_conv_gn_tiles(rows, w.n) : 0};
       }
-      // LayerNorm-folded 1x1 layers with many rows and K >= 512 (to_qkv, FeedForward layer 1 of stages 2-3): the persistent
-      // 128 x 256-tile kernel; measured per shape against the 128 x 128 kernel in tools/gemm_stream_probe
-      const bool one = w.kh == 1 && w.kw == 1 && stride == 1 && pad_y == 0 && pad_x == 0 && in_h == out_h && in_w == out_w;
-      // K = 512 layers on maps of a few thousand rows (a lat-band rank's share of the 0.25-degree stage 2: 2 000 - 4 000 tokens): the
-      // weight-stationary kernel (wx_gemm_wreg.h: the wave's weight slice in registers, activations streamed tile by tile, one barrier
-      // per tile).  tools/gemm_wreg_probe, M = 2500: to_qkv 11.5 us against 16.1 (persistent kernel) -- at M = 20 000 the two tie, so the
-      // unsharded model keeps the persistent kernel.  Bitwise the same outputs; row partials in N / 32 slots instead of N / 128.
-      const int64_t sel_rows = rule_rows > 0 ? rule_rows : (int64_t)out_h * out_w;   // what the selection rules see (row windows: the whole map)
-      const int64_t st_tok0 = rwn >= 0 && cur_stage >= 0 && cur_stage < 4 ? rw_tok0(cur_stage) : 0;
-      {
-        const int64_t rows = (int64_t)out_h * out_w;
-        const bool ln_v = rs && !res && !want_stats && w.colsum >= 0, res_v = !rs && res && want_stats && fuse_ln && act == 0;
-        if (use_wreg && use_dma && w.wt_kb >= 0 && one && w.cin == 512 && w.n % WREG_BN == 0 && w.bias >= 0 && out_mode == 0 && !want_gn && !dbg_flags &&
-            !blk_hidden && !blk_attn && rwn < 0 && rows >= wreg_min_rows && rows < wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
-            wreg_gemm_ok(rows, w.n, w.cin, p.stat_tiles, ln_v)) {
-          StreamGemmParams q;
-          std::memset(&q, 0, sizeof(q));
-          q.a = reinterpret_cast<const bf16_t*>(in); q.lda = in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt_kb);
-          q.M = (int)rows; q.N = w.n; q.K = w.cin; q.bias = p.bias; q.colsum = p.colsum;
-          q.rowstat = rs; q.stat_tiles = p.stat_tiles; q.stat_inv_c = p.stat_inv_c;
-          q.res = reinterpret_cast<const bf16_t*>(res); q.res_ld = res_ld;
-          q.stat_out = res_v ? stat_dst(rows, w.n / 32) : nullptr; q.stat_slots = w.n / 32;
-          q.out = reinterpret_cast<bf16_t*>(out); q.out_ld = out_ld; q.sink = stream_sink;
-          cur_family = "wreg";
-          timed(cls, flops, bytes, [&] { launch_gemm_wreg(q, res_v ? 3 : (act == 1 ? 2 : 1), cur_stream); });
-          if (res_v) last_stat_slots = q.stat_slots;
-          return res_v;
-        }
-      }
-      // residual layers with N = 512 / 1024 (to_out, FeedForward layer 2 of stages 2 and 3): 160 x 128 tiles, two workgroups per CU
-      // (47.9 vs 58.3 us on layer 2, 21.0 vs 23.2 us on to_out; bitwise equal to the 128 x 128 kernel's output)
-      if (use_stream && use_dma && w.wt_kb >= 0 && one && !rs && res && act == 0 && out_mode == 0 && want_stats && fuse_ln && !want_gn &&
-          !dbg_flags && (w.n == 512 || w.n == 1024) && w.bias >= 0 && sel_rows >= stream_min_rows &&
-          stream_gemm_ok((int64_t)out_h * out_w, w.n, w.cin, 128)) {
+      if (route != Route::conv128) {   // the persistent and weight-stationary kernels: 1x1 layers on the k-blocked weight copy
         StreamGemmParams q;
         std::memset(&q, 0, sizeof(q));
-        q.a = reinterpret_cast<const bf16_t*>(in); q.lda = in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt_kb);
-        q.M = out_h * out_w; q.N = w.n; q.K = w.cin; q.bias = p.bias;
-        q.res = reinterpret_cast<const bf16_t*>(res); q.res_ld = res_ld;
-        q.stat_out = stat_dst(st_tok0 + q.M, w.n / 64) + st_tok0 * (w.n / 64); q.stat_slots = w.n / 64;
-        q.out = reinterpret_cast<bf16_t*>(out); q.out_ld = out_ld; q.sink = stream_sink;
-        q.a_blk = (blk_hidden || blk_attn) ? 1 : 0; q.a_rows = q.M;
-        // experiment switch WX_GEMM8P_FF2=1: FeedForward layer 2 of stage 2 (20 000 x 512 x 2048 from the k-blocked hidden tensor) as one 160 x 256 tile
-        // of 32 K tiles per CU on the eight-phase kernel -- 43.7 against 45.9 us stand-alone (tools/gemm8p_probe), 46.8 against 47.3 inside the step
-        // (operands from HBM instead of a warm L2): a tie, so off.  Bitwise the same output and row partials (64-channel slots either way).
-        if (use_gemm8p && gemm8p_ff2 && blk_hidden && q.N == 512 && q.K >= 2048 && q.K % 128 == 0 && sel_rows >= gemm8p_min_rows && rwn < 0 && !band_on &&
-            gemm8p_fits(q.M, q.N, 2, 5, true)) {
-          Gemm8pParams g;
-          std::memset(&g, 0, sizeof(g));
-          g.a = q.a; g.a_blk = 1; g.a_rows = q.M; g.lda = q.K; g.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt); g.M = q.M; g.N = q.N; g.K = q.K;
-          g.bias = q.bias; g.res = q.res; g.res_ld = q.res_ld; g.stat_out = q.stat_out; g.stat_slots = q.stat_slots;
-          g.out = q.out; g.out_ld = q.out_ld; g.sink = stream_sink; g.xcd_part = 1;
-          cur_family = "gemm8p";
-          timed(cls, flops, bytes, [&] { launch_gemm8p<5>(g, 3, cur_stream); });
-          ++n_gemm8p;
-          last_stat_slots = q.stat_slots;
-          return true;
+        q.a = reinterpret_cast<const bf16_t*>(r.in); q.lda = r.in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt_kb);
+        q.M = (int)rows; q.N = w.n; q.K = w.cin; q.bias = p.bias; q.colsum = p.colsum;
+        q.rowstat = r.rs; q.stat_tiles = p.stat_tiles; q.stat_inv_c = p.stat_inv_c;
+        q.res = reinterpret_cast<const bf16_t*>(r.res); q.res_ld = r.res_ld;
+        q.out = reinterpret_cast<bf16_t*>(r.out); q.out_ld = r.out_ld; q.sink = stream_sink;
+        if (route == Route::wreg) {   // its residual form, or its LayerNorm-folded one
+          q.stat_slots = w.n / 32;
+          q.stat_out = r.res ? stat_dst(rows, q.stat_slots) : nullptr;
+          cur_family = "wreg";
+          timed(cls, flops, bytes, [&] { launch_gemm_wreg(q, r.res ? 3 : (r.act == 1 ? 2 : 1), cur_stream); });
+          return {r.res ? q.stat_slots : 0, 0};
         }
-        // at most one 160 x 128 tile per CU and a deep K (stage 3 of the 0.25-degree model): the loader / consumer form of the kernel
-        const bool lc = use_stream_lc && stream_gemm_lc_pays(sel_rows, q.N, q.K, 5);
+        if (route == Route::stream_ln) {
+          q.o_blk = r.blk != KBlk::none ? 1 : 0; q.o_rows = q.M;
+          // tile per epilogue (tools/gemm_stream_probe, MI355X): with GELU the 160-row tile on a 2-stage ring (256 VGPRs, 2 x 54 KB of
+          // LDS) wins -- 54.6 / 46.8 us on the stage-2 / stage-3 FeedForward shapes against 56.4 / 58.5 -- without it the 128-row tile
+          // on 3 stages does (39.8 vs 46.4 us on to_qkv)
+          cur_family = "stream";
+          timed(cls, flops, bytes, [&] {
+            if (r.act == 1) launch_gemm_stream<5, 2>(q, 2, cur_stream);
+            else launch_gemm_stream<4, 3>(q, 1, cur_stream);
+          });
+          return {};
+        }
+        const int64_t t0 = rwn >= 0 && cur_stage >= 0 && cur_stage < 4 ? rw_tok0(cur_stage) : 0;   // a row window's rows of `statpart`
+        q.stat_slots = w.n / 64;
+        q.stat_out = stat_dst(t0 + rows, q.stat_slots) + t0 * q.stat_slots;
+        q.a_blk = r.blk != KBlk::none ? 1 : 0; q.a_rows = q.M;
+        const bool lc = route == Route::stream_res_lc;
         cur_family = lc ? "stream_lc" : "stream";
         timed(cls, flops, bytes, [&] {
           if (lc) launch_gemm_stream_n128_lc<5, 8>(q, cur_stream);
           else launch_gemm_stream_n128<5, 3, 2>(q, cur_stream);
         });
-        last_stat_slots = q.stat_slots;
-        return true;
-      }
-      if (use_stream && use_dma && w.wt_kb >= 0 && w.n % 256 == 0 && one && rs && !res && out_mode == 0 && !want_stats && !want_gn && !dbg_flags &&
-          sel_rows >= stream_min_rows && stream_gemm_ok((int64_t)out_h * out_w, w.n, w.cin)) {
-        StreamGemmParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.a = reinterpret_cast<const bf16_t*>(in); q.lda = in_ld; q.w = reinterpret_cast<const bf16_t*>(wt_dev + w.wt_kb);
-        q.M = out_h * out_w; q.N = w.n; q.K = w.cin;
-        q.bias = p.bias; q.colsum = p.colsum; q.rowstat = rs; q.stat_tiles = p.stat_tiles; q.stat_inv_c = p.stat_inv_c;
-        q.out = reinterpret_cast<bf16_t*>(out); q.out_ld = out_ld; q.sink = stream_sink;
-        q.o_blk = ((blk_hidden && act == 1) || (blk_attn && act == 0)) ? 1 : 0; q.o_rows = q.M;
-        // tile per epilogue (tools/gemm_stream_probe, MI355X): with GELU the 160-row tile on a 2-stage ring (256 VGPRs, 2 x 54 KB of
-        // LDS) wins -- 54.6 / 46.8 us on the stage-2 / stage-3 FeedForward shapes against 56.4 / 58.5 -- without it the 128-row tile
-        // on 3 stages does (39.8 vs 46.4 us on to_qkv)
-        cur_family = "stream";
-        timed(cls, flops, bytes, [&] {
-          if (act == 1) launch_gemm_stream<5, 2>(q, 2, cur_stream);
-          else launch_gemm_stream<4, 3>(q, 1, cur_stream);
-        });
-        return false;
+        return {q.stat_slots, 0};
       }
     }
-    if (blk_hidden) throw StateError("k-blocked hidden tensor requested but the GEMM fell back to the row-major kernel");
-    if (blk_attn) throw StateError("k-blocked q|k|v / attention output requested but the GEMM fell back to the row-major kernel");
+    if (r.blk == KBlk::hidden) throw StateError("k-blocked hidden tensor requested but the GEMM fell back to the row-major kernel");
+    if (r.blk == KBlk::attn) throw StateError("k-blocked q|k|v / attention output requested but the GEMM fell back to the row-major kernel");
     if (rwn >= 0) throw StateError("row-window launch fell to the generic kernel (the two-stream schedule runs on the persistent GEMMs only)");
+    if (r.par) {   // the four parity convs of a ConvTranspose k4 s2 p1 (out_mode 2): one launch when the fast path takes it
+      if (merge_parity && dma && !dbg_flags && w.n <= 128) {
+        p.n_par = 4;
+        for (int q = 0; q < 4; ++q) p.wt_par[q] = (p.split ? ws_dev : wt_dev) + r.par[q].wt;
+        const double fl4 = 4.0 * 2.0 * m * w.n * w.kh * w.kw * w.cin_true;
+        const double by4 = (4.0 * m * w.n + (double)r.in_h * r.in_w * w.cin_true + 4.0 * w.n * w.kh * w.kw * w.cin) * sizeof(T);
+        if (p.split) ++n_split_gemms;   // the merged launch
+        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, gemm_cfg); });
+        return {};
+      }
+      for (int q = 0; q < 4; ++q) {
+        GemmReq rq = r;
+        rq.par = nullptr; rq.pad_y = r.pad_y - (q >> 1); rq.pad_x = r.pad_x - (q & 1); rq.py = q >> 1; rq.px = q & 1;
+        gemm(cls, r.par[q], rq);
+      }
+      return {};
+    }
+    GemmOut o;
+    if (r.want_stats && fuse_ln && dma) {
+      p.stat_out = statpart;
+      p.stat_stride = r.stat_stride; p.stat_slot0 = r.stat_slot0;
+    }
+    if (r.want_gn && fuse_ln && dma) {
+      p.gn_out = gnpart + (int64_t)r.gn_off * w.n;
+      o.gn_tiles = (int)cdiv(rows, (int64_t)128);
+    }
     // split-K for plain deep-K launches that cannot fill the chip (stage-3 CrossEmbed k = 4: 160 tiles walking K = 8192; every
     // CrossEmbed GEMM of the 1-degree grid): 128 x 128 tiles x S K-ranges, fp32 partial sums, fixed-order finish kernel
-    if (!rs && !res && act == 0 && out_mode == 0 && !p.gn_out && conv_gemm_is_dma<T>(p, zero_page)) {
-      const int S = plain_split_ways(w, (int64_t)out_h * out_w);
+    if (!r.rs && !r.res && r.act == 0 && r.out_mode == 0 && !p.gn_out && dma) {
+      const int S = plain_split_ways(w, rows);
       if (S >= 2) {
-        const size_t need = (size_t)S * out_h * out_w * w.n * sizeof(float);
-        p.partial = splitk_scratch(need);
+        p.partial = splitk_scratch((size_t)S * rows * w.n * sizeof(float));
         p.k_splits = S;
       }
     }
     // ... and for the deep-K 1 x 1 layers of the transformer blocks on maps of a few hundred pixels (1-degree grid, stages 2 - 3:
     // 4 - 12 tiles, each walking 16 - 32 K steps alone on its CU at 0.57 us per step): K ranges of >= skinny_steps steps over up to
     // skinny_max workgroups per tile; the finish kernel applies the whole epilogue (LayerNorm fold, GELU, residual, LN partials)
-    if (split_k && skinny_max >= 2 && use_dma && !p.partial && out_mode == 0 && !p.gn_out && w.kh == 1 && w.kw == 1 && stride == 1 &&
-        w.n % 64 == 0 && (w.cin * (int)sizeof(T)) % 128 == 0 && conv_gemm_is_dma<T>(p, zero_page) && !dbg_flags) {
-      const int64_t tiles = (int64_t)cdiv((int64_t)out_h * out_w, 128) * conv_gemm_n_tiles(w.n);
+    if (split_k && skinny_max >= 2 && !p.partial && r.out_mode == 0 && !p.gn_out && w.kh == 1 && w.kw == 1 && r.stride == 1 &&
+        w.n % 64 == 0 && (w.cin * (int)sizeof(T)) % 128 == 0 && dma && !dbg_flags) {
+      const int64_t tiles = (int64_t)cdiv(rows, (int64_t)128) * conv_gemm_n_tiles(w.n);
       const int nk = w.cin * (int)sizeof(T) / 128;
       // (the tiles the wider lat-band rule adds -- more than skinny_tiles of them -- take at most skinny_max_band K ranges: with 8 the fp32
       // partial sums of a rank's stage-2 FeedForward 2, 8 x 2 600 x 512 floats written and read back, cost more than the shorter K walk
@@ -1675,8 +1666,7 @@ class Engine : public EngineBase {
       // lat-band ranks: a rank's share of the 0.25-degree stage 2 is ~80 tiles walking K = 2048 alone (FeedForward layer 2: 40 us) -- the
       // rule tuned on the 1-degree model (<= 32 tiles) is widened there (slowest of 8 ranks 4.62 -> 4.53 ms)
       if (tiles <= (band_on ? std::max(skinny_tiles, skinny_tiles_band) : skinny_tiles) && nk >= skinny_min_nk && S >= 2) {
-        const size_t need = (size_t)S * out_h * out_w * w.n * sizeof(float);
-        p.partial = splitk_scratch(need);
+        p.partial = splitk_scratch((size_t)S * rows * w.n * sizeof(float));
         p.k_splits = S;
       }
     }
@@ -1685,15 +1675,15 @@ class Engine : public EngineBase {
       // N = 512 -> 628 tiles = 1.23 rounds): 128 x 64 tiles (1 256 of them: 2.45 half-length rounds; three workgroups per CU)
       // (measured, C3: FeedForward 2 of stage 2 2.74 -> 2.36 ms, to_out 1.03 -> 0.88; 64-column tiles EVERYWHERE lose -- to_qkv 1.82 -> 1.99,
       // FeedForward 1 2.59 -> 2.84: half the MFMAs per split activation fragment)
-      if (!p.partial && split_bn64 && conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr) && p.n_par != 4 && w.n >= 96 && w.n % 64 == 0 && (w.n <= 512 || !p.stat_out) && stat_share_stride == 0) {
-        const int64_t tiles = cdiv((int64_t)out_h * out_w, (int64_t)128) * cdiv(w.n, 128);
+      if (!p.partial && split_bn64 && dma && w.n >= 96 && w.n % 64 == 0 && (w.n <= 512 || !p.stat_out) && r.stat_stride == 0) {
+        const int64_t tiles = cdiv(rows, (int64_t)128) * cdiv(w.n, 128);
         const double rounds = (double)tiles / 512.0;
         if (tiles > 512 && rounds < 1.5) p.bn64 = 1;
       }
     }
     timed(cls, flops, bytes, [&] { launch_conv_gemm<T>(p, use_dma ? zero_page : nullptr, cur_stream, gemm_cfg); });
-    last_stat_slots = p.partial ? conv_gemm_finish_slots(w.n) : (p.bn64 ? cdiv(w.n, 64) : conv_gemm_n_tiles(w.n));
-    return made_stats;
+    if (p.stat_out) o.stat_slots = p.partial ? conv_gemm_finish_slots(w.n) : (p.bn64 ? cdiv(w.n, 64) : conv_gemm_n_tiles(w.n));
+    return o;
   }
   void upsample2x(const T* in, int h, int w, int64_t in_ld, int c) {
     constexpr int VEC = 16 / (int)sizeof(T);
@@ -1766,17 +1756,19 @@ class Engine : public EngineBase {
       }
     }
     const float2* rs = qkv_ready ? nullptr : stream_stats(x, ld, c, m);
-    struct Unblk { bool* f; ~Unblk() { *f = false; } } unblk{&blk_attn};   // set below for to_qkv / attention / to_out of this sub-block only
+    KBlk blk = KBlk::none;
     if (a.wsz == 1) {
-      gemm("gemm_qkv", a.vonly, x, h, w, ld, 1, 0, 0, h, w, attn_o, c, rs, 0, nullptr, 0);
+      gemm("gemm_qkv", a.vonly, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = attn_o, .out_ld = c, .rs = rs});
     } else {
       // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
-      // k-blocked (see blk_attn); outputs bitwise the row-major chain's
-      blk_attn = sizeof(T) == 2 && attn_blk_on && use_stream && use_dma && fuse_ln && !dbg_flags && !dbg_on && !band_on && rwn < 0 && cfg.dim_head == 32 &&
-                 !qkv_ready && !defer_out && attn_kind_override < 0 && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
-                 (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0;
-      if (blk_attn) ++n_attn_blk;
-      if (!qkv_ready) gemm("gemm_qkv", a.qkv, x, h, w, ld, 1, 0, 0, h, w, scratch, 3 * c, rs, 0, nullptr, 0);
+      // k-blocked (see KBlk); outputs bitwise the row-major chain's
+      if (sizeof(T) == 2 && attn_blk_on && use_stream && use_dma && fuse_ln && !dbg_flags && !dbg_on && !band_on && rwn < 0 && cfg.dim_head == 32 &&
+          !qkv_ready && !defer_out && attn_kind_override < 0 && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
+          (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
+        blk = KBlk::attn;
+        ++n_attn_blk;
+      }
+      if (!qkv_ready) gemm("gemm_qkv", a.qkv, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 3 * c, .rs = rs, .blk = blk});
       AttnParams p;
       p.trace = nullptr;
       p.qkv = scratch; p.ld_qkv = 3 * c; p.out = attn_o; p.ld_out = c; p.bias = f_dev + a.bias_tab; p.tb = a.bias_tb >= 0 ? f_dev + a.bias_tb : nullptr;
@@ -1784,7 +1776,7 @@ class Engine : public EngineBase {
       p.scale = (float)(1.0 / std::sqrt((double)cfg.dim_head));   // fp32 engine only: the bf16 engine's q already carries scale * log2(e)
       p.pack = attn_pack(a.wsz);
       p.mma3 = split_mma ? 1 : 0;
-      p.blk = blk_attn ? 1 : 0;
+      p.blk = blk == KBlk::attn ? 1 : 0;
       const double n = (double)a.wsz * a.wsz;
       timed("window_attn", 4.0 * m * n * c, 4.0 * m * c * sizeof(T), [&] {
         if (cfg.dim_head == 32) launch_window_attn<T>(p, cur_stream, attn_split);
@@ -1794,8 +1786,8 @@ class Engine : public EngineBase {
     }
     capture(dbg_name + ".attn", attn_o, h, w, c, c, w);
     if (defer_out) return;
-    const bool st = gemm("gemm_out", a.out, attn_o, h, w, c, 1, 0, 0, h, w, x, ld, nullptr, 0, x, ld, 0, 0, 0, 0, true);
-    stat_tiles_ready = st ? last_stat_slots : 0;
+    stat_tiles_ready = gemm("gemm_out", a.out, {.in = attn_o, .in_h = h, .in_w = w, .in_ld = c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
+                                                .blk = blk, .want_stats = true}).stat_slots;
     capture(dbg_name, x, h, w, c, ld, w);
   }
   // The fused feed-forward kernel gives every workgroup 128 (C = 128) or 64 (C = 256) pixels: below one workgroup per CU the
@@ -1841,113 +1833,90 @@ class Engine : public EngineBase {
     return sizeof(T) == 2 && ff_split_max >= 2 && !pre && f.pack >= 0 && fuse_ff && fuse_ln && !band_on && !dbg_flags &&
            ff_fused_supported(c, 4 * c) && small_map_tokens(s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
   }
+  // the form of a FeedForward (feedforward() below):
+  //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
+  //               attention's LayerNorm + to_qkv behind) form
+  //   split       bf16, launch-bound maps: the fused block with its hidden dimension split, and the split-K finish kernel
+  //   wide_split  bf16, C = 512 on lat-band ranks (WX_FF_WIDE=1): the same at C = 512
+  //   wide        bf16, C = 512 on the unsharded map (WX_FF_WIDE=2): the plain one-launch block
+  //   split_bf16  split-bf16 precision, C = 128 / 256: both layers in one launch (wx_ff_split.h), plain / PRE / POST
+  //   chain       ff1 + ff2 on gemm()
+  enum class FFForm { fused, split, wide_split, wide, split_bf16, chain };
+  FFForm ff_form(const FFL& f, int s, const AttnL* pre) const {
+    if (sizeof(T) == 2) {
+      if (ff_split_ok(f, s, pre)) return FFForm::split;
+      if (f.pack >= 0 && fuse_ff && ff_big_enough()) return FFForm::fused;
+      const bool wide_ok = f.pack_wide >= 0 && !pre && fuse_ff && fuse_ln && !dbg_flags && rwn < 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
+      if (wide_ok && band_on && cdiv((int64_t)rw_rows(s) * sw[s], (int64_t)64) <= 128) return FFForm::wide_split;
+      if (wide_ok && !band_on && ff_wide >= 2) return FFForm::wide;
+    } else if (ff_split_fused_ok(f, cfg.dim[s])) {
+      return FFForm::split_bf16;
+    }
+    return FFForm::chain;
+  }
   void feedforward(const FFL& f, int s, const std::string& dbg_name, const AttnL* pre = nullptr) {
     const int c = cfg.dim[s], h = rw_rows(s), w = sw[s], m = h * w;
     const int64_t ld = stream_ld(s), t0 = rw_tok0(s);
     T* x = stream_ptr(s) + t0 * ld;
     T* const scratch = this->scratch + t0 * 4 * c;   // the window's own hidden tensor
-    if (rwn >= 0 && (pre || (sizeof(T) == 2 && f.pack >= 0 && fuse_ff && ff_big_enough())))
-      throw StateError("fused feed-forward on a row window");
+    const FFForm form = ff_form(f, s, pre);
+    if (rwn >= 0 && (pre || form != FFForm::chain)) throw StateError("fused feed-forward on a row window");
+    if (pre && form != FFForm::fused && form != FFForm::split_bf16) throw StateError("feedforward: out-projection deferred to a layer that cannot take it");
     if constexpr (sizeof(T) == 2) {
-      if (f.pack >= 0 && fuse_ff && ff_big_enough() && !ff_split_ok(f, s, pre)) {
+      auto block_params = [&](int64_t pack) {   // the one-launch block's operands
         FFParams fp{};
         fp.x = reinterpret_cast<const bf16_t*>(x); fp.ld = ld; fp.out = reinterpret_cast<bf16_t*>(x); fp.out_ld = ld;
+        fp.M = m; fp.hidden = 4 * c; fp.wpack = reinterpret_cast<const char*>(wt_dev + pack);
+        fp.cs1 = f_dev + f.w1.colsum; fp.b1 = f_dev + f.w1.bias; fp.b2 = f_dev + f.w2.bias;
+        return fp;
+      };
+      // the fused block with the hidden dimension cut into S ranges over blockIdx.y -- every workgroup streams 1/S of W1 | W2 instead of
+      // all of it -- and the split-K finish kernel behind it (+ b2 + residual, rounding, LayerNorm partials): two launches instead of
+      // ff1 + ff2 (+ finish)
+      auto hidden_split = [&](int64_t pack, int S) {
+        const int nch = 4 * c / 32, ch_per = cdiv(nch, S), S_eff = cdiv(nch, ch_per);
+        splitk_scratch((size_t)S_eff * m * c * sizeof(float));
+        FFParams fp = block_params(pack);
+        fp.partial = splitk_buf; fp.ch_per = ch_per;
+        ConvGemmParams q;
+        std::memset(&q, 0, sizeof(q));
+        q.out_h = h; q.out_w = w; q.n = c; q.partial = splitk_buf; q.k_splits = S_eff;
+        q.bias = f_dev + f.w2.bias; q.res = x; q.res_ld = ld; q.out = x; q.out_ld = ld; q.stat_out = statpart;
+        timed("ff_fused_split", 16.0 * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] {
+          launch_ff_fused_split(c, fp, zero_page, cur_stream);
+          const int64_t waves = (int64_t)m * conv_gemm_finish_slots(c);
+          hipLaunchKernelGGL(conv_gemm_finish_kernel<T>, dim3((unsigned)cdiv(waves, (int64_t)4)), dim3(256), 0, cur_stream, q);
+          WX_HIP(hipGetLastError());
+        });
+        stat_tiles_ready = conv_gemm_finish_slots(c);
+      };
+      if (form == FFForm::fused) {
         const bool post = pre && ff_makes_qkv(f);
-        fp.M = m; fp.hidden = 4 * c; fp.wpack = reinterpret_cast<const char*>(wt_dev + (post ? f.pack_pp : pre ? f.pack_pre : f.pack));
+        FFParams fp = block_params(post ? f.pack_pp : pre ? f.pack_pre : f.pack);
         fp.qkv = post ? reinterpret_cast<bf16_t*>(scratch) : nullptr; fp.ld_qkv = 3 * c;
         fp.csq = post ? f_dev + f.next->qkv.colsum : nullptr; fp.bq = post ? f_dev + f.next->qkv.bias : nullptr;
         fp.o = pre ? reinterpret_cast<const bf16_t*>(attn_o) : nullptr; fp.ld_o = c; fp.bo = pre ? f_dev + pre->out.bias : nullptr;
-        fp.cs1 = f_dev + f.w1.colsum; fp.b1 = f_dev + f.w1.bias; fp.b2 = f_dev + f.w2.bias;
         fp.stat_out = fuse_ln ? statpart : nullptr; fp.dbg = ff_dbg;
         timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, (c == 128 && !pre && ff_small_px64 && cdiv(m, 128) < 128) ? 3 : ff_variant); });
         stat_tiles_ready = fuse_ln ? 1 : 0;
-        capture(dbg_name, x, h, w, c, ld, w);
-        return;
-      }
-    }
-    if constexpr (sizeof(T) == 2) {
-      // launch-bound maps (1-degree grid, C = 128 / 256 stages of 23 - 45 pixel tiles): the fused block with the hidden dimension cut over
-      // blockIdx.y -- every workgroup streams 1/S of W1 | W2 instead of all of it -- and the split-K finish kernel behind it
-      // (+ b2 + residual, rounding, LayerNorm partials): two launches instead of ff1 + ff2 + finish
-      const int nch = 4 * c / 32;
-      if (ff_split_ok(f, s, pre)) {
-        const int S = std::min(ff_split_max, nch / 4);
-        const int ch_per = cdiv(nch, S), S_eff = cdiv(nch, ch_per);
-        const size_t need = (size_t)S_eff * m * c * sizeof(float);
-        splitk_scratch(need);
-        FFParams fp{};
-        fp.x = reinterpret_cast<const bf16_t*>(x); fp.ld = ld; fp.out = reinterpret_cast<bf16_t*>(x); fp.out_ld = ld;
-        fp.M = m; fp.hidden = 4 * c; fp.wpack = reinterpret_cast<const char*>(wt_dev + f.pack);
-        fp.cs1 = f_dev + f.w1.colsum; fp.b1 = f_dev + f.w1.bias; fp.b2 = f_dev + f.w2.bias;
-        fp.partial = splitk_buf; fp.ch_per = ch_per;
-        ConvGemmParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.out_h = h; q.out_w = w; q.n = c; q.partial = splitk_buf; q.k_splits = S_eff;
-        q.bias = f_dev + f.w2.bias; q.res = x; q.res_ld = ld; q.out = x; q.out_ld = ld; q.stat_out = statpart;
-        timed("ff_fused_split", 16.0 * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] {
-          launch_ff_fused_split(c, fp, zero_page, cur_stream);
-          const int64_t waves = (int64_t)m * conv_gemm_finish_slots(c);
-          hipLaunchKernelGGL(conv_gemm_finish_kernel<T>, dim3((unsigned)cdiv(waves, (int64_t)4)), dim3(256), 0, cur_stream, q);
-          WX_HIP(hipGetLastError());
-        });
-        stat_tiles_ready = conv_gemm_finish_slots(c);
-        capture(dbg_name, x, h, w, c, ld, w);
-        return;
-      }
-    }
-    if constexpr (sizeof(T) == 2) {
-      // C = 512 (wx_ff.h ff_wide_supported).  Lat-band ranks: a band of 2 000 - 4 000 stage-2 tokens is 32 - 63 pixel tiles -- the hidden
-      // dimension is cut into S ranges so that ~ff_wide_wgs workgroups each stream 1 / S of W1 | W2, and the split-K finish kernel adds the
-      // ranges (+ b2 + residual, rounding, LayerNorm partials): two launches and no hidden tensor instead of ff1 + split-K ff2 + finish.
-      // WX_FF_WIDE=2 also runs the plain one-launch block on the unsharded map (an experiment; it loses there).
-      const int tiles = (int)cdiv(m, 64);
-      const bool wide_ok = f.pack_wide >= 0 && !pre && fuse_ff && fuse_ln && !dbg_flags && rwn < 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
-      if (wide_ok && band_on && tiles <= 128) {
-        const int nch = 4 * c / 32;
-        const int S = std::min(8, std::max(2, (int)cdiv(ff_wide_wgs, tiles)));
-        const int ch_per = cdiv(nch, S), S_eff = cdiv(nch, ch_per);
-        const size_t need = (size_t)S_eff * m * c * sizeof(float);
-        splitk_scratch(need);
-        FFParams fp{};
-        fp.x = reinterpret_cast<const bf16_t*>(x); fp.ld = ld; fp.out = reinterpret_cast<bf16_t*>(x); fp.out_ld = ld;
-        fp.M = m; fp.hidden = 4 * c; fp.wpack = reinterpret_cast<const char*>(wt_dev + f.pack_wide);
-        fp.cs1 = f_dev + f.w1.colsum; fp.b1 = f_dev + f.w1.bias; fp.b2 = f_dev + f.w2.bias;
-        fp.partial = splitk_buf; fp.ch_per = ch_per;
-        ConvGemmParams q;
-        std::memset(&q, 0, sizeof(q));
-        q.out_h = h; q.out_w = w; q.n = c; q.partial = splitk_buf; q.k_splits = S_eff;
-        q.bias = f_dev + f.w2.bias; q.res = x; q.res_ld = ld; q.out = x; q.out_ld = ld; q.stat_out = statpart;
+      } else if (form == FFForm::split) {   // launch-bound maps (1-degree grid, C = 128 / 256 stages of 23 - 45 pixel tiles)
+        hidden_split(f.pack, std::min(ff_split_max, 4 * c / 32 / 4));
+      } else if (form == FFForm::wide_split) {
+        // C = 512 (wx_ff.h ff_wide_supported) on lat-band ranks: a band of 2 000 - 4 000 stage-2 tokens is 32 - 63 pixel tiles -- S ranges
+        // so that ~ff_wide_wgs workgroups run, instead of ff1 + split-K ff2 + finish
         ++n_ff_wide;
-        timed("ff_fused_split", 16.0 * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] {
-          launch_ff_fused_split(c, fp, zero_page, cur_stream);
-          const int64_t waves = (int64_t)m * conv_gemm_finish_slots(c);
-          hipLaunchKernelGGL(conv_gemm_finish_kernel<T>, dim3((unsigned)cdiv(waves, (int64_t)4)), dim3(256), 0, cur_stream, q);
-          WX_HIP(hipGetLastError());
-        });
-        stat_tiles_ready = conv_gemm_finish_slots(c);
-        last_stat_slots = stat_tiles_ready;
-        capture(dbg_name, x, h, w, c, ld, w);
-        return;
-      }
-      if (wide_ok && !band_on && ff_wide >= 2) {
-        FFParams fp{};
-        fp.x = reinterpret_cast<const bf16_t*>(x); fp.ld = ld; fp.out = reinterpret_cast<bf16_t*>(x); fp.out_ld = ld;
-        fp.M = m; fp.hidden = 4 * c; fp.wpack = reinterpret_cast<const char*>(wt_dev + f.pack_wide);
-        fp.cs1 = f_dev + f.w1.colsum; fp.b1 = f_dev + f.w1.bias; fp.b2 = f_dev + f.w2.bias;
+        hidden_split(f.pack_wide, std::min(8, std::max(2, (int)cdiv(ff_wide_wgs, (int)cdiv(m, 64)))));
+      } else if (form == FFForm::wide) {   // an experiment: it loses on the unsharded map
+        FFParams fp = block_params(f.pack_wide);
         fp.stat_out = statpart;
         ++n_ff_wide;
         timed("ff_fused", 16.0 * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, 0); });
         stat_tiles_ready = 1;
-        last_stat_slots = 1;
-        capture(dbg_name, x, h, w, c, ld, w);
-        return;
       }
     }
-    if (pre && !(sizeof(T) == 4 && ff_split_fused_ok(f, c))) throw StateError("feedforward: out-projection deferred to a layer that cannot take it");
-    const float2* rs = pre ? nullptr : stream_stats(x, ld, c, m);   // the PRE form takes the statistics of x1 itself
     if constexpr (sizeof(T) == 4) {
-      // split-bf16 precision, C = 128 / 256: both layers in one launch, the hidden tensor stays in registers (wx_ff_split.h)
-      if (ff_split_fused_ok(f, c)) {
+      if (form == FFForm::split_bf16) {   // the hidden tensor stays in registers
+        const float2* rs = pre ? nullptr : stream_stats(x, ld, c, m);   // the PRE form takes the statistics of x1 itself
         FFSplitParams q{};
         q.x = reinterpret_cast<float*>(x); q.ld = ld; q.M = m; q.hidden = 4 * c;
         q.w1s = reinterpret_cast<const float*>(ws_dev + f.w1.wt); q.b1 = f_dev + f.w1.bias;
@@ -1979,33 +1948,28 @@ class Engine : public EngineBase {
         timed(post ? "out_ff_qkv_split_fused" : pre ? "out_ff_split_fused" : "ff_split_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c,
               (post ? 6.0 : pre ? 3.0 : 2.0) * m * c * sizeof(T) + (post ? 12.0 : pre ? 9.0 : 8.0) * c * c * sizeof(T), [&] { launch_ff_split(c, q, cur_stream, ff_split_tw ? ff_split_tw : (cdiv(m, 128) >= 512 ? 2 : 1)); });
         stat_tiles_ready = q.stat_out ? 1 : 0;
-        last_stat_slots = 1;
-        capture(dbg_name, x, h, w, c, ld, w);
-        return;
       }
     }
-    // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
-    blk_hidden = sizeof(T) == 2 && use_stream && use_dma && fuse_ln && !dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
-                 (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && f.w2.bias >= 0;
-    gemm("gemm_ff1", f.w1, x, h, w, ld, 1, 0, 0, h, w, scratch, 4 * c, rs, 1, nullptr, 0);
-    const bool st = gemm("gemm_ff2", f.w2, scratch, h, w, 4 * c, 1, 0, 0, h, w, x, ld, nullptr, 0, x, ld, 0, 0, 0, 0, true);
-    blk_hidden = false;
-    stat_tiles_ready = st ? last_stat_slots : 0;
+    if (form == FFForm::chain) {
+      const float2* rs = stream_stats(x, ld, c, m);
+      // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
+      const KBlk blk = sizeof(T) == 2 && use_stream && use_dma && fuse_ln && !dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
+                       (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
+      gemm("gemm_ff1", f.w1, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 4 * c, .rs = rs, .act = 1, .blk = blk});
+      stat_tiles_ready = gemm("gemm_ff2", f.w2, {.in = scratch, .in_h = h, .in_w = w, .in_ld = 4 * c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
+                                                 .blk = blk, .want_stats = true}).stat_slots;
+    }
     capture(dbg_name, x, h, w, c, ld, w);
   }
-  int stat_share_stride = 0, stat_share_slot0 = 0;   // LN partials of several launches into one row of `statpart` (cross_embed)
-  int gn_tile_off = 0;      // tiles already written to gnpart by earlier launches of the same conv (gn_accum)
-  bool gn_accum = false;
-  void gn_local_stats(const T* x, int c, int64_t m, bool have_partials) {   // -> gn_acc[2c] (sum, sum sq) in fp64
+  // -> gn_acc[2c] (sum, sum sq) in fp64; tiles > 0: the producing conv's epilogue left that many per-tile (sum, sum sq) in gnpart
+  void gn_local_stats(const T* x, int c, int64_t m, int tiles) {
     constexpr int VEC = 16 / (int)sizeof(T);
     if (c / VEC > 256) throw ConfigError("GroupNorm width unsupported");
-    if (have_partials) {  // the producing conv's epilogue left per-tile (sum, sum sq): just fold them
-      const int tiles = gn_tile_off > 0 ? gn_tile_off : cdiv(m, 128);
+    if (tiles > 0) {  // just fold them
       timed("gn_stats", 0.0, (double)tiles * c * 8.0, [&] {
         hipLaunchKernelGGL(gn_fold_partials_kernel, dim3(c), dim3(256), 0, cur_stream, gnpart, tiles, c, gn_acc);
         WX_HIP(hipGetLastError());
       });
-      gn_tile_off = 0;
     } else {
       WX_HIP(hipMemsetAsync(gn_acc, 0, 2 * c * sizeof(double), cur_stream));
       const int rows_per_block = 256 / (c / VEC);
@@ -2032,16 +1996,12 @@ class Engine : public EngineBase {
   }
   int gn_fold_max_tiles = getenv("WX_GN_FOLD_TILES") ? atoi(getenv("WX_GN_FOLD_TILES")) : 16;   // 12 tiles: 13 -> 9 us; 45 tiles: 13 -> 17 us (the serial fold in every workgroup)
   void group_norm_silu(const T* x, int c, int64_t m, int64_t g_off, int64_t b_off, const T* res, int64_t res_ld, T* out,
-                       int64_t out_ld, bool have_partials) {
-    if (have_partials) {   // few tiles: the apply kernel folds the partials itself (one launch instead of two)
-      const int tiles = gn_tile_off > 0 ? gn_tile_off : (int)cdiv(m, 128);
-      if (tiles <= gn_fold_max_tiles) {
-        gn_tile_off = 0;
-        gn_finalize_apply(x, c, m, m, g_off, b_off, res, res_ld, out, out_ld, tiles);
-        return;
-      }
+                       int64_t out_ld, int tiles) {   // tiles: the producing conv's GroupNorm partials (gn_local_stats)
+    if (tiles > 0 && tiles <= gn_fold_max_tiles) {   // few tiles: the apply kernel folds the partials itself (one launch instead of two)
+      gn_finalize_apply(x, c, m, m, g_off, b_off, res, res_ld, out, out_ld, tiles);
+      return;
     }
-    gn_local_stats(x, c, m, have_partials);
+    gn_local_stats(x, c, m, tiles);
     gn_finalize_apply(x, c, m, m, g_off, b_off, res, res_ld, out, out_ld);
   }
 
@@ -2079,9 +2039,8 @@ class Engine : public EngineBase {
     if (s >= 1 && st.merged.wt >= 0 && embed_merge && !band_on) {
       const int k = st.embed_k.back(), stv = cfg.embed_strides[s], pd = (k - stv) / 2;
       // ... which also leaves the LayerNorm partials of its rows for the stage's first sub-block
-      const bool made = gemm("gemm_embed", st.merged, in, in_h, sw[s - 1], in_ld_s, stv, pd + in_row0, pd, sh[s], sw[s], x, ld, nullptr, 0, nullptr, 0,
-                             0, 0, 0, 0, true);
-      stat_tiles_ready = made ? last_stat_slots : 0;
+      stat_tiles_ready = gemm("gemm_embed", st.merged, {.in = in, .in_h = in_h, .in_w = sw[s - 1], .in_ld = in_ld_s, .out = x, .out_ld = ld, .stride = stv,
+                                                        .pad_y = pd + in_row0, .pad_x = pd, .out_h = sh[s], .out_w = sw[s], .want_stats = true}).stat_slots;
       return;
     }
     // stages 1-3: every branch's epilogue (or split-K finish) leaves the LayerNorm partials of ITS channel range in the shared row of
@@ -2176,15 +2135,14 @@ class Engine : public EngineBase {
           side_open = true;
         }
         struct Back { Engine* e; hipStream_t s; ~Back() { e->cur_stream = s; } } back{this, main_s};
-        gemm("gemm_embed", st.embed[b], in, in_h, Wp + 2 * halo, cpad0, stv, pd - halo, pd - halo, sh[0], sw[0],
-             x + choff, ld, nullptr, 0, nullptr, 0);
+        gemm("gemm_embed", st.embed[b], {.in = in, .in_h = in_h, .in_w = Wp + 2 * halo, .in_ld = cpad0, .out = x + choff, .out_ld = ld, .stride = stv,
+                                         .pad_y = pd - halo, .pad_x = pd - halo, .out_h = sh[0], .out_w = sw[0]});
       } else {
-        if (share) { stat_share_stride = total_slots; stat_share_slot0 = slot_at; }
-        const bool made = gemm("gemm_embed", st.embed[b], in, in_h, sw[s - 1], in_ld_s, stv, pd + in_row0, pd, sh[s], sw[s],
-                               x + choff, ld, nullptr, 0, nullptr, 0, 0, 0, 0, 0, share);
-        stat_share_stride = stat_share_slot0 = 0;
-        if (share && made && last_stat_slots != slots[b]) throw StateError("cross_embed: LayerNorm partial slots of a branch differ from the prediction");
-        all_made = all_made && made;
+        const int made = gemm("gemm_embed", st.embed[b], {.in = in, .in_h = in_h, .in_w = sw[s - 1], .in_ld = in_ld_s, .out = x + choff, .out_ld = ld,
+                                                          .stride = stv, .pad_y = pd + in_row0, .pad_x = pd, .out_h = sh[s], .out_w = sw[s], .want_stats = share,
+                                                          .stat_stride = share ? total_slots : 0, .stat_slot0 = share ? slot_at : 0}).stat_slots;
+        if (share && made && made != slots[b]) throw StateError("cross_embed: LayerNorm partial slots of a branch differ from the prediction");
+        all_made = all_made && made > 0;
         slot_at += slots[b];
       }
       choff += st.embed[b].n;
@@ -2258,13 +2216,13 @@ class Engine : public EngineBase {
     auto join = [&] { WX_HIP(hipEventRecord(ev_join, side_stream)); WX_HIP(hipStreamWaitEvent(main_s, ev_join, 0)); };
     // the (host-side) LayerNorm-partial bookkeeping of a chain: both halves start from the same state and must end in the same one
     auto half = [&](int r0, int rn, hipStream_t strm, auto&& body) {
-      const int save_ready = stat_tiles_ready, save_slots = last_stat_slots;
+      const int save_ready = stat_tiles_ready;
       rw0 = r0; rwn = rn; cur_stream = strm;
       body();
       rw0 = 0; rwn = -1; cur_stream = main_s;
-      const int end_ready = stat_tiles_ready, end_slots = last_stat_slots;
-      stat_tiles_ready = save_ready; last_stat_slots = save_slots;
-      return std::make_pair(end_ready, end_slots);
+      const int end_ready = stat_tiles_ready;
+      stat_tiles_ready = save_ready;
+      return end_ready;
     };
     // A fork is safe only while both halves keep ONE LayerNorm-partial layout: statpart is [token][slots], a half's region starts at
     // (its first token) x slots, and the residual layers of a half leave dim / 64 slots per row (the persistent GEMM's N tiles).  When the
@@ -2280,7 +2238,7 @@ class Engine : public EngineBase {
       const auto eb = half(rows_a, rows_b, side_stream, body);
       join();
       if (ea != eb) throw StateError("two-stream schedule: the halves left different LayerNorm-partial states");
-      stat_tiles_ready = ea.first; last_stat_slots = ea.second;
+      stat_tiles_ready = ea;
     };
     if (pointwise_long) {
       size_t first = 0;
@@ -2452,22 +2410,20 @@ class Engine : public EngineBase {
       T *scut = dtmp[0], *ta = dtmp[1], *tb = dtmp[2];
       if (cfg.arch == WX_ARCH_WXFORMER) {
         // x = PixelShuffle(conv3x3(x)); x = x + sharp(x)   (wxformer/crossformer.py:157-158)
-        gemm("gemm_convPS", u.convps, in, sh[si], sw[si], in_ld, 1, 1, 1, sh[si], sw[si], dtmp[3], u.cout, nullptr, 0, nullptr, 0, 1,
-             u.cout);
-        gemm("gemm_conv3", u.sharp, dtmp[3], sh[so], sw[so], u.cout, 1, 1, 1, sh[so], sw[so], scut, u.cout, nullptr, 0, dtmp[3],
-             u.cout);
+        gemm("gemm_convPS", u.convps, {.in = in, .in_h = sh[si], .in_w = sw[si], .in_ld = in_ld, .out = dtmp[3], .out_ld = u.cout, .out_mode = 1,
+                                       .cout = u.cout});
+        gemm("gemm_conv3", u.sharp, {.in = dtmp[3], .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = scut, .out_ld = u.cout, .res = dtmp[3],
+                                     .res_ld = u.cout});
       } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
         upsample2x(in, sh[si], sw[si], in_ld, u.cin);
-        gemm("gemm_conv3", u.upc, upbuf, sh[so], sw[so], u.cin, 1, 1, 1, sh[so], sw[so], scut, u.cout, nullptr, 0, nullptr, 0);
+        gemm("gemm_conv3", u.upc, {.in = upbuf, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cin, .out = scut, .out_ld = u.cout});
       } else {
-        gemm("gemm_convT2", u.convt, in, sh[si], sw[si], in_ld, 1, 0, 0, sh[si], sw[si], scut, u.cout, nullptr, 0, nullptr, 0, 1, u.cout);
+        gemm("gemm_convT2", u.convt, {.in = in, .in_h = sh[si], .in_w = sw[si], .in_ld = in_ld, .out = scut, .out_ld = u.cout, .out_mode = 1, .cout = u.cout});
       }
-      bool gp = gemm("gemm_conv3", u.c1, scut, sh[so], sw[so], u.cout, 1, 1, 1, sh[so], sw[so], ta, u.cout, nullptr, 0, nullptr, 0,
-                     0, 0, 0, 0, false, true);
-      group_norm_silu(ta, u.cout, mo, u.g1, u.b1, nullptr, 0, tb, u.cout, gp);
-      gp = gemm("gemm_conv3", u.c2, tb, sh[so], sw[so], u.cout, 1, 1, 1, sh[so], sw[so], ta, u.cout, nullptr, 0, nullptr, 0,
-                0, 0, 0, 0, false, true);
-      group_norm_silu(ta, u.cout, mo, u.g2, u.b2, scut, u.cout, cat[so], 2 * cfg.dim[so], gp);
+      int tiles = gemm("gemm_conv3", u.c1, {.in = scut, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = ta, .out_ld = u.cout, .want_gn = true}).gn_tiles;
+      group_norm_silu(ta, u.cout, mo, u.g1, u.b1, nullptr, 0, tb, u.cout, tiles);
+      tiles = gemm("gemm_conv3", u.c2, {.in = tb, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = ta, .out_ld = u.cout, .want_gn = true}).gn_tiles;
+      group_norm_silu(ta, u.cout, mo, u.g2, u.b2, scut, u.cout, cat[so], 2 * cfg.dim[so], tiles);
       capture("up_block" + std::to_string(i + 1), cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
       if (noise_slot_on(3 + i)) {       // before the concat: the up block's half of cat[so]
         noise_inject(3 + i, cat[so], 2 * cfg.dim[so], sh[so], sw[so]);
@@ -2476,15 +2432,16 @@ class Engine : public EngineBase {
     }
     cur_stage = 7;
     if (cfg.arch == WX_ARCH_WXFORMER) {
-      gemm("gemm_convPS", ps4, cat[0], sh[0], sw[0], 2 * cfg.dim[0], 1, 1, 1, sh[0], sw[0], ps4_buf, cpad4, nullptr, 0, nullptr, 0, 1,
-           cpad4);
-      gemm("gemm_conv3", fin4, ps4_buf, Hd, Wd, cpad4, 1, 1, 1, Hd, Wd, dec, ld_dec, nullptr, 0, nullptr, 0);
+      gemm("gemm_convPS", ps4, {.in = cat[0], .in_h = sh[0], .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = ps4_buf, .out_ld = cpad4, .out_mode = 1,
+                                .cout = cpad4});
+      gemm("gemm_conv3", fin4, {.in = ps4_buf, .in_h = Hd, .in_w = Wd, .in_ld = cpad4, .out = dec, .out_ld = ld_dec});
     } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
       upsample2x(cat[0], sh[0], sw[0], 2 * cfg.dim[0], 2 * cfg.dim[0]);
-      gemm("gemm_conv3", up4c, upbuf, Hd, Wd, 2 * cfg.dim[0], 1, 1, 1, Hd, Wd, dec, ld_dec, nullptr, 0, nullptr, 0);
+      gemm("gemm_conv3", up4c, {.in = upbuf, .in_h = Hd, .in_w = Wd, .in_ld = 2 * cfg.dim[0], .out = dec, .out_ld = ld_dec});
     } else {
-      gemm_par = up4;   // pads (1 - py, 1 - px), output pixel (2 oy + py, 2 ox + px): gemm() runs the four parities (merged when it can)
-      gemm("gemm_convT4", up4[0], cat[0], sh[0], sw[0], 2 * cfg.dim[0], 1, 1, 1, sh[0], sw[0], dec, ld_dec, nullptr, 0, nullptr, 0, 2, 0, 0, 0);
+      // pads (1 - py, 1 - px), output pixel (2 oy + py, 2 ox + px): gemm() runs the four parities (merged when it can)
+      gemm("gemm_convT4", up4[0], {.in = cat[0], .in_h = sh[0], .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = dec, .out_ld = ld_dec, .pad_y = 1,
+                                   .pad_x = 1, .out_mode = 2, .par = up4});
     }
     capture("up_block4", dec, Hd, Wd, C_out, ld_dec, Wd);
   }
@@ -2874,9 +2831,9 @@ class Engine : public EngineBase {
     b_unpack_slots = 0;
   }
   // GroupNorm: local (sum, sum sq) -> gn_acc
-  void band_gn_local(const T* x, int c, int64_t m, bool have_partials) {
+  void band_gn_local(const T* x, int c, int64_t m, int tiles) {
     if (m <= 0) { WX_HIP(hipMemsetAsync(gn_acc, 0, 2 * c * sizeof(double), cur_stream)); return; }
-    gn_local_stats(x, c, m, have_partials);
+    gn_local_stats(x, c, m, tiles);
   }
   void band_gn_finish(const T* x, int c, int64_t m_local, int64_t m_global, int64_t g_off, int64_t b_off, const T* res, int64_t res_ld,
                       T* out, int64_t out_ld) {
@@ -2888,33 +2845,26 @@ class Engine : public EngineBase {
   // A 3x3 conv (+ GroupNorm partials) over a band whose input buffer carries one halo row above and below (rows + 2 buffer rows).
   // Output rows 1 .. rows - 2 need no halo: they are launched as the op's `pre` part, right after the halo exchange was packed
   // (boundary = false); the two outer rows follow once the halo rows have arrived (boundary = true).  The GroupNorm tile
-  // partials of the three launches are appended to one list and folded together.
-  bool band_conv3_rows(const ConvW& w, const T* in, T* out, int rows, int wd, int c, bool boundary) {
-    if (rows <= 0) { if (boundary) gn_tile_off = 0; return false; }
+  // partials of the three launches are appended to one list and folded together.  Returns the boundary call's tile count for
+  // band_gn_local (0: no partials -- it falls back to the two-pass statistics kernel).
+  int b_gn_tiles = 0;   // tiles the interior launch of the current conv wrote (boundary = false)
+  int band_conv3_rows(const ConvW& w, const T* in, T* out, int rows, int wd, int c, bool boundary) {
     const int64_t row = (int64_t)wd * c;
     const bool split = b_split && rows >= 4;
-    bool gp = false;
+    auto conv = [&](const T* src, int out_rows, T* dst, bool gn, int gn_off) {   // output rows of dst from rows out_rows + 2 of src
+      return gemm("gemm_conv3", w, {.in = src, .in_h = out_rows + 2, .in_w = wd, .in_ld = c, .out = dst, .out_ld = c, .pad_y = 0, .out_h = out_rows,
+                                    .want_gn = gn, .gn_off = gn_off}).gn_tiles;
+    };
     if (!boundary) {
-      gn_tile_off = 0;
-      if (!split) return false;
-      gn_accum = true;
-      gp = gemm("gemm_conv3", w, in + row, rows, wd, c, 1, 0, 1, rows - 2, wd, out + row, c, nullptr, 0, nullptr, 0, 0, 0, 0, 0, false, true);
-      gn_accum = false;
-      if (!gp) gn_tile_off = 0;
-      return gp;
+      b_gn_tiles = rows > 0 && split ? conv(in + row, rows - 2, out + row, true, 0) : 0;
+      return b_gn_tiles;
     }
-    if (!split) {
-      gn_tile_off = 0;
-      return gemm("gemm_conv3", w, in, rows + 2, wd, c, 1, 0, 1, rows, wd, out, c, nullptr, 0, nullptr, 0, 0, 0, 0, 0, false, true);
-    }
-    const bool pre_gp = gn_tile_off > 0;   // the interior launch left partials
-    gn_accum = true;
-    gp = gemm("gemm_conv3", w, in, 3, wd, c, 1, 0, 1, 1, wd, out, c, nullptr, 0, nullptr, 0, 0, 0, 0, 0, false, pre_gp);
-    gp = gemm("gemm_conv3", w, in + (rows - 1) * row, 3, wd, c, 1, 0, 1, 1, wd, out + (rows - 1) * row, c, nullptr, 0, nullptr, 0, 0, 0, 0, 0, false,
-              pre_gp) && gp;
-    gn_accum = false;
-    if (!(pre_gp && gp)) gn_tile_off = 0;   // (no partials: band_gn_local falls back to the two-pass statistics kernel)
-    return pre_gp && gp;
+    if (rows <= 0) return 0;
+    if (!split) return conv(in, rows, out, true, 0);
+    const int pre = b_gn_tiles;
+    const int top = conv(in, 1, out, pre > 0, pre);
+    const int bottom = conv(in + (rows - 1) * row, 1, out + (rows - 1) * row, pre > 0, pre + top);
+    return pre > 0 && top > 0 && bottom > 0 ? pre + top + bottom : 0;
   }
   void band_build_program() {
     const BandGeom& g = bplan.g;
@@ -2976,22 +2926,21 @@ class Engine : public EngineBase {
           bplan.dec_ps_rows(so, a, b, &j0, &j1);
           const int64_t row = (int64_t)sw[so] * u.cout;
           T* ps = bps[i];                                    // buffer row 0 = map row a - 2
-          gemm("gemm_convPS", u.convps, bdec_in, j1 - j0 + 2, sw[si], in_ld, 1, 0, 1, j1 - j0, sw[si], ps + (2 * j0 - (a - 2)) * row, u.cout,
-               nullptr, 0, nullptr, 0, 1, u.cout);
-          gemm("gemm_conv3", u.sharp, ps + row, b - a + 2, sw[so], u.cout, 1, 0, 1, b - a, sw[so], bscut + row, u.cout, nullptr, 0, ps + 2 * row,
-               u.cout);
+          gemm("gemm_convPS", u.convps, {.in = bdec_in, .in_h = j1 - j0 + 2, .in_w = sw[si], .in_ld = in_ld, .out = ps + (2 * j0 - (a - 2)) * row,
+                                         .out_ld = u.cout, .pad_y = 0, .out_h = j1 - j0, .out_mode = 1, .cout = u.cout});
+          gemm("gemm_conv3", u.sharp, {.in = ps + row, .in_h = b - a + 2, .in_w = sw[so], .in_ld = u.cout, .out = bscut + row, .out_ld = u.cout, .pad_y = 0,
+                                       .out_h = b - a, .res = ps + 2 * row, .res_ld = u.cout});
         } else if (b > a) {
           const int j0 = a / 2, j1 = (b + 1) / 2;
           T* out = bscut + (int64_t)(2 * j0 - (a - 1)) * sw[so] * u.cout;   // output rows 2 j0 .. 2 j1 - 1; owned row `a` is buffer row 1
-          gemm("gemm_convT2", u.convt, bdec_in, j1 - j0, sw[si], in_ld, 1, 0, 0, j1 - j0, sw[si], out, u.cout,
-               nullptr, 0, nullptr, 0, 1, u.cout);
+          gemm("gemm_convT2", u.convt, {.in = bdec_in, .in_h = j1 - j0, .in_w = sw[si], .in_ld = in_ld, .out = out, .out_ld = u.cout, .out_mode = 1,
+                                        .cout = u.cout});
         }
       }, "halo_scut", lv);
       band_op([this, i, so, r] {
         const UpL& u = ups[i];
         const int rows = bplan.g.rows_short(so, r);
-        const bool gp = band_conv3_rows(u.c1, bscut, bta, rows, sw[so], u.cout, /*boundary=*/true);
-        band_gn_local(bta, u.cout, (int64_t)rows * sw[so], gp);
+        band_gn_local(bta, u.cout, (int64_t)rows * sw[so], band_conv3_rows(u.c1, bscut, bta, rows, sw[so], u.cout, /*boundary=*/true));
       }, "gn", lv + ".0");
       band_pre([this, i, so, r] { band_conv3_rows(ups[i].c1, bscut, bta, bplan.g.rows_short(so, r), sw[so], ups[i].cout, /*boundary=*/false); });
       band_op([this, i, so, r] {
@@ -3004,8 +2953,7 @@ class Engine : public EngineBase {
       band_op([this, i, so, r] {
         const UpL& u = ups[i];
         const int rows = bplan.g.rows_short(so, r);
-        const bool gp = band_conv3_rows(u.c2, btb, bta, rows, sw[so], u.cout, /*boundary=*/true);
-        band_gn_local(bta, u.cout, (int64_t)rows * sw[so], gp);
+        band_gn_local(bta, u.cout, (int64_t)rows * sw[so], band_conv3_rows(u.c2, btb, bta, rows, sw[so], u.cout, /*boundary=*/true));
       }, "gn", lv + ".1");
       band_pre([this, i, so, r] { band_conv3_rows(ups[i].c2, btb, bta, bplan.g.rows_short(so, r), sw[so], ups[i].cout, /*boundary=*/false); });
       band_op([this, i, so, r] {
@@ -3022,8 +2970,8 @@ class Engine : public EngineBase {
       band_op([this, r] {
         cur_stage = 7;
         const int rows = bplan.g.rows_short(0, r);
-        gemm("gemm_convPS", ps4, bcat[0], rows + 2, sw[0], 2 * cfg.dim[0], 1, 0, 1, rows, sw[0], bps4 + (int64_t)Wd * cpad4, cpad4, nullptr, 0,
-             nullptr, 0, 1, cpad4);
+        gemm("gemm_convPS", ps4, {.in = bcat[0], .in_h = rows + 2, .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = bps4 + (int64_t)Wd * cpad4,
+                                  .out_ld = cpad4, .pad_y = 0, .out_h = rows, .out_mode = 1, .cout = cpad4});
       }, "halo_ps4");
     }
     band_op([this, r] {
@@ -3031,12 +2979,12 @@ class Engine : public EngineBase {
       cur_stage = 7;
       const int rows = g.rows_short(0, r);
       if (cfg.arch == WX_ARCH_WXFORMER) {
-        gemm("gemm_conv3", fin4, bps4, 2 * rows + 2, Wd, cpad4, 1, 0, 1, 2 * rows, Wd, bdec + (int64_t)Wd * ld_dec, ld_dec, nullptr, 0, nullptr, 0);
+        gemm("gemm_conv3", fin4, {.in = bps4, .in_h = 2 * rows + 2, .in_w = Wd, .in_ld = cpad4, .out = bdec + (int64_t)Wd * ld_dec, .out_ld = ld_dec,
+                                  .pad_y = 0, .out_h = 2 * rows});
         return;
       }
-      gemm_par = up4;
-      gemm("gemm_convT4", up4[0], bcat[0], rows + 2, sw[0], 2 * cfg.dim[0], 1, 0, 1, rows, sw[0], bdec + (int64_t)Wd * ld_dec, ld_dec,
-           nullptr, 0, nullptr, 0, 2, 0, 0, 0);
+      gemm("gemm_convT4", up4[0], {.in = bcat[0], .in_h = rows + 2, .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = bdec + (int64_t)Wd * ld_dec,
+                                   .out_ld = ld_dec, .pad_y = 0, .pad_x = 1, .out_h = rows, .out_mode = 2, .par = up4});
     }, "halo_dec");
     band_op([this, r] { band_tail(2 * bplan.g.ps[0][r] - 1, post != nullptr); });
     if (post) {   // a12 under sharding: local integrals, every rank's sums to everyone, added in rank order, local correction
