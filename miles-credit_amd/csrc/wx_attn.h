@@ -873,10 +873,10 @@ inline int attn_nkf_tokens(int n) {
 inline int attn_pack(int wsz) { const int n = wsz * wsz; return n <= 8 ? 16 / n : 1; }
 inline int attn_nkf(int wsz) { return attn_nkf_tokens(wsz * wsz * attn_pack(wsz)); }
 
-inline bool attn_no_block_order() { static const bool v = getenv("WX_ATTN_NO_B2") && getenv("WX_ATTN_NO_B2")[0] == '1'; return v; }   // A/B switch
 template <typename T>
-inline void launch_window_attn(const AttnParams& p, hipStream_t stream, int split_mode = 0) {
+inline void launch_window_attn(const AttnParams& p, hipStream_t stream, int split_mode, bool no_block_order) {
   // split_mode: 0 = automatic (split when the launch has fewer than ~8 tasks per SIMD), 1 = never, 2 = always (>= 4 key fragments)
+  // no_block_order: A/B switch, the 100-token bf16 windows without the 2 x 2-block bias order
   const int n_win = (p.H / p.wsz) * (p.W / p.wsz);
   const int64_t tasks = (int64_t)((n_win + p.pack - 1) / p.pack) * p.heads;
   const int nkf = attn_nkf_tokens(p.wsz * p.wsz * p.pack);
@@ -907,7 +907,7 @@ inline void launch_window_attn(const AttnParams& p, hipStream_t stream, int spli
       break;
     case 7:
       if (split) launch_window_attn_n<T, 7, true>(p, stream);
-      else if (bt && p.wsz == 10 && (p.wsz_x == 0 || p.wsz_x == 10) && sizeof(T) == 2 && !attn_no_block_order()) launch_window_attn_n<T, 7, false, true, 32, false, 10>(p, stream);
+      else if (bt && p.wsz == 10 && (p.wsz_x == 0 || p.wsz_x == 10) && sizeof(T) == 2 && !no_block_order) launch_window_attn_n<T, 7, false, true, 32, false, 10>(p, stream);
       else if (bt) launch_window_attn_n<T, 7, false, true>(p, stream);
       else launch_window_attn_n<T, 7, false>(p, stream);
       break;

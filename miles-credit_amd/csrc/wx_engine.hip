@@ -36,6 +36,7 @@
 #include "wx_post.h"
 #include "wx_pre.h"
 #include "wx_noise.h"
+#include "wx_options.h"
 
 namespace wx {
 
@@ -165,7 +166,8 @@ class Engine : public EngineBase {
   // x = x_hi + x_lo, W = W_hi + W_lo (split once at load), three bf16 MFMAs per product with fp32 accumulation.  Measured error against
   // the reference's fp32 forward: ~1e-5 of max|y| (base weights), 5-7e-5 on the stress families -- inside the stated 1e-4 tolerance.
   bool split_mma = false;
-  explicit Engine(const wx_config& c, int dev, bool split = false) : split_mma(split && sizeof(T) == 4), cfg(c) {
+  const Options opt;   // the run-time switches, read once by wx_create (wx_options.h)
+  Engine(const wx_config& c, int dev, const Options& o, bool split = false) : split_mma(split && sizeof(T) == 4), opt(o), cfg(c) {
     device = dev;
     derive();
     build_spec();
@@ -496,7 +498,7 @@ class Engine : public EngineBase {
   // 256 output channels is then 16 contiguous KB (full cache lines per LDS-DMA piece instead of half-used ones)
   void pack_kblocked(ConvW& cw) {
     if constexpr (sizeof(T) != 2) return;
-    if (!use_stream || cw.kh != 1 || cw.kw != 1 || cw.n % 128 != 0 || cw.cin % 32 != 0 || cw.cin < 512) return;
+    if (!opt.use_stream || cw.kh != 1 || cw.kw != 1 || cw.n % 128 != 0 || cw.cin % 32 != 0 || cw.cin < 512) return;
     while (wt_host.size() % 8) wt_host.push_back(Elem<T>::from_f(0.f));
     const int64_t off = (int64_t)wt_host.size();
     wt_host.resize(off + (int64_t)cw.n * cw.cin);
@@ -807,7 +809,7 @@ class Engine : public EngineBase {
         if (prev) f.pack_pre = pack_ff(f, c, 4 * c, &prev->out);
       } else if (ff_plain_supported(c, 4 * c)) {
         f.pack = pack_ff(f, c, 4 * c);
-      } else if (ff_wide && ff_wide_supported(c, 4 * c)) {
+      } else if (opt.ff_wide && ff_wide_supported(c, 4 * c)) {
         f.pack_wide = pack_ff(f, c, 4 * c);   // its own field: every rule that reads `pack` (two-stream stages, row windows) stays as it was
       }
     }
@@ -843,7 +845,7 @@ class Engine : public EngineBase {
         if (ks[b] == 4) b4 = (int)b;
       }
       int ride[3] = {0, 0, 0}, ride0[3] = {0, 0, 0};   // k = 4 channels [ride0, ride0 + ride) in the spare rows of branch j
-      if (s == 0 && embed_ride4 && b4 >= 0 && cos[b4] % 4 == 0 && bidx[0] >= 0 && bidx[1] >= 0 && bidx[2] >= 0 &&
+      if (s == 0 && opt.embed_ride4 && b4 >= 0 && cos[b4] % 4 == 0 && bidx[0] >= 0 && bidx[1] >= 0 && bidx[2] >= 0 &&
           (cap[0] - used[0]) + (cap[1] - used[1]) + (cap[2] - used[2]) >= cos[b4]) {
         int left = cos[b4], at4 = 0;
         for (int j = 0; j < 3; ++j) {
@@ -884,7 +886,7 @@ class Engine : public EngineBase {
         st.patch_bias64 = push_f(bias64);
       }
       {   // one launch for the whole CrossEmbed where launches, not FLOPs, are the cost (stages 1-3 of the 1-degree grid)
-        bool same_parity = ks.size() >= 2 && embed_merge && s >= 1;
+        bool same_parity = ks.size() >= 2 && opt.embed_merge && s >= 1;
         for (int kk : ks) same_parity = same_parity && ((ks.back() - kk) % 2 == 0) && kk >= cfg.embed_strides[s];
         // launch-bound = the merged GEMM itself is tiny (1-degree grid: 0.75 G products per stage); the 0.25-degree stages 2-3 pass the
         // token test but are 42 G products each, where the padding costs more than the launch (107 / 123 us against 96 / 100 for the pair)
@@ -1027,81 +1029,28 @@ class Engine : public EngineBase {
   T* dec = nullptr;          // up_block4 output [Hd][Wd][ld_dec]
   float2* rowstat = nullptr;
   char* zero_page = nullptr;
-  bool use_dma = true;
-  bool merge_parity = !getenv("WX_NO_MERGE_PARITY");
-  bool split_k = !getenv("WX_NO_SPLIT_K");
-  bool embed_merge = !getenv("WX_NO_EMBED_MERGE");
-  bool ff_small_px64 = !(getenv("WX_FF_PX64") && getenv("WX_FF_PX64")[0] == '0');   // C = 128 plain block on 64-pixel tiles when the map yields < 128 tiles of 128 (1-degree stage 1: 21.5 -> 15.5 us)
-  int ff_split_tiles = getenv("WX_FF_SPLIT_TILES") ? atoi(getenv("WX_FF_SPLIT_TILES")) : 32;   // pixel tiles, at most
-  // C = 512 (wx_ff.h ff_wide_supported), round 6 -- built, measured, OFF (0): the form is LDS-read-bound and loses both ways.
-  // 1: the chunk blocks are packed (+ 4 MB per FeedForward) and lat-band ranks run the FeedForward of their stage-2 band (2 000 - 4 000
-  // tokens) as the hidden-split fused block + the split-K finish kernel instead of ff1 + split-K ff2 + finish (71 vs 52 us per block);
-  // 2: the unsharded map runs the plain fused block as well (213 vs 104 us per block)
-  int ff_wide = getenv("WX_FF_WIDE") ? atoi(getenv("WX_FF_WIDE")) : 0;
-  int ff_wide_wgs = getenv("WX_FF_WIDE_WGS") ? atoi(getenv("WX_FF_WIDE_WGS")) : 256;   // hidden ranges S: the fewest that yield this many workgroups (<= 8)
   int n_ff_wide = 0;
-  int ff_split_max = getenv("WX_FF_SPLIT") ? atoi(getenv("WX_FF_SPLIT")) : 8;   // hidden ranges of the split fused FeedForward (0 / 1: off)
-  bool attn_pack2 = !getenv("WX_NO_ATTN_PACK2");
-  int ff_split_tw = getenv("WX_FF_SPLIT_TW") ? atoi(getenv("WX_FF_SPLIT_TW")) : 0;   // 0: by map size
-  bool ff_split_fused = !getenv("WX_NO_FF_SPLIT_FUSED");   // split-bf16 precision: the C = 128 / 256 FeedForward as one launch (wx_ff_split.h)
-  bool ff_split_256 = !getenv("WX_NO_FF_SPLIT_256");
-  bool ff_split_pre = !getenv("WX_NO_FF_SPLIT_PRE");       // ... with the attention's out-projection in front (its PRE form)
-  bool ff_split_post = !getenv("WX_NO_FF_SPLIT_POST");     // ... and the next attention's LayerNorm + to_qkv behind (its POST form)
-  bool embed_tail_split = !getenv("WX_NO_EMBED_TAIL_SPLIT");
   float* embed_tail = nullptr;
   size_t embed_tail_bytes = 0;
-  bool embed_ride4 = !getenv("WX_NO_EMBED_RIDE4");
-  // stage-0 CrossEmbed: the branch outside the patch kernel on the side stream, beside it.  OFF: bit-identical and a tie on MI355X (C3 bf16, same
-  // box, four alternations: 8.084 - 8.185 ms/step with it, 8.066 - 8.100 without) -- the patch launch fills the chip, the 88 us GEMM only moves
-  bool embed_side = getenv("WX_EMBED_SIDE") && getenv("WX_EMBED_SIDE")[0] == '1';
-  bool pack_align = !getenv("WX_NO_PACK_ALIGN");   // pack_input: block origin shifted onto the source's 256-byte boundaries
-  bool stat_share = !getenv("WX_NO_EMBED_STATS");
-  int skinny_max = getenv("WX_SKINNY_MAX") ? atoi(getenv("WX_SKINNY_MAX")) : 8;          // K ranges per tile (0 / 1: off)
-  int skinny_steps = getenv("WX_SKINNY_STEPS") ? std::max(1, atoi(getenv("WX_SKINNY_STEPS"))) : 2;   // 128-byte K steps per range, at least
-  int skinny_min_nk = getenv("WX_SKINNY_MIN_NK") ? atoi(getenv("WX_SKINNY_MIN_NK")) : 16;
-  int skinny_tiles = getenv("WX_SKINNY_TILES") ? atoi(getenv("WX_SKINNY_TILES")) : 32;
-  int skinny_tiles_band = getenv("WX_SKINNY_TILES_BAND") ? atoi(getenv("WX_SKINNY_TILES_BAND")) : 128;
-  int skinny_max_band = getenv("WX_SKINNY_MAX_BAND") ? atoi(getenv("WX_SKINNY_MAX_BAND")) : 4;
   float* splitk_buf = nullptr;   // fp32 partial sums of every split-K form (plain, skinny, hidden-split FeedForward): ONE buffer, sized in
   size_t splitk_bytes = 0;       // alloc_activations from the split rules' own bounds -- the forward never allocates (hipMalloc inside a
                                  // forward would also be illegal under the opt-in graph capture)
   size_t splitk_bound(bool band = false) const {   // band: the wider skinny rule of lat-band ranks (reserved by band_enable only)
     const size_t tile = (size_t)128 * 128 * sizeof(float);
     size_t b = (size_t)512 * tile;                                                               // plain rule: S * tiles <= 512
-    b = std::max(b, (size_t)std::max(band ? std::max(skinny_tiles, skinny_tiles_band) : skinny_tiles, 1) * (size_t)std::max(skinny_max, 1) * tile); // skinny rule: tiles <= skinny_tiles, S <= skinny_max
-    b = std::max(b, (size_t)std::max(ff_split_tiles, 1) * 128 * 256 * (size_t)std::max(ff_split_max, 1) * sizeof(float));   // <= ff_split_tiles pixel tiles of <= 128 px, C <= 256
-    if (band && ff_wide) b = std::max(b, (size_t)(std::max(ff_wide_wgs, 256) + 128) * 64 * 512 * sizeof(float));   // C = 512 hidden split: S * tiles < ff_wide_wgs + tiles, tiles <= 128 of 64 px
+    b = std::max(b, (size_t)std::max(band ? std::max(opt.skinny_tiles, opt.skinny_tiles_band) : opt.skinny_tiles, 1) * (size_t)std::max(opt.skinny_max, 1) * tile); // skinny rule: tiles <= skinny_tiles, S <= skinny_max
+    b = std::max(b, (size_t)std::max(opt.ff_split_tiles, 1) * 128 * 256 * (size_t)std::max(opt.ff_split_max, 1) * sizeof(float));   // <= ff_split_tiles pixel tiles of <= 128 px, C <= 256
+    if (band && opt.ff_wide) b = std::max(b, (size_t)(std::max(opt.ff_wide_wgs, 256) + 128) * 64 * 512 * sizeof(float));   // C = 512 hidden split: S * tiles < ff_wide_wgs + tiles, tiles <= 128 of 64 px
     return b;
   }
   float* splitk_scratch(size_t need) {
     if (need > splitk_bytes) throw StateError("split-K scratch: a launch asks for " + std::to_string(need) + " bytes, " + std::to_string(splitk_bytes) + " were reserved (the split rules and splitk_bound() disagree)");
     return splitk_buf;
   }
-  bool embed_split = !getenv("WX_NO_EMBED_SPLIT");
-  int embed_split_ways = getenv("WX_EMBED_SPLIT") ? std::max(2, atoi(getenv("WX_EMBED_SPLIT"))) : 4;
   float* embed_partial = nullptr;
   size_t embed_partial_bytes = 0;
-  bool use_stream = !(getenv("WX_NO_STREAM") && getenv("WX_NO_STREAM")[0] == '1');   // persistent large-tile GEMM (wx_gemm_stream.h) for the LN-folded 1x1 layers of the deep stages
-  int stream_min_rows = 4096;
-  bool use_stream_lc = !(getenv("WX_NO_STREAM_LC") && getenv("WX_NO_STREAM_LC")[0] == '1');   // loader / consumer form of the persistent GEMM (one-tile-per-CU residual layers)
-  bool use_gemm8p = !(getenv("WX_NO_GEMM8P") && getenv("WX_NO_GEMM8P")[0] == '1');   // eight-phase 160 x 256 kernel (wx_gemm8p.h) for the deep-K stride-1 k x k convs of the decoder
-  int64_t gemm8p_min_rows = getenv("WX_GEMM8P_MIN_ROWS") ? atoll(getenv("WX_GEMM8P_MIN_ROWS")) : 16384;
   int64_t n_gemm8p = 0;              // launches of the last forward that took it
-  bool use_wreg = !(getenv("WX_NO_WREG") && getenv("WX_NO_WREG")[0] == '1');   // weight-stationary GEMM (wx_gemm_wreg.h) for K = 512 layers on mid-sized maps
-  int wreg_min_rows = getenv("WX_WREG_MIN_ROWS") ? atoi(getenv("WX_WREG_MIN_ROWS")) : 1024;
-  int wreg_max_rows = getenv("WX_WREG_MAX_ROWS") ? atoi(getenv("WX_WREG_MAX_ROWS")) : 4096;
   char* stream_sink = nullptr;
-  int dbg_flags = 0;
-  int gemm_cfg = 0;
-  bool fuse_ln = true;
-  bool fuse_ff = true, fuse_out = true, fuse_qkv = true;          // stages with C in {128, 256}: FeedForward as one kernel (wx_ff.h), bf16 engine
-  int ff_variant = 0, ff_dbg = 0, attn_split = 0;
-  int attn_block = 2;           // WX_ATTN_BLOCK: LN + to_qkv + window attention + to_out + residual as ONE launch (wx_attn_block.h), bf16 engine.
-                                // 0 never; 1 wherever the kernel exists (C in {128, 256}); 2 (default) only where it measured faster than the
-                                // fused feed-forward chain on MI355X: C = 128 with 100-token windows on >= 2048 windows (C3 stage 0: 165 + 136 us
-                                // against 91 + 218 us per sub-block, and 0.5 GB less HBM traffic each) and on maps of <= 32768 tokens, where three
-                                // launch-bound kernels become one (1-degree model +5 %); slower in between
-  int ff_min_wgs = 256;         // fused feed-forward only when it yields at least this many workgroups (WX_FF_MIN_WGS)
   float2* statpart = nullptr;   // [rows][slots] LayerNorm partials written by the producing GEMM epilogue (slots <= 8, or C / 32)
   int64_t statpart_elems = 0;
   float2* stat_dst(int64_t rows, int slots) const {
@@ -1112,7 +1061,6 @@ class Engine : public EngineBase {
   }
   float2* gnpart = nullptr;     // [m_tiles][C] GroupNorm partials written by the 3x3 conv epilogue
   int64_t gnpart_elems = 0;
-  bool attn_blk_on = !(getenv("WX_NO_ATTN_BLK") && getenv("WX_NO_ATTN_BLK")[0] == '1');   // attention sub-blocks on the k-blocked layouts (KBlk::attn)
   int64_t n_attn_blk = 0;       // attention sub-blocks of the last forward that ran on the k-blocked layouts
   // Row window (round 5): attention() / feedforward() / gemm() work on map rows [rw0, rw0 + rwn) of the current stage instead of the whole
   // map when rwn >= 0 -- the half-maps of the two-stream schedule below.  Every buffer a sub-block touches is indexed by token, so a
@@ -1124,7 +1072,6 @@ class Engine : public EngineBase {
   int64_t rw_tok0(int s) const { return rwn >= 0 ? (int64_t)rw0 * sw[s] : 0; }
   int rw_rows(int s) const { return rwn >= 0 ? rwn : sh[s]; }
   int stat_tiles_ready = 0;     // > 0: `statpart` holds partials of the current stream contents (that many per row)
-  bool use_patch = true, planar_xin = true;
   double* gn_acc = nullptr;
   float *d_mean = nullptr, *d_std = nullptr, *d_lo = nullptr, *d_hi = nullptr;
   bool have_denorm = false, have_tracer = false;
@@ -1136,10 +1083,10 @@ class Engine : public EngineBase {
     const int64_t xin_elems = (int64_t)(Hp + 2 * halo + 2) * (Wp + 2 * halo + 2) * cpad0;
     xin = (T*)dalloc(xin_elems * sizeof(T));
     WX_HIP(hipMemset(xin, 0, xin_elems * sizeof(T)));
-    if (split_mma && use_patch && sp16_dev) {   // the patch kernel reads the bf16 (hi, lo) planes: no fp32 planar copy in this mode
+    if (split_mma && opt.use_patch && sp16_dev) {   // the patch kernel reads the bf16 (hi, lo) planes: no fp32 planar copy in this mode
       xs_planes = (char*)dalloc((size_t)xin_elems * 2 * 2);
       WX_HIP(hipMemset(xs_planes, 0, (size_t)xin_elems * 2 * 2));
-    } else if (use_patch && planar_xin) {
+    } else if (opt.use_patch && opt.planar_xin) {
       xin_planar = (T*)dalloc(xin_elems * sizeof(T));
       WX_HIP(hipMemset(xin_planar, 0, xin_elems * sizeof(T)));
     }
@@ -1175,24 +1122,9 @@ class Engine : public EngineBase {
     gnpart = (float2*)dalloc(gnpart_elems * sizeof(float2));
     zero_page = (char*)dalloc(256);
     WX_HIP(hipMemset(zero_page, 0, 256));
-    if (const char* e = getenv("WX_NO_DMA")) use_dma = !(e[0] == '1');
     stream_sink = (char*)dalloc(8192);   // 16 bytes per thread of the widest workgroup (512: wx_gemm8p.h)
     splitk_bytes = splitk_bound();
     splitk_buf = (float*)dalloc(splitk_bytes);
-    if (const char* e = getenv("WX_DBG")) dbg_flags = atoi(e);
-    if (const char* e = getenv("WX_STREAM_MIN_ROWS")) stream_min_rows = atoi(e);
-    if (const char* e = getenv("WX_GEMM_CFG")) gemm_cfg = atoi(e);
-    if (const char* e = getenv("WX_NO_LNFUSE")) fuse_ln = !(e[0] == '1');
-    if (const char* e = getenv("WX_NO_FFFUSE")) fuse_ff = !(e[0] == '1');
-    if (const char* e = getenv("WX_FF_MIN_WGS")) ff_min_wgs = atoi(e);
-    if (const char* e = getenv("WX_ATTN_BLOCK")) attn_block = atoi(e);
-    if (const char* e = getenv("WX_NO_OUTFUSE")) fuse_out = !(e[0] == '1');
-    if (const char* e = getenv("WX_NO_QKVFUSE")) fuse_qkv = !(e[0] == '1');
-    if (const char* e = getenv("WX_FF_VARIANT")) ff_variant = atoi(e);
-    if (const char* e = getenv("WX_FF_DBG")) ff_dbg = atoi(e);
-    if (const char* e = getenv("WX_ATTN_SPLIT")) attn_split = atoi(e);
-    if (const char* e = getenv("WX_NO_PATCH")) use_patch = !(e[0] == '1');
-    if (const char* e = getenv("WX_NO_PLANAR")) planar_xin = !(e[0] == '1');
     const int cmax = cfg.dim[3];
     gn_acc = (double*)dalloc(2 * cmax * sizeof(double));
     d_mean = (float*)dalloc(C_out * sizeof(float));
@@ -1325,7 +1257,6 @@ class Engine : public EngineBase {
   int64_t n_ff_split_pre = 0;        // ... of which with the out-projection in front (three GEMMs)
   int64_t n_ff_split_post = 0;       // ... of which also with the next to_qkv behind (four GEMMs)
   int64_t n_ff_split_fused = 0;      // ... of which FeedForward sub-blocks in one launch (wx_ff_split.h; counted as two GEMMs above)
-  int split_bn64 = getenv("WX_SPLIT_BN64") ? atoi(getenv("WX_SPLIT_BN64")) : 1;   // 0: never the 64-column tiles of the badly quantised residual layers
   int64_t n_launches = 0;            // timed() calls of the last forward (one per kernel launch or launch + finish pair)
   bool query(const std::string& key, int64_t* v) override {
     if (key == "two_stream_stages") { *v = n_two_stream_stages; return true; }
@@ -1443,7 +1374,7 @@ class Engine : public EngineBase {
   // ------------------------------------------------------------------ launch helpers
   // K ranges of the plain split-K rule (gemm() below) for a bias-only convolution of `rows` output pixels; 1 = not split
   int plain_split_ways(const ConvW& w, int64_t rows) const {
-    if (!split_k || !use_dma || w.n % 128 != 0 || (w.cin * (int)sizeof(T)) % 128 != 0) return 1;
+    if (!opt.split_k || !opt.use_dma || w.n % 128 != 0 || (w.cin * (int)sizeof(T)) % 128 != 0) return 1;
     const int64_t tiles = cdiv(rows, (int64_t)128) * (w.n / 128);
     const int nk = w.kh * w.kw * (w.cin * (int)sizeof(T) / 128);
     int S = (int)std::min<int64_t>(8, 512 / std::max<int64_t>(tiles, 1));
@@ -1483,7 +1414,7 @@ class Engine : public EngineBase {
   enum class Route { gemm8p_conv, gemm8p_convt2, wreg, stream_res, stream_res_lc, stream_ln, conv128 };
   // the kernel a (normalised) request runs on; conv128 is the 128 x 128 implicit-GEMM kernel, every shape's fall-back
   Route gemm_route(const ConvW& w, const GemmReq& r) const {
-    if (sizeof(T) != 2 || !use_dma || dbg_flags) return Route::conv128;
+    if (sizeof(T) != 2 || !opt.use_dma || opt.dbg_flags) return Route::conv128;
     const int64_t rows = (int64_t)r.out_h * r.out_w;
     const int64_t sel_rows = rule_rows > 0 ? rule_rows : rows;   // what the selection rules see (row windows: the whole map)
     const bool same_map = r.stride == 1 && r.in_h == r.out_h && r.in_w == r.out_w;
@@ -1492,35 +1423,35 @@ class Engine : public EngineBase {
     // UpBlocks at 0.25 degrees: K = 4608 / 2304): the eight-phase kernel's conv form (wx_gemm8p.h) -- 127.7 -> 90.1 us and 112.6 -> 102.0 us
     // against the 128 x 128 kernel (tools/gemm8p_probe, profiles/r06_gemm8p_probe_b_conv_form.txt); bitwise the same outputs where the two
     // walk K in the same order.  GroupNorm partials: one per (160-row tile, wave row) = 80 output rows, folded like the 128-row ones.
-    if (use_gemm8p && rwn < 0 && !band_on && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && same_map && r.pad_y == (w.kh - 1) / 2 &&
+    if (opt.use_gemm8p && rwn < 0 && !band_on && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && same_map && r.pad_y == (w.kh - 1) / 2 &&
         r.pad_x == (w.kw - 1) / 2 && !r.rs && r.act == 0 && r.out_mode == 0 && !r.want_stats && w.n % 256 == 0 && w.cin % 64 == 0 &&
-        (w.kh * w.kw * w.cin) % 128 == 0 && rows >= gemm8p_min_rows && rows * r.in_ld * 2 < (int64_t)0x7fffff00 && gemm8p_fits(rows, w.n, 2, 5, true) &&
-        (!r.want_gn || (fuse_ln && (int64_t)(r.gn_off + gemm8p_conv_gn_tiles(rows, w.n)) * w.n <= gnpart_elems)))
+        (w.kh * w.kw * w.cin) % 128 == 0 && rows >= opt.gemm8p_min_rows && rows * r.in_ld * 2 < (int64_t)0x7fffff00 && gemm8p_fits(rows, w.n, 2, 5, true) &&
+        (!r.want_gn || (opt.fuse_ln && (int64_t)(r.gn_off + gemm8p_conv_gn_tiles(rows, w.n)) * w.n <= gnpart_elems)))
       return Route::gemm8p_conv;
     // ConvTranspose k2 s2 (a 1x1 GEMM with N = 4 cout whose epilogue scatters 2 x 2 pixels; the decoder's three UpBlocks): the same
     // kernel's 1x1 form with the scatter in its epilogue -- 33.4 -> 24.6, 59.3 -> 41.9, 63.1 -> 47.3 us at 0.25 degrees, bitwise equal
-    if (use_gemm8p && rwn < 0 && !band_on && one && !r.rs && !r.res && r.act == 0 && r.out_mode == 1 && !r.want_stats && !r.want_gn &&
-        r.cout > 0 && w.n == 4 * r.cout && r.cout % 64 == 0 && w.cin % 128 == 0 && rows >= gemm8p_min_rows / 4 && gemm8p_fits(rows, w.n, 2, 5, true))
+    if (opt.use_gemm8p && rwn < 0 && !band_on && one && !r.rs && !r.res && r.act == 0 && r.out_mode == 1 && !r.want_stats && !r.want_gn &&
+        r.cout > 0 && w.n == 4 * r.cout && r.cout % 64 == 0 && w.cin % 128 == 0 && rows >= opt.gemm8p_min_rows / 4 && gemm8p_fits(rows, w.n, 2, 5, true))
       return Route::gemm8p_convt2;
     // K = 512 layers on maps of a few thousand rows (a lat-band rank's share of the 0.25-degree stage 2: 2 000 - 4 000 tokens): the
     // weight-stationary kernel (wx_gemm_wreg.h: the wave's weight slice in registers, activations streamed tile by tile, one barrier
     // per tile).  tools/gemm_wreg_probe, M = 2500: to_qkv 11.5 us against 16.1 (persistent kernel) -- at M = 20 000 the two tie, so the
     // unsharded model keeps the persistent kernel.  Bitwise the same outputs; row partials in N / 32 slots instead of N / 128.
-    const bool ln_v = r.rs && !r.res && !r.want_stats && w.colsum >= 0, res_v = !r.rs && r.res && r.want_stats && fuse_ln && r.act == 0;
-    if (use_wreg && w.wt_kb >= 0 && one && w.cin == 512 && w.n % WREG_BN == 0 && w.bias >= 0 && r.out_mode == 0 && !r.want_gn && r.blk == KBlk::none &&
-        rwn < 0 && rows >= wreg_min_rows && rows < wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
+    const bool ln_v = r.rs && !r.res && !r.want_stats && w.colsum >= 0, res_v = !r.rs && r.res && r.want_stats && opt.fuse_ln && r.act == 0;
+    if (opt.use_wreg && w.wt_kb >= 0 && one && w.cin == 512 && w.n % WREG_BN == 0 && w.bias >= 0 && r.out_mode == 0 && !r.want_gn && r.blk == KBlk::none &&
+        rwn < 0 && rows >= opt.wreg_min_rows && rows < opt.wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
         wreg_gemm_ok(rows, w.n, w.cin, r.rs ? stat_tiles_ready : 0, ln_v))
       return Route::wreg;
     // residual layers with N = 512 / 1024 (to_out, FeedForward layer 2 of stages 2 and 3): the persistent kernel on 160 x 128 tiles, two
     // workgroups per CU (47.9 vs 58.3 us on layer 2, 21.0 vs 23.2 us on to_out; bitwise equal to the 128 x 128 kernel's output) -- with at
     // most one tile per CU and a deep K (stage 3 of the 0.25-degree model) in its loader / consumer form
-    if (use_stream && w.wt_kb >= 0 && one && !r.rs && r.res && r.act == 0 && r.out_mode == 0 && r.want_stats && fuse_ln && !r.want_gn &&
-        (w.n == 512 || w.n == 1024) && w.bias >= 0 && sel_rows >= stream_min_rows && stream_gemm_ok(rows, w.n, w.cin, 128))
-      return use_stream_lc && stream_gemm_lc_pays(sel_rows, w.n, w.cin, 5) ? Route::stream_res_lc : Route::stream_res;
+    if (opt.use_stream && w.wt_kb >= 0 && one && !r.rs && r.res && r.act == 0 && r.out_mode == 0 && r.want_stats && opt.fuse_ln && !r.want_gn &&
+        (w.n == 512 || w.n == 1024) && w.bias >= 0 && sel_rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin, 128))
+      return opt.use_stream_lc && stream_gemm_lc_pays(sel_rows, w.n, w.cin, 5) ? Route::stream_res_lc : Route::stream_res;
     // LayerNorm-folded 1x1 layers with many rows and K >= 512 (to_qkv, FeedForward layer 1 of stages 2-3): the persistent
     // 128 x 256-tile kernel; measured per shape against the 128 x 128 kernel in tools/gemm_stream_probe
-    if (use_stream && w.wt_kb >= 0 && w.n % 256 == 0 && one && r.rs && !r.res && r.out_mode == 0 && !r.want_stats && !r.want_gn &&
-        sel_rows >= stream_min_rows && stream_gemm_ok(rows, w.n, w.cin))
+    if (opt.use_stream && w.wt_kb >= 0 && w.n % 256 == 0 && one && r.rs && !r.res && r.out_mode == 0 && !r.want_stats && !r.want_gn &&
+        sel_rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin))
       return Route::stream_ln;
     return Route::conv128;
   }
@@ -1540,12 +1471,12 @@ class Engine : public EngineBase {
     p.stat_tiles = r.rs ? stat_tiles_ready : 0; p.stat_inv_c = 1.0f / (float)w.cin_true;
     if (r.rs && w.colsum < 0) throw StateError("LayerNorm-folded GEMM without column sums");
     p.act = r.act; p.res = r.res; p.res_ld = r.res_ld; p.out = r.out; p.out_ld = r.out_ld;
-    p.out_mode = r.out_mode; p.cout = r.cout; p.py = r.py; p.px = r.px; p.dbg = dbg_flags;
-    const bool dma = conv_gemm_is_dma<T>(p, use_dma ? zero_page : nullptr);
+    p.out_mode = r.out_mode; p.cout = r.cout; p.py = r.py; p.px = r.px; p.dbg = opt.dbg_flags;
+    const bool dma = conv_gemm_is_dma<T>(p, opt.use_dma ? zero_page : nullptr);
     const int64_t rows = (int64_t)r.out_h * r.out_w;
     const double m = (double)rows;
     if constexpr (sizeof(T) == 4) {
-      if (split_mma && w.cin % 32 == 0 && !dbg_flags && dma) {
+      if (split_mma && w.cin % 32 == 0 && !opt.dbg_flags && dma) {
         p.split = 1;
         p.wt = ws_dev + w.wt;
         if (!r.par) ++n_split_gemms;   // a ConvTranspose's outer call only dispatches: its launches are counted where they happen
@@ -1618,13 +1549,13 @@ class Engine : public EngineBase {
     if (r.blk == KBlk::attn) throw StateError("k-blocked q|k|v / attention output requested but the GEMM fell back to the row-major kernel");
     if (rwn >= 0) throw StateError("row-window launch fell to the generic kernel (the two-stream schedule runs on the persistent GEMMs only)");
     if (r.par) {   // the four parity convs of a ConvTranspose k4 s2 p1 (out_mode 2): one launch when the fast path takes it
-      if (merge_parity && dma && !dbg_flags && w.n <= 128) {
+      if (opt.merge_parity && dma && !opt.dbg_flags && w.n <= 128) {
         p.n_par = 4;
         for (int q = 0; q < 4; ++q) p.wt_par[q] = (p.split ? ws_dev : wt_dev) + r.par[q].wt;
         const double fl4 = 4.0 * 2.0 * m * w.n * w.kh * w.kw * w.cin_true;
         const double by4 = (4.0 * m * w.n + (double)r.in_h * r.in_w * w.cin_true + 4.0 * w.n * w.kh * w.kw * w.cin) * sizeof(T);
         if (p.split) ++n_split_gemms;   // the merged launch
-        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, gemm_cfg); });
+        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, opt.gemm_cfg, opt.gemm_deep_tiles); });
         return {};
       }
       for (int q = 0; q < 4; ++q) {
@@ -1635,11 +1566,11 @@ class Engine : public EngineBase {
       return {};
     }
     GemmOut o;
-    if (r.want_stats && fuse_ln && dma) {
+    if (r.want_stats && opt.fuse_ln && dma) {
       p.stat_out = statpart;
       p.stat_stride = r.stat_stride; p.stat_slot0 = r.stat_slot0;
     }
-    if (r.want_gn && fuse_ln && dma) {
+    if (r.want_gn && opt.fuse_ln && dma) {
       p.gn_out = gnpart + (int64_t)r.gn_off * w.n;
       o.gn_tiles = (int)cdiv(rows, (int64_t)128);
     }
@@ -1655,17 +1586,17 @@ class Engine : public EngineBase {
     // ... and for the deep-K 1 x 1 layers of the transformer blocks on maps of a few hundred pixels (1-degree grid, stages 2 - 3:
     // 4 - 12 tiles, each walking 16 - 32 K steps alone on its CU at 0.57 us per step): K ranges of >= skinny_steps steps over up to
     // skinny_max workgroups per tile; the finish kernel applies the whole epilogue (LayerNorm fold, GELU, residual, LN partials)
-    if (split_k && skinny_max >= 2 && !p.partial && r.out_mode == 0 && !p.gn_out && w.kh == 1 && w.kw == 1 && r.stride == 1 &&
-        w.n % 64 == 0 && (w.cin * (int)sizeof(T)) % 128 == 0 && dma && !dbg_flags) {
+    if (opt.split_k && opt.skinny_max >= 2 && !p.partial && r.out_mode == 0 && !p.gn_out && w.kh == 1 && w.kw == 1 && r.stride == 1 &&
+        w.n % 64 == 0 && (w.cin * (int)sizeof(T)) % 128 == 0 && dma && !opt.dbg_flags) {
       const int64_t tiles = (int64_t)cdiv(rows, (int64_t)128) * conv_gemm_n_tiles(w.n);
       const int nk = w.cin * (int)sizeof(T) / 128;
       // (the tiles the wider lat-band rule adds -- more than skinny_tiles of them -- take at most skinny_max_band K ranges: with 8 the fp32
       // partial sums of a rank's stage-2 FeedForward 2, 8 x 2 600 x 512 floats written and read back, cost more than the shorter K walk
       // saves: slowest of 8 ranks 4.51 -> 4.32 ms with 4, 4.42 with 2)
-      const int S = std::min((band_on && tiles > skinny_tiles) ? std::min(skinny_max, skinny_max_band) : skinny_max, nk / skinny_steps);
+      const int S = std::min((band_on && tiles > opt.skinny_tiles) ? std::min(opt.skinny_max, opt.skinny_max_band) : opt.skinny_max, nk / opt.skinny_steps);
       // lat-band ranks: a rank's share of the 0.25-degree stage 2 is ~80 tiles walking K = 2048 alone (FeedForward layer 2: 40 us) -- the
       // rule tuned on the 1-degree model (<= 32 tiles) is widened there (slowest of 8 ranks 4.62 -> 4.53 ms)
-      if (tiles <= (band_on ? std::max(skinny_tiles, skinny_tiles_band) : skinny_tiles) && nk >= skinny_min_nk && S >= 2) {
+      if (tiles <= (band_on ? std::max(opt.skinny_tiles, opt.skinny_tiles_band) : opt.skinny_tiles) && nk >= opt.skinny_min_nk && S >= 2) {
         p.partial = splitk_scratch((size_t)S * rows * w.n * sizeof(float));
         p.k_splits = S;
       }
@@ -1675,13 +1606,13 @@ class Engine : public EngineBase {
       // N = 512 -> 628 tiles = 1.23 rounds): 128 x 64 tiles (1 256 of them: 2.45 half-length rounds; three workgroups per CU)
       // (measured, C3: FeedForward 2 of stage 2 2.74 -> 2.36 ms, to_out 1.03 -> 0.88; 64-column tiles EVERYWHERE lose -- to_qkv 1.82 -> 1.99,
       // FeedForward 1 2.59 -> 2.84: half the MFMAs per split activation fragment)
-      if (!p.partial && split_bn64 && dma && w.n >= 96 && w.n % 64 == 0 && (w.n <= 512 || !p.stat_out) && r.stat_stride == 0) {
+      if (!p.partial && opt.split_bn64 && dma && w.n >= 96 && w.n % 64 == 0 && (w.n <= 512 || !p.stat_out) && r.stat_stride == 0) {
         const int64_t tiles = cdiv(rows, (int64_t)128) * cdiv(w.n, 128);
         const double rounds = (double)tiles / 512.0;
         if (tiles > 512 && rounds < 1.5) p.bn64 = 1;
       }
     }
-    timed(cls, flops, bytes, [&] { launch_conv_gemm<T>(p, use_dma ? zero_page : nullptr, cur_stream, gemm_cfg); });
+    timed(cls, flops, bytes, [&] { launch_conv_gemm<T>(p, opt.use_dma ? zero_page : nullptr, cur_stream, opt.gemm_cfg, opt.gemm_deep_tiles); });
     if (p.stat_out) o.stat_slots = p.partial ? conv_gemm_finish_slots(w.n) : (p.bn64 ? cdiv(w.n, 64) : conv_gemm_n_tiles(w.n));
     return o;
   }
@@ -1719,15 +1650,15 @@ class Engine : public EngineBase {
   // exist in memory on this path: a debug run captures the sub-block's output only)
   bool small_map_tokens(int s) const { return (int64_t)sh[s] * sw[s] <= 32768; }
   bool attn_block_ok(const AttnL& a, int s) const {
-    if (sizeof(T) != 2 || !attn_block || band_on || attn_kind_override >= 0 || a.bias_tb < 0 || cfg.dim_head != 32) return false;
-    if (attn_block == 2) {
+    if (sizeof(T) != 2 || !opt.attn_block || band_on || attn_kind_override >= 0 || a.bias_tb < 0 || cfg.dim_head != 32) return false;
+    if (opt.attn_block == 2) {
       const bool big_s0 = cfg.dim[s] == 128 && attn_nkf(a.wsz) == 7 && (int64_t)(sh[s] / a.wsz) * (sw[s] / a.wsz) >= 2048;
       const bool small_map = small_map_tokens(s);   // launch-bound maps (1-degree model): one launch instead of three
       if (!big_s0 && !small_map) return false;
     }
     // 2 x 2 windows: one 16-token fragment per window loses even on launch-bound maps (37 us against 26 for the three launches); four
     // windows per fragment (AttnBlockParams::pack) win there
-    if (a.wsz == 2 && !(attn_pack2 && small_map_tokens(s) && ((sh[s] / 2) * (sw[s] / 2)) % 4 == 0)) return false;
+    if (a.wsz == 2 && !(opt.attn_pack2 && small_map_tokens(s) && ((sh[s] / 2) * (sw[s] / 2)) % 4 == 0)) return false;
     return a.wsz > 1 && attn_block_supported(cfg.dim[s], a.wsz, true) &&
            (a.kind == 0 || a.kind == 1) && a.qkv.cin == cfg.dim[s] && a.out.cin == cfg.dim[s];
   }
@@ -1748,7 +1679,7 @@ class Engine : public EngineBase {
         bp.tb = f_dev + a.bias_tb; bp.H = h; bp.W = w; bp.wsz = a.wsz; bp.kind = a.kind;
         bp.pack = a.wsz == 2 ? 4 : 1;
         const double n = (double)a.wsz * a.wsz;
-        bp.stat_out = fuse_ln && !dbg_flags ? stat_dst(m, c / 32) : nullptr;
+        bp.stat_out = opt.fuse_ln && !opt.dbg_flags ? stat_dst(m, c / 32) : nullptr;
         timed("attn_block", 8.0 * m * c * c + 4.0 * m * n * c, 2.0 * m * c * sizeof(T), [&] { launch_attn_block(c, bp, cur_stream); });
         stat_tiles_ready = bp.stat_out ? c / 32 : 0;
         capture(dbg_name, x, h, w, c, ld, w);
@@ -1762,9 +1693,9 @@ class Engine : public EngineBase {
     } else {
       // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
       // k-blocked (see KBlk); outputs bitwise the row-major chain's
-      if (sizeof(T) == 2 && attn_blk_on && use_stream && use_dma && fuse_ln && !dbg_flags && !dbg_on && !band_on && rwn < 0 && cfg.dim_head == 32 &&
+      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_on && !band_on && rwn < 0 && cfg.dim_head == 32 &&
           !qkv_ready && !defer_out && attn_kind_override < 0 && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
-          (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
+          (rule_rows > 0 ? rule_rows : (int64_t)m) >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
         blk = KBlk::attn;
         ++n_attn_blk;
       }
@@ -1779,7 +1710,7 @@ class Engine : public EngineBase {
       p.blk = blk == KBlk::attn ? 1 : 0;
       const double n = (double)a.wsz * a.wsz;
       timed("window_attn", 4.0 * m * n * c, 4.0 * m * c * sizeof(T), [&] {
-        if (cfg.dim_head == 32) launch_window_attn<T>(p, cur_stream, attn_split);
+        if (cfg.dim_head == 32) launch_window_attn<T>(p, cur_stream, opt.attn_split, opt.attn_no_b2);
         else launch_window_attn_any<T>(p, cfg.dim_head, cur_stream);   // [NP][NP] bias table shared by the heads (bias_head_stride 0)
       });
       capture(dbg_name + ".qkv", scratch, h, w, 3 * c, 3 * c, w);
@@ -1797,13 +1728,13 @@ class Engine : public EngineBase {
     const int64_t m = (int64_t)sh[cur_stage] * sw[cur_stage];
     // C = 128 on a launch-bound map (1-degree grid stage 1: 45 workgroups): one launch instead of two wins from 40 workgroups on
     // (724 -> 729 steps/s); C = 256 at 23 workgroups loses (710)
-    if (cfg.dim[cur_stage] == 128 || cfg.dim[cur_stage] == 64) return cdiv(m, 128) >= std::min(ff_min_wgs, 40);
-    return cdiv(m, 64) >= ff_min_wgs;
+    if (cfg.dim[cur_stage] == 128 || cfg.dim[cur_stage] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
+    return cdiv(m, 64) >= opt.ff_min_wgs;
   }
-  bool ff_takes_out(const FFL& f) const { return sizeof(T) == 2 && fuse_ff && fuse_out && f.pack_pre >= 0 && !dbg_on && ff_big_enough() && cfg.dim_head == 32; }
+  bool ff_takes_out(const FFL& f) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_on && ff_big_enough() && cfg.dim_head == 32; }
   // split-bf16 precision: the one-launch FeedForward (wx_ff_split.h) of this layer ...
   bool ff_split_fused_ok(const FFL& f, int c) const {
-    return sizeof(T) == 4 && split_mma && ff_split_fused && !dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || ff_split_256) && f.w1.cin == c &&
+    return sizeof(T) == 4 && split_mma && opt.ff_split_fused && !opt.dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || opt.ff_split_256) && f.w1.cin == c &&
            f.w2.cin == 4 * c && f.w1.kh == 1 && f.w2.kh == 1 && f.w1.bias >= 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
   }
   // ... and whether it also applies the attention's out-projection + residual in front (its PRE form: to_out's launch, the write of x1 by
@@ -1811,7 +1742,7 @@ class Engine : public EngineBase {
   bool ff_split_takes_out(const FFL& f, const AttnL& a) const {
     if (cur_stage < 0 || cur_stage > 3) return false;
     const int c = cfg.dim[cur_stage];
-    return ff_split_fused_ok(f, c) && ff_split_pre && fuse_ln && !dbg_on && !band_on && rwn < 0 && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
+    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_on && !band_on && rwn < 0 && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
   }
   bool ff_takes_out(const FFL& f, const AttnL& a) const {
     if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a);
@@ -1822,16 +1753,16 @@ class Engine : public EngineBase {
       if (cur_stage < 0 || cur_stage > 3 || !f.next) return false;
       const int c = cfg.dim[cur_stage];
       const ConvW& q = f.next->qkv;
-      return ff_split_fused_ok(f, c) && ff_split_pre && ff_split_post && fuse_ln && !dbg_on && !band_on && rwn < 0 && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
+      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_on && !band_on && rwn < 0 && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
              q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
     }
-    return ff_takes_out(f) && fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, cur_stage));
+    return ff_takes_out(f) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, cur_stage));
   }
   bool ff_split_ok(const FFL& f, int s, const AttnL* pre) const {
     const int c = cfg.dim[s];
     const int64_t m = (int64_t)sh[s] * sw[s];
-    return sizeof(T) == 2 && ff_split_max >= 2 && !pre && f.pack >= 0 && fuse_ff && fuse_ln && !band_on && !dbg_flags &&
-           ff_fused_supported(c, 4 * c) && small_map_tokens(s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
+    return sizeof(T) == 2 && opt.ff_split_max >= 2 && !pre && f.pack >= 0 && opt.fuse_ff && opt.fuse_ln && !band_on && !opt.dbg_flags &&
+           ff_fused_supported(c, 4 * c) && small_map_tokens(s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= opt.ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
   }
   // the form of a FeedForward (feedforward() below):
   //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
@@ -1845,10 +1776,10 @@ class Engine : public EngineBase {
   FFForm ff_form(const FFL& f, int s, const AttnL* pre) const {
     if (sizeof(T) == 2) {
       if (ff_split_ok(f, s, pre)) return FFForm::split;
-      if (f.pack >= 0 && fuse_ff && ff_big_enough()) return FFForm::fused;
-      const bool wide_ok = f.pack_wide >= 0 && !pre && fuse_ff && fuse_ln && !dbg_flags && rwn < 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
+      if (f.pack >= 0 && opt.fuse_ff && ff_big_enough()) return FFForm::fused;
+      const bool wide_ok = f.pack_wide >= 0 && !pre && opt.fuse_ff && opt.fuse_ln && !opt.dbg_flags && rwn < 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
       if (wide_ok && band_on && cdiv((int64_t)rw_rows(s) * sw[s], (int64_t)64) <= 128) return FFForm::wide_split;
-      if (wide_ok && !band_on && ff_wide >= 2) return FFForm::wide;
+      if (wide_ok && !band_on && opt.ff_wide >= 2) return FFForm::wide;
     } else if (ff_split_fused_ok(f, cfg.dim[s])) {
       return FFForm::split_bf16;
     }
@@ -1896,16 +1827,16 @@ class Engine : public EngineBase {
         fp.qkv = post ? reinterpret_cast<bf16_t*>(scratch) : nullptr; fp.ld_qkv = 3 * c;
         fp.csq = post ? f_dev + f.next->qkv.colsum : nullptr; fp.bq = post ? f_dev + f.next->qkv.bias : nullptr;
         fp.o = pre ? reinterpret_cast<const bf16_t*>(attn_o) : nullptr; fp.ld_o = c; fp.bo = pre ? f_dev + pre->out.bias : nullptr;
-        fp.stat_out = fuse_ln ? statpart : nullptr; fp.dbg = ff_dbg;
-        timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, (c == 128 && !pre && ff_small_px64 && cdiv(m, 128) < 128) ? 3 : ff_variant); });
-        stat_tiles_ready = fuse_ln ? 1 : 0;
+        fp.stat_out = opt.fuse_ln ? statpart : nullptr; fp.dbg = opt.ff_dbg;
+        timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, (c == 128 && !pre && opt.ff_small_px64 && cdiv(m, 128) < 128) ? 3 : opt.ff_variant); });
+        stat_tiles_ready = opt.fuse_ln ? 1 : 0;
       } else if (form == FFForm::split) {   // launch-bound maps (1-degree grid, C = 128 / 256 stages of 23 - 45 pixel tiles)
-        hidden_split(f.pack, std::min(ff_split_max, 4 * c / 32 / 4));
+        hidden_split(f.pack, std::min(opt.ff_split_max, 4 * c / 32 / 4));
       } else if (form == FFForm::wide_split) {
         // C = 512 (wx_ff.h ff_wide_supported) on lat-band ranks: a band of 2 000 - 4 000 stage-2 tokens is 32 - 63 pixel tiles -- S ranges
         // so that ~ff_wide_wgs workgroups run, instead of ff1 + split-K ff2 + finish
         ++n_ff_wide;
-        hidden_split(f.pack_wide, std::min(8, std::max(2, (int)cdiv(ff_wide_wgs, (int)cdiv(m, 64)))));
+        hidden_split(f.pack_wide, std::min(8, std::max(2, (int)cdiv(opt.ff_wide_wgs, (int)cdiv(m, 64)))));
       } else if (form == FFForm::wide) {   // an experiment: it loses on the unsharded map
         FFParams fp = block_params(f.pack_wide);
         fp.stat_out = statpart;
@@ -1922,7 +1853,7 @@ class Engine : public EngineBase {
         q.w1s = reinterpret_cast<const float*>(ws_dev + f.w1.wt); q.b1 = f_dev + f.w1.bias;
         q.w2s = reinterpret_cast<const float*>(ws_dev + f.w2.wt); q.b2 = f_dev + f.w2.bias;
         q.rowstat = rs; q.stat_tiles = pre ? 0 : stat_tiles_ready; q.stat_inv_c = 1.0f / (float)c;
-        q.stat_out = fuse_ln ? stat_dst(t0 + m, 1) + t0 : nullptr;
+        q.stat_out = opt.fuse_ln ? stat_dst(t0 + m, 1) + t0 : nullptr;
         if (!pre && q.stat_out && stat_tiles_ready > 1) {
           // the launch would read `statpart` as [M][stat_tiles_ready] in its prologue and write it as [M][1] in its epilogue: workgroup 2j's
           // stores land on the entries workgroup j still has to read, and nothing orders the two (lat-band ranks, WX_NO_FF_SPLIT_PRE,
@@ -1946,15 +1877,15 @@ class Engine : public EngineBase {
         n_split_gemms += 2;
         ++n_ff_split_fused;
         timed(post ? "out_ff_qkv_split_fused" : pre ? "out_ff_split_fused" : "ff_split_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c,
-              (post ? 6.0 : pre ? 3.0 : 2.0) * m * c * sizeof(T) + (post ? 12.0 : pre ? 9.0 : 8.0) * c * c * sizeof(T), [&] { launch_ff_split(c, q, cur_stream, ff_split_tw ? ff_split_tw : (cdiv(m, 128) >= 512 ? 2 : 1)); });
+              (post ? 6.0 : pre ? 3.0 : 2.0) * m * c * sizeof(T) + (post ? 12.0 : pre ? 9.0 : 8.0) * c * c * sizeof(T), [&] { launch_ff_split(c, q, cur_stream, opt.ff_split_tw ? opt.ff_split_tw : (cdiv(m, 128) >= 512 ? 2 : 1)); });
         stat_tiles_ready = q.stat_out ? 1 : 0;
       }
     }
     if (form == FFForm::chain) {
       const float2* rs = stream_stats(x, ld, c, m);
       // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
-      const KBlk blk = sizeof(T) == 2 && use_stream && use_dma && fuse_ln && !dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
-                       (rule_rows > 0 ? rule_rows : (int64_t)m) >= stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
+      const KBlk blk = sizeof(T) == 2 && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
+                       (rule_rows > 0 ? rule_rows : (int64_t)m) >= opt.stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
       gemm("gemm_ff1", f.w1, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 4 * c, .rs = rs, .act = 1, .blk = blk});
       stat_tiles_ready = gemm("gemm_ff2", f.w2, {.in = scratch, .in_h = h, .in_w = w, .in_ld = 4 * c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
                                                  .blk = blk, .want_stats = true}).stat_slots;
@@ -1994,10 +1925,9 @@ class Engine : public EngineBase {
       WX_HIP(hipGetLastError());
     });
   }
-  int gn_fold_max_tiles = getenv("WX_GN_FOLD_TILES") ? atoi(getenv("WX_GN_FOLD_TILES")) : 16;   // 12 tiles: 13 -> 9 us; 45 tiles: 13 -> 17 us (the serial fold in every workgroup)
   void group_norm_silu(const T* x, int c, int64_t m, int64_t g_off, int64_t b_off, const T* res, int64_t res_ld, T* out,
                        int64_t out_ld, int tiles) {   // tiles: the producing conv's GroupNorm partials (gn_local_stats)
-    if (tiles > 0 && tiles <= gn_fold_max_tiles) {   // few tiles: the apply kernel folds the partials itself (one launch instead of two)
+    if (tiles > 0 && tiles <= opt.gn_fold_max_tiles) {   // few tiles: the apply kernel folds the partials itself (one launch instead of two)
       gn_finalize_apply(x, c, m, m, g_off, b_off, res, res_ld, out, out_ld, tiles);
       return;
     }
@@ -2021,7 +1951,7 @@ class Engine : public EngineBase {
     // channel group = all of cpad0 while its [cg][65] fp32 tile stays under 64 KB of LDS; block origin shifted so that the 256-byte source
     // runs of the interior rows are line-aligned (wx_elem.h)
     const int cg = std::min(cpad0, 224);
-    const int xshift = pack_align ? (64 - p.pl % 64) % 64 : 0;
+    const int xshift = opt.pack_align ? (64 - p.pl % 64) % 64 : 0;
     timed("pack_input", 0.0, (double)C_in * nrows * cfg.image_width * 4.0 + (double)nrows * Wp * cpad0 * sizeof(T), [&] {
       hipLaunchKernelGGL(pack_input_kernel<T>, dim3(cdiv(Wp + xshift, 64), nrows), dim3(256), (size_t)cg * 65 * sizeof(float), cur_stream, p, cg, xshift);
       WX_HIP(hipGetLastError());
@@ -2036,7 +1966,7 @@ class Engine : public EngineBase {
     const int64_t ld = stream_ld(s);
     if (sh[s] <= 0) return;
     int choff = 0;
-    if (s >= 1 && st.merged.wt >= 0 && embed_merge && !band_on) {
+    if (s >= 1 && st.merged.wt >= 0 && opt.embed_merge && !band_on) {
       const int k = st.embed_k.back(), stv = cfg.embed_strides[s], pd = (k - stv) / 2;
       // ... which also leaves the LayerNorm partials of its rows for the stage's first sub-block
       stat_tiles_ready = gemm("gemm_embed", st.merged, {.in = in, .in_h = in_h, .in_w = sw[s - 1], .in_ld = in_ld_s, .out = x, .out_ld = ld, .stride = stv,
@@ -2046,7 +1976,7 @@ class Engine : public EngineBase {
     // stages 1-3: every branch's epilogue (or split-K finish) leaves the LayerNorm partials of ITS channel range in the shared row of
     // `statpart` -- the stage's first sub-block then needs no ln_stats launch (slot counts are predicted here and checked after each launch)
     int slots[8] = {0}, total_slots = 0;
-    bool share = s >= 1 && fuse_ln && use_dma && !band_on && !dbg_flags && stat_share && st.embed.size() <= 8;
+    bool share = s >= 1 && opt.fuse_ln && opt.use_dma && !band_on && !opt.dbg_flags && opt.stat_share && st.embed.size() <= 8;
     for (size_t b = 0; share && b < st.embed.size(); ++b) {
       const ConvW& w = st.embed[b];
       slots[b] = plain_split_ways(w, (int64_t)sh[s] * sw[s]) > 1 ? conv_gemm_finish_slots(w.n) : conv_gemm_n_tiles(w.n);
@@ -2057,14 +1987,14 @@ class Engine : public EngineBase {
     int slot_at = 0;
     for (size_t b = 0; b < st.embed.size(); ++b) {
       const int k = st.embed_k[b], stv = cfg.embed_strides[s], pd = (k - stv) / 2;
-      const bool patch_on = s == 0 && use_patch && st.embed_k.back() == 32 && st.patch.back().wt >= 0 && st.patch_tab >= 0;
+      const bool patch_on = s == 0 && opt.use_patch && st.embed_k.back() == 32 && st.patch.back().wt >= 0 && st.patch_tab >= 0;
       if (patch_on && k == 4 && st.ride4) { choff += st.embed[b].n; continue; }   // computed by the patch kernel's spare accumulator rows
       if (patch_on && st.patch[b].wt >= 0) {
         if (k != 32) { choff += st.embed[b].n; continue; }  // rides along in the fused launch issued with k = 32
         EmbedPatchParams ep;
         std::memset(&ep, 0, sizeof(ep));
         ep.xin = in; ep.xin_planar = in_planar; ep.Hb = in_h; ep.Wb = Wp + 2 * halo; ep.cpad = cpad0; ep.org = halo - 15;
-        ep.out_ld = ld; ep.out_h = sh[0]; ep.out_w = sw[0]; ep.dbg = dbg_flags;
+        ep.out_ld = ld; ep.out_h = sh[0]; ep.out_w = sw[0]; ep.dbg = opt.dbg_flags;
         ep.slot_tab = f_dev + st.patch_tab; ep.bias64 = f_dev + st.patch_bias64; ep.out_row = x;
         double fl = 0.0;
         int off = 0;
@@ -2084,8 +2014,8 @@ class Engine : public EngineBase {
         // small maps (1-degree grid, lat-band ranks): the serial walk over the channel chunks bounds the launch -> split it four
         // ways over blockIdx.y, fp32 partial sums, fixed-order finish kernel
         const int chunks0 = cpad0 / (16 / (int)sizeof(T));
-        if (embed_split && embed_patch_small_map(sh[0], sw[0], dbg_flags) && chunks0 >= 8) {
-          const int n_split = embed_split_ways;
+        if (opt.embed_split && embed_patch_small_map(sh[0], sw[0], opt.dbg_flags) && chunks0 >= 8) {
+          const int n_split = opt.embed_split_ways;
           const size_t need = (size_t)n_split * sh[0] * sw[0] * 64 * sizeof(float);
           if (need > embed_partial_bytes) {
             embed_partial = (float*)dalloc(need);   // grows at most a few times (batch / band geometry); dalloc's list frees the older ones at destroy
@@ -2093,7 +2023,7 @@ class Engine : public EngineBase {
           }
           ep.partial = embed_partial;
           ep.chunk_per = cdiv(chunks0, n_split);
-        } else if (embed_tail_split && !dbg_flags) {
+        } else if (opt.embed_tail_split && !opt.dbg_flags) {
           // big maps: the partly filled last round of tiles (0.25 degrees: 125 of 625) runs as ONE round of half-chunk workgroups
           const int tail = embed_patch_tail_rows(sh[0], sw[0], chunks0);
           if (tail > 0) {
@@ -2102,7 +2032,7 @@ class Engine : public EngineBase {
             ep.tail_partial = embed_tail;
           }
         }
-        const bool split_patch = split_mma && xs_planes && in == xin && !dbg_flags;
+        const bool split_patch = split_mma && xs_planes && in == xin && !opt.dbg_flags;
         if (split_patch) {   // the bf16 kernel over the K-concatenated (hi, lo) operands, fp32 out
           ep.xin = nullptr; ep.xin_planar = xs_planes; ep.cpad = 3 * cpad0; ep.plane_wrap = 2 * cpad0 / 8;   // chunks [2n, 3n) re-read the x_hi planes
           ep.wt32 = ep.wt16 = ep.wt8 = nullptr;
@@ -2113,7 +2043,7 @@ class Engine : public EngineBase {
             if (st.embed_k[j] == 16) ep.wt16 = sp16_dev + pw.wt16;
             if (st.embed_k[j] == 8) ep.wt8 = sp16_dev + pw.wt16;
           }
-          if (ep.chunk_per) ep.chunk_per = cdiv(3 * cpad0 / 8, embed_split_ways);
+          if (ep.chunk_per) ep.chunk_per = cdiv(3 * cpad0 / 8, opt.embed_split_ways);
           ++n_split_gemms;
         }
         timed("embed_patch", fl, (double)(in_h * Wp) * cpad0 * sizeof(T) + (double)sh[0] * sw[0] * 64 * sizeof(T), [&] {
@@ -2126,7 +2056,7 @@ class Engine : public EngineBase {
         // the branch that does not ride in the patch kernel (k = 4 of the 0.25-degree model: 64 channels, its own implicit GEMM) writes a
         // channel range of the rows nobody else writes and reads the packed input only: on the engine's side stream, beside the patch
         // launch (whose 625 tiles leave a partly filled last round), joined at the end of this function
-        const bool side = embed_side && patch_on && !band_on && !prof_on && !dbg_on && !dbg_flags && rwn < 0 && !side_open;
+        const bool side = opt.embed_side && patch_on && !band_on && !prof_on && !dbg_on && !opt.dbg_flags && rwn < 0 && !side_open;
         hipStream_t main_s = cur_stream;
         if (side) {
           side_ensure();
@@ -2172,28 +2102,27 @@ class Engine : public EngineBase {
   // register file (two 256-VGPR waves per SIMD) so the other half's attention only ever backfills a tail, and that is worth less than
   // the halved launches cost.  (Two whole forecasts in flight gain 5-7 % because their launches keep full size and the overlapping
   // kernels are of different kinds.)  OFF by default; WX_TWO_STREAM=1 keeps it testable (bit-identical, tests/test_variants_gpu.py).
-  int two_stream = getenv("WX_TWO_STREAM") ? atoi(getenv("WX_TWO_STREAM")) : 0;   // 0 off; 1 on where it applies; 2 / 3: stages with a dilated / pointwise long window only (probes)
   hipStream_t side_stream = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool two_stream_ok(int s) const {
-    if (sizeof(T) != 2 || !two_stream || band_on || dbg_on || prof_on || dbg_flags || !use_stream || !use_dma || !fuse_ln) return false;
-    if (cfg.dim_head != 32 || cfg.dim[s] < 512 || (int64_t)sh[s] * sw[s] < stream_min_rows) return false;
+    if (sizeof(T) != 2 || !opt.two_stream || band_on || dbg_on || prof_on || opt.dbg_flags || !opt.use_stream || !opt.use_dma || !opt.fuse_ln) return false;
+    if (cfg.dim_head != 32 || cfg.dim[s] < 512 || (int64_t)sh[s] * sw[s] < opt.stream_min_rows) return false;
     const StageL& st = stages[s];
     if (st.blocks.empty()) return false;
     const int wsz = st.blocks[0].sa.wsz;
     if (wsz <= 1 || sh[s] / wsz < 2) return false;
     const bool pointwise_long = st.blocks[0].la.wsz == 1;
-    if ((two_stream == 2 && pointwise_long) || (two_stream == 3 && !pointwise_long)) return false;   // probes: one kind of stage only
+    if ((opt.two_stream == 2 && pointwise_long) || (opt.two_stream == 3 && !pointwise_long)) return false;   // probes: one kind of stage only
     for (const BlockL& bl : st.blocks)
       if (attn_block_ok(bl.sa, s) || attn_block_ok(bl.la, s) || bl.sf.pack >= 0 || bl.lf.pack >= 0 || bl.sa.wsz != wsz) return false;
     return true;
   }
   void side_ensure() {
     if (side_stream) return;
-    if (const char* e = getenv("WX_TWO_STREAM_PRIO")) {   // probe: the side stream at the lowest (1) / highest (2) priority
+    if (opt.two_stream_prio != INT_MIN) {   // probe: the side stream at the highest (2) / lowest (any other value) priority
       int lo = 0, hi = 0;
       WX_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      WX_HIP(hipStreamCreateWithPriority(&side_stream, hipStreamNonBlocking, atoi(e) == 2 ? hi : lo));
+      WX_HIP(hipStreamCreateWithPriority(&side_stream, hipStreamNonBlocking, opt.two_stream_prio == 2 ? hi : lo));
     } else {
       WX_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
     }
@@ -2498,7 +2427,7 @@ class Engine : public EngineBase {
   bool b_async = false, b_cstream_own = false;
   // interior / boundary split of the convolutions behind a halo exchange: OFF unless an overlapped transport asks for it (measured on
   // MI355X, profiles/r03_latband_overlap_virtual_ranks_C3_bf16.txt: the two one-row launches cost each rank more than the ~20 us exchange they would hide)
-  bool b_split = getenv("WX_BAND_SPLIT") && getenv("WX_BAND_SPLIT")[0] == '1';
+  bool b_split = opt.band_split;   // set by band_comm_stream
   void* band_comm_stream(void* adopt) override {
     band_need();
     WX_HIP(hipSetDevice(device));
@@ -2527,7 +2456,6 @@ class Engine : public EngineBase {
   size_t b_pc = 0;
   int b_pending = -1;
   int b_unpack_slots = 0;   // > 0: the last band_unpack left that many LayerNorm partials per token of the layout it filled
-  bool band_stats_ship = !getenv("WX_NO_BAND_STATS");
   const float *bx_own = nullptr, *bfrc_own = nullptr;
   float *by = nullptr, *by_phys = nullptr, *bx_next = nullptr;
   int attn_kind_override = -1;
@@ -2595,7 +2523,7 @@ class Engine : public EngineBase {
     const int64_t xin_elems = (int64_t)(st0 * g.rows_short(0, rank) + 2 * halo + 2) * (Wp + 2 * halo + 2) * cpad0;
     bxin = (T*)dalloc(xin_elems * sizeof(T));
     WX_HIP(hipMemset(bxin, 0, xin_elems * sizeof(T)));
-    if (use_patch && planar_xin) {
+    if (opt.use_patch && opt.planar_xin) {
       bxin_planar = (T*)dalloc(xin_elems * sizeof(T));
       WX_HIP(hipMemset(bxin_planar, 0, xin_elems * sizeof(T)));
     }
@@ -2782,7 +2710,7 @@ class Engine : public EngineBase {
     // the two copies below (wx_band.h: to_long / to_short gather whole layouts, no zero fill), so the sub-block behind the exchange
     // starts from statpart instead of an ln_stats launch
     int slots = 0, row_off = 0, rows = 0;
-    if (band_stats_ship && fuse_ln && (x.name.compare(0, 8, "to_long.") == 0 || x.name.compare(0, 9, "to_short.") == 0) && d.n_zero == 0) {
+    if (opt.band_stats_ship && opt.fuse_ln && (x.name.compare(0, 8, "to_long.") == 0 || x.name.compare(0, 9, "to_short.") == 0) && d.n_zero == 0) {
       const int64_t w16 = dv.width / 16;
       const bool to_long = x.dst_buf == BB_STREAM_L;
       rows = to_long ? bplan.g.rows_long(x.stage, b_rank) : bplan.g.rows_short(x.stage, b_rank);
@@ -3102,7 +3030,7 @@ class Engine : public EngineBase {
     if (!b_recv && b_recv_need) b_recv = (char*)dalloc((size_t)b_recv_need);
     b_msgs.resize(bplan.xs.size());
     for (size_t x = 0; x < bplan.xs.size(); ++x) band_messages(bplan.xs[x], b_rank, &b_msgs[x].first, &b_msgs[x].second);
-    if (getenv("WX_BAND_OVERLAP") && getenv("WX_BAND_OVERLAP")[0] == '1') band_comm_stream(nullptr);
+    if (opt.band_overlap) band_comm_stream(nullptr);
   }
   void band_step_rccl(const float* x_own, const float* frc_own, float* y, float* y_phys, float* x_next, hipStream_t s) override {
     if (!b_comm) throw StateError("wx_band_step_rccl: no communicator (wx_band_rccl_init)");
@@ -3196,12 +3124,8 @@ class Engine : public EngineBase {
     for (auto& kv : roll_graphs) (void)hipGraphExecDestroy(kv.second);
     roll_graphs.clear();
   }
-  // WX_GRAPH=1 replays each step from a captured hipGraph.  OFF by default, on measurement (MI355X, 1-degree model, 48 steps): eager
-  // 557.7 steps/s (1.79 ms/step, ~170 launches), graph replay 484.8 (2.06 ms): on this stack the cost between two dependent kernels is
-  // the device-side dispatch boundary (~1.5 us, MI355X_MICROARCH.md "boundary": eager == hipGraph), not host launch time, so a graph
-  // removes nothing and adds its replay overhead plus the forcing staging copy.
-  int graph_mode = getenv("WX_GRAPH") ? atoi(getenv("WX_GRAPH")) : 0;
-  bool want_graph() const { return graph_mode == 1 && !prof_on && !dbg_on && !band_on && !post; }
+  // WX_GRAPH=1 (Options::graph_mode) replays each step from a captured hipGraph; off by default, measured slower (wx_options.h)
+  bool want_graph() const { return opt.graph_mode == 1 && !prof_on && !dbg_on && !band_on && !post; }
   void step_body(const float* x, const float* frc, float* y_phys, float* x_next, hipStream_t s, bool with_static = true) {
     cur_stream = s;
     core(x);
@@ -3323,9 +3247,10 @@ int wx_create(const wx_config* cfg, int device, wx_handle* out) {
     if (device < 0 || device >= ndev) throw wx::ConfigError("wx_create: no such GPU device");
     WX_HIP(hipSetDevice(device));
     std::unique_ptr<wx_engine> h(new wx_engine);
-    if (cfg->precision == WX_PREC_FP32) h->impl.reset(new wx::Engine<float>(*cfg, device));
-    else if (cfg->precision == WX_PREC_FP32_SPLIT) h->impl.reset(new wx::Engine<float>(*cfg, device, /*split=*/true));
-    else if (cfg->precision == WX_PREC_BF16) h->impl.reset(new wx::Engine<wx::bf16_t>(*cfg, device));
+    const wx::Options opt = wx::Options::from_env();
+    if (cfg->precision == WX_PREC_FP32) h->impl.reset(new wx::Engine<float>(*cfg, device, opt));
+    else if (cfg->precision == WX_PREC_FP32_SPLIT) h->impl.reset(new wx::Engine<float>(*cfg, device, opt, /*split=*/true));
+    else if (cfg->precision == WX_PREC_BF16) h->impl.reset(new wx::Engine<wx::bf16_t>(*cfg, device, opt));
     else throw wx::ConfigError("wx_create: unknown precision");
     *out = h.release();
   });
@@ -3433,12 +3358,13 @@ int wx_band_plan_create(const wx_config* cfg, int nranks, wx_band_plan* out) {
     if (!cfg || !out) throw wx::ConfigError("wx_band_plan_create: null argument");
     if (nranks < 1) throw wx::ConfigError("wx_band_plan_create: nranks must be >= 1");
     std::unique_ptr<wx_band_plan_s> p(new wx_band_plan_s);
+    const wx::Options opt = wx::Options::from_env();
     if (cfg->precision == WX_PREC_FP32 || cfg->precision == WX_PREC_FP32_SPLIT) {   // the plan depends on geometry, not on arithmetic
-      wx::Engine<float> e(*cfg, -1);
+      wx::Engine<float> e(*cfg, -1, opt);
       wx::Engine<float>::band_check_supported(e);
       p->plan.build(wx::Engine<float>::band_model(e, nranks));
     } else {
-      wx::Engine<wx::bf16_t> e(*cfg, -1);
+      wx::Engine<wx::bf16_t> e(*cfg, -1, opt);
       wx::Engine<wx::bf16_t>::band_check_supported(e);
       p->plan.build(wx::Engine<wx::bf16_t>::band_model(e, nranks));
     }
@@ -3688,10 +3614,11 @@ int wx_swin_create(const wx_swin_desc* d, int device, wx_swin_handle* out) {
     wx::SwinDesc sd{d->H, d->W, d->C, d->heads, d->wsz_y, d->wsz_x, d->depth, d->hidden, d->shift_y, d->shift_x, d->mask_value, d->ln_eps};
     if (d->mask_axes != 0 && d->mask_axes != 1 && d->mask_axes != 3) throw wx::ConfigError("swin: mask_axes must be 1 (latitude) or 3 (both axes)");
     sd.mask_axes = d->mask_axes == 3 ? 3 : 1;
+    const wx::Options opt = wx::Options::from_env();
     auto w = std::make_unique<wx_swin>();
     try {
-      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::SwinStage<wx::bf16_t>>(sd, device);
-      else w->impl = std::make_unique<wx::SwinStage<float>>(sd, device, d->precision == WX_PREC_FP32_SPLIT);
+      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::SwinStage<wx::bf16_t>>(sd, device, opt);
+      else w->impl = std::make_unique<wx::SwinStage<float>>(sd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
     } catch (const std::runtime_error& e) {
       throw wx::ConfigError(e.what());
     }
@@ -3738,10 +3665,11 @@ int wx_fuxi_create(const wx_fuxi_desc* d, int device, wx_fuxi_handle* out) {
     if (d->stage_variant != WX_STAGE_V2_CR && d->stage_variant != WX_STAGE_TIMM_V2) throw wx::ConfigError("fuxi: unknown stage_variant");
     wx::FuxiDesc fd{d->H, d->W, d->C_in, d->C_out, d->frames, d->patch_h, d->patch_w, d->dim, d->heads, d->window, d->depth, d->groups_down, d->groups_up};
     fd.stage_variant = d->stage_variant;
+    const wx::Options opt = wx::Options::from_env();
     auto w = std::make_unique<wx_fuxi>();
     try {
-      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::FuxiModel<wx::bf16_t>>(fd, device);
-      else w->impl = std::make_unique<wx::FuxiModel<float>>(fd, device, d->precision == WX_PREC_FP32_SPLIT);
+      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::FuxiModel<wx::bf16_t>>(fd, device, opt);
+      else w->impl = std::make_unique<wx::FuxiModel<float>>(fd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
     } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) {
       throw wx::ConfigError(e.what());
     }

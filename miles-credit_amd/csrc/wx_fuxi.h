@@ -166,7 +166,8 @@ struct FuxiModel : FuxiBase {
   // re-encoded shadow copy of its weight (wx_swin.h SwinStage::split); GroupNorm, LayerNorm, the patch reshapes and the attention stay fp32
   bool split = false;
   std::map<const void*, T*> split_of;
-  FuxiModel(const FuxiDesc& desc, int dev, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4) {
+  const Options opt;   // the run-time switches, read once by wx_fuxi_create (wx_options.h)
+  FuxiModel(const FuxiDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4), opt(o) {
     if (d.H % d.ph || d.W % d.pw) throw std::runtime_error("fuxi: the image must be a multiple of the patch");
     Hp = d.H / d.ph; Wp = d.W / d.pw;
     if (Hp % 2 || Wp % 2) throw std::runtime_error("fuxi: the patch grid must be even (DownBlock halves it, UpBlock doubles it back)");
@@ -185,7 +186,7 @@ struct FuxiModel : FuxiBase {
     if (Hs <= d.wsz) sd.shift_y = 0;
     if (Ws <= d.wsz) sd.shift_x = 0;
     sd.mask_axes = d.stage_variant == 1 ? 3 : 1;   // timm's block masks the longitude seam too
-    stage = std::make_unique<SwinStage<T>>(sd, device, split);
+    stage = std::make_unique<SwinStage<T>>(sd, device, opt, split);
     const size_t dim = d.dim, Mp = (size_t)Hp * Wp, Md = (size_t)Hd * Wd, Ms = (size_t)Hs * Ws;
     auto wT = [&](size_t n) { return (T*)dalloc(n * sizeof(T)); };
     auto wf = [&](size_t n) { float* p = (float*)dalloc(n * 4); return p; };
@@ -336,7 +337,7 @@ struct FuxiModel : FuxiBase {
       const auto it = split_of.find(w);
       if (it != split_of.end() && cin % 32 == 0 && conv_gemm_is_dma<T>(p, zero_page)) { p.split = 1; p.wt = it->second; }
     }
-    launch_conv_gemm<T>(p, zero_page, s, 0);
+    launch_conv_gemm<T>(p, zero_page, s, 0, opt.gemm_deep_tiles);
   }
   // out = SiLU(GroupNorm(x)) [+ res]
   void gn_silu(const T* x, int64_t m, const float* g, const float* b, int groups, const T* res, T* out, int64_t out_ld, hipStream_t s) {

@@ -19,6 +19,7 @@
 #include "wx_attn.h"
 #include "wx_gemm.h"
 #include "wx_gemm_stream.h"
+#include "wx_options.h"
 
 namespace wx {
 
@@ -127,7 +128,8 @@ struct SwinStage : SwinStageBase {
   // (general head dimension, seam mask, cosine mode) and the LayerNorm kernels stay exact fp32
   bool split = false;
   std::map<const void*, T*> split_of;
-  SwinStage(const SwinDesc& desc, int dev, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4) {
+  const Options opt;   // the run-time switches, read once by wx_swin_create / wx_fuxi_create (wx_options.h)
+  SwinStage(const SwinDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4), opt(o) {
     constexpr int VEC = 16 / (int)sizeof(T);
     if (d.C % 64 || d.hidden % 64 || d.C % d.heads) throw std::runtime_error("swin: C and hidden must be multiples of 64, C of heads");
     const int hd = d.C / d.heads;
@@ -151,8 +153,7 @@ struct SwinStage : SwinStageBase {
       b.bias_tab = (float*)dalloc((size_t)d.heads * NP * NP * 4);
       b.logit = (float*)dalloc(d.heads * 4);
     }
-    const size_t stream_min_rows = getenv("WX_SWIN_STREAM_MIN_ROWS") ? (size_t)atoll(getenv("WX_SWIN_STREAM_MIN_ROWS")) : 4096;
-    use_stream = sizeof(T) == 2 && M >= stream_min_rows && d.C >= 512 && d.C % 256 == 0 && d.hidden % 256 == 0 && !getenv("WX_SWIN_NO_STREAM");
+    use_stream = sizeof(T) == 2 && M >= (size_t)opt.swin_stream_min_rows && d.C >= 512 && d.C % 256 == 0 && d.hidden % 256 == 0 && opt.swin_stream;
     if (use_stream) {
       for (Block& b : blocks) {
         b.wqkv_kb = (T*)dalloc((size_t)3 * d.C * d.C * sizeof(T));
@@ -278,7 +279,7 @@ struct SwinStage : SwinStageBase {
       const auto it = split_of.find(w);
       if (it != split_of.end() && K % 32 == 0 && conv_gemm_is_dma<T>(p, zero_page)) { p.split = 1; p.wt = it->second; }
     }
-    launch_conv_gemm<T>(p, zero_page, s, 0);
+    launch_conv_gemm<T>(p, zero_page, s, 0, opt.gemm_deep_tiles);
   }
   void apply(const void* x_in, void* x_out, hipStream_t s) override {
     if (!ready) throw std::runtime_error("swin: call wx_swin_finalize after loading every tensor");

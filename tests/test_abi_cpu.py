@@ -275,3 +275,14 @@ def test_library_version_carries_the_source_hash(lib):
             return b"wxengine 0.2 (gfx950) wxsrc:0123456789abcdef"
     with pytest.raises(E.WXEngineError, match="built from other sources"):
         E._check_not_stale(Fake())
+
+
+def test_run_time_switches_are_read_in_one_place_and_documented():
+    """Every WX_* switch of the native code is read by Options::from_env() (csrc/wx_options.h) and nowhere else, and the
+    INTEGRATION.md table lists exactly those switches."""
+    csrc = os.path.join(ROOT, "miles-credit_amd", "csrc")
+    readers = sorted(f for f in os.listdir(csrc) if "getenv" in open(os.path.join(csrc, f)).read())
+    assert readers == ["wx_options.h"]
+    read = set(re.findall(r'"(WX_[A-Z0-9_]+)"', open(os.path.join(csrc, "wx_options.h")).read()))
+    doc = set(re.findall(r"^\| `(WX_[A-Z0-9_]+)` \|", open(os.path.join(ROOT, "INTEGRATION.md")).read(), re.M))
+    assert read and read == doc, f"read but not documented: {sorted(read - doc)}; documented but not read: {sorted(doc - read)}"

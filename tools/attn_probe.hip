@@ -41,10 +41,10 @@ int main(int argc, char** argv) {
   const int n_win = (H / wsz) * (W / wsz);
   const size_t tasks = (size_t)((n_win + pack - 1) / pack) * heads;
   hipStream_t st; WX_HIP(hipStreamCreate(&st));
-  for (int i = 0; i < 3; ++i) launch_window_attn<elem_t>(p, st);
+  for (int i = 0; i < 3; ++i) launch_window_attn<elem_t>(p, st, 0, false);
   hipEvent_t e0, e1; WX_HIP(hipEventCreate(&e0)); WX_HIP(hipEventCreate(&e1));
   WX_HIP(hipEventRecord(e0, st));
-  for (int i = 0; i < 20; ++i) launch_window_attn<elem_t>(p, st);
+  for (int i = 0; i < 20; ++i) launch_window_attn<elem_t>(p, st, 0, false);
   WX_HIP(hipEventRecord(e1, st)); WX_HIP(hipStreamSynchronize(st));
   float ms; WX_HIP(hipEventElapsedTime(&ms, e0, e1));
   printf("H=%d W=%d C=%d wsz=%d kind=%d tasks=%zu nkf=%d: %.1f us\n", H, W, C, wsz, kind, tasks, nkf, ms * 1e3 / 20);
@@ -54,7 +54,7 @@ int main(int argc, char** argv) {
   unsigned long long* tr = (unsigned long long*)dalloc(tasks * 64);
   WX_HIP(hipMemset(tr, 0, tasks * 64));
   p.trace = tr;
-  launch_window_attn<elem_t>(p, st);
+  launch_window_attn<elem_t>(p, st, 0, false);
   WX_HIP(hipStreamSynchronize(st));
   std::vector<unsigned long long> t(tasks * 8);
   WX_HIP(hipMemcpy(t.data(), tr, tasks * 64, hipMemcpyDeviceToHost));
