@@ -1,0 +1,506 @@
+// wxengine: the C ABI of include/wxengine.h -- exception-to-status mapping and the extern "C" wrappers of every handle type
+// (engine, lat-band plan, pre block, post block, window attention, Swin stage, FuXi model).  Included last by wx_engine.hip: it
+// needs every class defined there and in the headers before it.
+#pragma once
+
+namespace wx {
+static thread_local std::string g_last_error;
+}  // namespace wx
+
+struct wx_engine {
+  std::unique_ptr<wx::EngineBase> impl;
+};
+
+template <typename F>
+static int guarded(F&& fn) {
+  try {
+    fn();
+    return WX_OK;
+  } catch (const wx::ConfigError& e) { wx::g_last_error = e.what(); return WX_ERR_INVALID;
+  } catch (const wx::StateError& e) { wx::g_last_error = e.what(); return WX_ERR_STATE;
+  } catch (const wx::MissingError& e) { wx::g_last_error = e.what(); return WX_ERR_MISSING;
+  } catch (const wx::ShapeError& e) { wx::g_last_error = e.what(); return WX_ERR_SHAPE;
+  } catch (const wx::HipError& e) { wx::g_last_error = e.what(); return WX_ERR_HIP;
+  } catch (const std::exception& e) { wx::g_last_error = e.what(); return WX_ERR_INVALID; }
+}
+#define WX_NEED(h) if (!(h) || !(h)->impl) throw wx::ConfigError("null engine handle")
+static void need_device(int device, const char* fn) {
+  int ndev = 0;
+  WX_HIP(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) throw wx::ConfigError(std::string(fn) + ": no such GPU device");
+}
+// a wrapped object's std::runtime_error becomes the ABI error class `Err`; a HIP failure keeps its own
+template <typename Err, typename F>
+static void remap(F&& fn) {
+  try {
+    fn();
+  } catch (const wx::HipError&) {
+    throw;
+  } catch (const std::runtime_error& e) {
+    throw Err(e.what());
+  }
+}
+
+extern "C" {
+
+int wx_create(const wx_config* cfg, int device, wx_handle* out) {
+  return guarded([&] {
+    if (!cfg || !out) throw wx::ConfigError("wx_create: null argument");
+    need_device(device, "wx_create");
+    WX_HIP(hipSetDevice(device));
+    std::unique_ptr<wx_engine> h(new wx_engine);
+    const wx::Options opt = wx::Options::from_env();
+    if (cfg->precision == WX_PREC_FP32) h->impl.reset(new wx::Engine<float>(*cfg, device, opt));
+    else if (cfg->precision == WX_PREC_FP32_SPLIT) h->impl.reset(new wx::Engine<float>(*cfg, device, opt, /*split=*/true));
+    else if (cfg->precision == WX_PREC_BF16) h->impl.reset(new wx::Engine<wx::bf16_t>(*cfg, device, opt));
+    else throw wx::ConfigError("wx_create: unknown precision");
+    *out = h.release();
+  });
+}
+int wx_destroy(wx_handle h) {
+  return guarded([&] { delete h; });
+}
+int wx_load_tensor(wx_handle h, const char* key, const float* data, int ndim, const int64_t* shape) {
+  return guarded([&] { WX_NEED(h); if (!key || !data || !shape) throw wx::ConfigError("wx_load_tensor: null argument"); h->impl->load_tensor(key, data, ndim, shape); });
+}
+int wx_finalize_weights(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->finalize(); }); }
+int wx_num_tensors(wx_handle h) { return (h && h->impl) ? h->impl->num_tensors() : WX_ERR_INVALID; }
+int wx_tensor_info(wx_handle h, int index, const char** key, int* ndim, int64_t shape[8]) {
+  return guarded([&] { WX_NEED(h); h->impl->tensor_info(index, key, ndim, shape); });
+}
+int wx_set_denorm(wx_handle h, const float* mean, const float* stdv, int n) {
+  return guarded([&] { WX_NEED(h); if (!mean || !stdv) throw wx::ConfigError("wx_set_denorm: null argument"); h->impl->set_denorm(mean, stdv, n); });
+}
+int wx_set_tracer_fixer(wx_handle h, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
+  return guarded([&] { WX_NEED(h); if (n > 0 && (!inds || !thres)) throw wx::ConfigError("wx_set_tracer_fixer: null argument"); h->impl->set_tracer(inds, thres, thres_max, n, denorm); });
+}
+int wx_set_layout(wx_handle h, int n_prog, int n_static, int n_dyn) {
+  return guarded([&] { WX_NEED(h); h->impl->set_layout(n_prog, n_static, n_dyn); });
+}
+int wx_set_layout_groups(wx_handle h, int n_groups, const int32_t* kind, const int32_t* x_start, const int32_t* src_start, const int32_t* count) {
+  return guarded([&] { WX_NEED(h); h->impl->set_layout_groups(n_groups, kind, x_start, src_start, count); });
+}
+int wx_forward(wx_handle h, const float* x_dev, float* y_dev, int batch, void* stream) {
+  return guarded([&] { WX_NEED(h); if (!x_dev || !y_dev) throw wx::ConfigError("wx_forward: null pointer"); h->impl->forward(x_dev, y_dev, batch, (hipStream_t)stream); });
+}
+int wx_step(wx_handle h, const float* x_dev, const float* frc_dev, float* y_dev, float* y_phys_dev, float* x_next_dev, void* stream) {
+  return guarded([&] { WX_NEED(h); if (!x_dev) throw wx::ConfigError("wx_step: null input"); h->impl->step(x_dev, frc_dev, y_dev, y_phys_dev, x_next_dev, (hipStream_t)stream); });
+}
+int wx_rollout(wx_handle h, const float* x0_dev, const float* const* frc_dev, int n_steps, float* const* y_phys_dev, float* x_final_dev,
+               void* stream) {
+  return guarded([&] { WX_NEED(h); h->impl->rollout(x0_dev, frc_dev, n_steps, y_phys_dev, x_final_dev, (hipStream_t)stream); });
+}
+int wx_band_enable(wx_handle h, int rank, int nranks) { return guarded([&] { WX_NEED(h); h->impl->band_enable(rank, nranks); }); }
+int wx_band_info(wx_handle h, int* own_row0, int* own_rows, int64_t* send_bytes, int64_t* recv_bytes, int* n_exchanges) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!own_row0 || !own_rows || !send_bytes || !recv_bytes || !n_exchanges) throw wx::ConfigError("wx_band_info: null argument");
+    h->impl->band_info(own_row0, own_rows, send_bytes, recv_bytes, n_exchanges);
+  });
+}
+int wx_band_set_staging(wx_handle h, void* send_dev, int64_t send_bytes, void* recv_dev, int64_t recv_bytes) {
+  return guarded([&] { WX_NEED(h); h->impl->band_set_staging(send_dev, send_bytes, recv_dev, recv_bytes); });
+}
+int wx_band_exchange(wx_handle h, int xid, wx_band_msg* sends, int cap_sends, int* n_sends, wx_band_msg* recvs, int cap_recvs, int* n_recvs) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!sends || !recvs || !n_sends || !n_recvs) throw wx::ConfigError("wx_band_exchange: null argument");
+    h->impl->band_messages_of(xid, sends, cap_sends, n_sends, recvs, cap_recvs, n_recvs);
+  });
+}
+int wx_band_begin(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band, void* stream,
+                  int* next_xid) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!next_xid) throw wx::ConfigError("wx_band_begin: null next_xid");
+    *next_xid = h->impl->band_begin(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream);
+  });
+}
+int wx_band_resume(wx_handle h, int* next_xid) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!next_xid) throw wx::ConfigError("wx_band_resume: null next_xid");
+    *next_xid = h->impl->band_resume();
+  });
+}
+int wx_band_comm_stream(wx_handle h, void* adopt_stream, void** stream_out) {
+  return guarded([&] {
+    WX_NEED(h);
+    void* st = h->impl->band_comm_stream(adopt_stream);
+    if (stream_out) *stream_out = st;
+  });
+}
+int wx_band_rccl_unique_id(uint8_t id[128]) {
+  return guarded([&] {
+    if (!id) throw wx::ConfigError("wx_band_rccl_unique_id: null argument");
+    wx::RcclApi& api = wx::RcclApi::get();
+    ncclUniqueId u;
+    api.check(api.GetUniqueId(&u), "ncclGetUniqueId");
+    static_assert(sizeof(u) == 128, "ncclUniqueId size");
+    std::memcpy(id, &u, 128);
+  });
+}
+int wx_band_rccl_init(wx_handle h, const uint8_t id[128]) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!id) throw wx::ConfigError("wx_band_rccl_init: null argument");
+    ncclUniqueId u;
+    std::memcpy(&u, id, 128);
+    h->impl->band_rccl_init(u);
+  });
+}
+int wx_band_step_rccl(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band,
+                      void* stream) {
+  return guarded([&] { WX_NEED(h); h->impl->band_step_rccl(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream); });
+}
+// host-only plan: the model spec supplies the derived geometry (no HIP call is made)
+struct wx_band_plan_s { wx::BandPlan plan; };
+int wx_band_plan_create(const wx_config* cfg, int nranks, wx_band_plan* out) {
+  return guarded([&] {
+    if (!cfg || !out) throw wx::ConfigError("wx_band_plan_create: null argument");
+    if (nranks < 1) throw wx::ConfigError("wx_band_plan_create: nranks must be >= 1");
+    std::unique_ptr<wx_band_plan_s> p(new wx_band_plan_s);
+    const wx::ModelSpec spec(*cfg);
+    wx::band_check_supported(spec);
+    // the plan depends on geometry and the element size, not on arithmetic
+    const bool f32 = cfg->precision == WX_PREC_FP32 || cfg->precision == WX_PREC_FP32_SPLIT;
+    p->plan.build(wx::band_model(spec, nranks, f32 ? 4 : 2, 0));
+    *out = p.release();
+  });
+}
+int wx_band_plan_destroy(wx_band_plan p) { return guarded([&] { delete p; }); }
+int wx_band_plan_num_exchanges(wx_band_plan p, int* n) {
+  return guarded([&] { if (!p || !n) throw wx::ConfigError("null argument"); *n = (int)p->plan.xs.size(); });
+}
+int wx_band_plan_exchange_name(wx_band_plan p, int xid, const char** name) {
+  return guarded([&] {
+    if (!p || !name || xid < 0 || xid >= (int)p->plan.xs.size()) throw wx::ConfigError("wx_band_plan_exchange_name: bad argument");
+    *name = p->plan.xs[xid].name.c_str();
+  });
+}
+int wx_band_plan_messages(wx_band_plan p, int xid, int rank, wx_band_msg* sends, int cap_sends, int* n_sends, wx_band_msg* recvs,
+                          int cap_recvs, int* n_recvs) {
+  return guarded([&] {
+    if (!p || !sends || !recvs || !n_sends || !n_recvs || xid < 0 || xid >= (int)p->plan.xs.size() || rank < 0 || rank >= p->plan.m.n)
+      throw wx::ConfigError("wx_band_plan_messages: bad argument");
+    std::vector<wx::BandMsg> s, r;
+    wx::band_messages(p->plan.xs[xid], rank, &s, &r);
+    if ((int)s.size() > cap_sends || (int)r.size() > cap_recvs) throw wx::ConfigError("wx_band_plan_messages: arrays too small");
+    for (size_t i = 0; i < s.size(); ++i) sends[i] = wx_band_msg{s[i].peer, s[i].offset, s[i].bytes};
+    for (size_t i = 0; i < r.size(); ++i) recvs[i] = wx_band_msg{r[i].peer, r[i].offset, r[i].bytes};
+    *n_sends = (int)s.size(); *n_recvs = (int)r.size();
+  });
+}
+int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts) {
+  return guarded([&] {
+    if (!p || !starts || which < 0 || which > 8) throw wx::ConfigError("wx_band_plan_partition: bad argument");
+    const std::vector<int>& v = which < 4 ? p->plan.g.ps[which] : which < 8 ? p->plan.g.pl[which - 4] : p->plan.g.po;
+    for (size_t i = 0; i < v.size(); ++i) starts[i] = v[i];
+  });
+}
+int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step) {
+  return guarded([&] { WX_NEED(h); h->impl->set_noise(seed, member0, step); });
+}
+int wx_set_noise_tape(wx_handle h, const float* const* draws, int n) {
+  return guarded([&] { WX_NEED(h); h->impl->set_noise_tape(draws, n); });
+}
+int wx_set_debug(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->set_debug(enable); }); }
+int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]) {
+  return guarded([&] { WX_NEED(h); if (!name || !shape) throw wx::ConfigError("wx_debug_read: null argument"); h->impl->debug_read(name, host_out, capacity, shape); });
+}
+int wx_query(wx_handle h, const char* key, int64_t* value) {
+  return guarded([&] {
+    WX_NEED(h);
+    if (!key || !value) throw wx::ConfigError("wx_query: null argument");
+    if (!h->impl->query(key, value)) throw wx::ConfigError(std::string("wx_query: unknown key '") + key + "'");
+  });
+}
+int wx_profile(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->profile(enable); }); }
+int wx_profile_reset(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->profile_reset(); }); }
+int wx_profile_read(wx_handle h, wx_kernel_stat* out, int capacity, int* count) {
+  return guarded([&] { WX_NEED(h); if (!out || !count) throw wx::ConfigError("wx_profile_read: null argument"); *count = h->impl->profile_read(out, capacity); });
+}
+// ---- pre block (input normalisation + channel concatenation) ---------------------------------------------------------
+struct wx_pre {
+  std::unique_ptr<wx::PreBlock> impl;
+};
+int wx_pre_create(int n_fields, const int32_t* n_levels, int frames, int H, int W, const float* mean, const float* stdv, int device,
+                  wx_pre_handle* out) {
+  return guarded([&] {
+    if (!out || !n_levels) throw wx::ConfigError("wx_pre_create: null argument");
+    need_device(device, "wx_pre_create");
+    std::unique_ptr<wx_pre> p(new wx_pre);
+    p->impl.reset(new wx::PreBlock(n_fields, n_levels, frames, H, W, mean, stdv, device));
+    *out = p.release();
+  });
+}
+int wx_pre_destroy(wx_pre_handle p) { return guarded([&] { delete p; }); }
+int wx_pre_channels(wx_pre_handle p, int* channels) {
+  return guarded([&] { if (!p || !p->impl || !channels) throw wx::ConfigError("wx_pre_channels: null argument"); *channels = p->impl->channels(); });
+}
+int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, int batch, void* stream) {
+  return guarded([&] {
+    if (!p || !p->impl || !fields_dev || !x_dev) throw wx::ConfigError("wx_pre_apply: null argument");
+    p->impl->apply(fields_dev, x_dev, batch, (hipStream_t)stream);
+  });
+}
+// ---- post block ------------------------------------------------------------------------------------------------
+struct wx_post {
+  std::unique_ptr<wx::PostBlock> impl;
+};
+#define WX_NEEDP(p) if (!(p) || !(p)->impl) throw wx::ConfigError("null post-block handle")
+int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx_post_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_post_create: null argument");
+    need_device(device, "wx_post_create");
+    std::unique_ptr<wx_post> p(new wx_post);
+    p->impl.reset(new wx::PostBlock(H, W, c_in, frames, c_out, device));
+    *out = p.release();
+  });
+}
+int wx_post_destroy(wx_post_handle p) { return guarded([&] { delete p; }); }
+int wx_post_set_band(wx_post_handle p, int row0, int rows) {
+  return guarded([&] { if (!p || !p->impl) throw wx::ConfigError("null post handle"); p->impl->set_band(row0, rows); });
+}
+int wx_post_set_grid_sigma(wx_post_handle p, const float* lat2d, const float* lon2d, const float* coef_a, const float* coef_b,
+                           int n_levels, int midpoint, int sp_ind) {
+  return guarded([&] {
+    WX_NEEDP(p);
+    if (!lat2d || !lon2d || !coef_a || !coef_b) throw wx::ConfigError("wx_post_set_grid_sigma: null argument");
+    p->impl->set_grid_sigma(lat2d, lon2d, coef_a, coef_b, n_levels, midpoint, sp_ind);
+  });
+}
+int wx_post_set_grid(wx_post_handle p, const float* lat2d, const float* lon2d, const float* p_levels, int n_levels, int midpoint) {
+  return guarded([&] { WX_NEEDP(p); if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument"); p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint); });
+}
+int wx_post_set_stats(wx_post_handle p, const float* mi, const float* si, const float* mo, const float* so) {
+  return guarded([&] { WX_NEEDP(p); if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument"); p->impl->set_stats(mi, si, mo, so); });
+}
+int wx_post_add_tracer_fixer(wx_post_handle p, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
+  return guarded([&] { WX_NEEDP(p); if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument"); p->impl->add_tracer(inds, thres, thres_max, n, denorm); });
+}
+int wx_post_add_mass_fixer(wx_post_handle p, int q_start, int fix_level_num, int denorm) {
+  return guarded([&] { WX_NEEDP(p); p->impl->add_mass(q_start, fix_level_num, denorm); });
+}
+int wx_post_add_water_fixer(wx_post_handle p, int q_start, int precip_ind, int evapor_ind, float n_seconds, int denorm) {
+  return guarded([&] { WX_NEEDP(p); p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
+}
+int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, int n_toa,
+                                    const int32_t* toa_inds, const float* toa_signs, int n_srf, const int32_t* srf_inds,
+                                    const float* srf_signs, const float* gph_surf, float n_seconds, int denorm) {
+  return guarded([&] {
+    WX_NEEDP(p);
+    if (!toa_inds || !toa_signs || !srf_inds || !srf_signs || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_signed: null argument");
+    p->impl->add_energy_signed(T_start, q_start, U_start, V_start, n_toa, toa_inds, toa_signs, n_srf, srf_inds, srf_signs, gph_surf,
+                               n_seconds, denorm);
+  });
+}
+int wx_post_add_energy_fixer_updown(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t flux_inds[9],
+                                    const float* gph_surf, float n_seconds, int denorm) {
+  return guarded([&] {
+    WX_NEEDP(p);
+    if (!flux_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_updown: null argument");
+    p->impl->add_energy_updown(T_start, q_start, U_start, V_start, flux_inds, gph_surf, n_seconds, denorm);
+  });
+}
+int wx_post_add_energy_fixer(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t rad_inds[6],
+                             const float* gph_surf, float n_seconds, int denorm) {
+  return guarded([&] { WX_NEEDP(p); if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument"); p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm); });
+}
+int wx_post_apply(wx_post_handle p, const float* x_dev, float* y_dev, void* stream) {
+  return guarded([&] { WX_NEEDP(p); if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer"); p->impl->apply(x_dev, y_dev, (hipStream_t)stream); });
+}
+int wx_attach_postblock(wx_handle h, wx_post_handle p) {
+  return guarded([&] { WX_NEED(h); h->impl->attach_post(p ? p->impl.get() : nullptr); });
+}
+
+// ---- standalone window attention (the Swin / FuXi mode of the attention kernel) -----------------------
+struct wx_winattn {
+  wx_winattn_desc d;
+  int device = 0;
+  int NP = 0;
+  float* bias_dev = nullptr;     // [n_bias_heads][NP][NP], padded keys -1e30, x log2(e) for bf16
+  float* logit_dev = nullptr;    // [heads] or nullptr
+  int64_t n_bias_stride = 0;     // floats between two heads' tables (0: one table shared by every head)
+  ~wx_winattn() {
+    if (bias_dev) (void)hipFree(bias_dev);
+    if (logit_dev) (void)hipFree(logit_dev);
+  }
+};
+int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bias_heads, const float* logit_scale_host, int device,
+                      wx_winattn_handle* out) {
+  return guarded([&] {
+    if (!d || !out) throw wx::ConfigError("null argument");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
+    const int wsx = d->wsz_x > 0 ? d->wsz_x : d->wsz_y;
+    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16) throw wx::ConfigError("winattn: unknown precision");
+    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 96 && d->head_dim != 128) throw wx::ConfigError("winattn: head_dim must be 32, 64, 96 or 128");
+    if (d->heads < 1 || d->C != d->heads * d->head_dim) throw wx::ConfigError("winattn: C must equal heads * head_dim");
+    if (d->wsz_y < 1 || wsx < 1 || d->H % d->wsz_y || d->W % wsx) throw wx::ConfigError("winattn: the window must divide the token map");
+    if (d->kind != 0 && d->kind != 1 && d->kind != 3) throw wx::ConfigError("winattn: kind must be 0 (block), 1 (dilated) or 3 (shifted block)");
+    if (d->kind == 1 && wsx != d->wsz_y) throw wx::ConfigError("winattn: dilated windows must be square");
+    if (d->kind == 3 && (d->shift_y < 0 || d->shift_y >= d->wsz_y || d->shift_x < 0 || d->shift_x >= wsx)) throw wx::ConfigError("winattn: shift must lie inside the window");
+    const int N = d->wsz_y * wsx;
+    const int nkf = wx::attn_nkf_tokens(N);
+    if (nkf < 0 || nkf > 8) throw wx::ConfigError("winattn: at most 128 tokens per window");
+    if (n_bias_heads != 0 && n_bias_heads != 1 && n_bias_heads != d->heads) throw wx::ConfigError("winattn: bias for 0, 1 or `heads` heads");
+    WX_HIP(hipSetDevice(device));
+    auto w = std::make_unique<wx_winattn>();
+    w->d = *d; w->device = device; w->NP = nkf * 16;
+    const int NP = w->NP, nb = n_bias_heads > 0 ? n_bias_heads : 1;
+    const float l2e = d->precision == WX_PREC_BF16 ? 1.4426950408889634f : 1.0f;   // bf16 softmax runs on exp2
+    std::vector<float> tab((size_t)nb * NP * NP, -1.0e30f);
+    for (int h = 0; h < nb; ++h)
+      for (int q = 0; q < NP; ++q)
+        for (int k = 0; k < N; ++k)
+          tab[((size_t)h * NP + q) * NP + k] = (q < N && bias_host && n_bias_heads > 0) ? bias_host[((size_t)h * N + q) * N + k] * l2e : 0.f;
+    WX_HIP(hipMalloc(&w->bias_dev, tab.size() * sizeof(float)));
+    WX_HIP(hipMemcpy(w->bias_dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    w->n_bias_stride = nb > 1 ? (int64_t)NP * NP : 0;
+    if (logit_scale_host) {
+      std::vector<float> ls(d->heads);
+      for (int h = 0; h < d->heads; ++h) ls[h] = logit_scale_host[h] * l2e;
+      WX_HIP(hipMalloc(&w->logit_dev, ls.size() * sizeof(float)));
+      WX_HIP(hipMemcpy(w->logit_dev, ls.data(), ls.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    *out = w.release();
+  });
+}
+int wx_winattn_destroy(wx_winattn_handle w) { return guarded([&] { delete w; }); }
+int wx_winattn_apply(wx_winattn_handle w, const void* qkv_dev, void* out_dev, void* stream) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null winattn handle");
+    if (!qkv_dev || !out_dev) throw wx::ConfigError("winattn: null tensor pointer");
+    WX_HIP(hipSetDevice(w->device));
+    const wx_winattn_desc& d = w->d;
+    wx::AttnParams p;
+    p.trace = nullptr; p.tb = nullptr; p.pack = 1;
+    p.qkv = qkv_dev; p.ld_qkv = 3 * (int64_t)d.C; p.out = out_dev; p.ld_out = d.C;
+    p.bias = w->bias_dev;
+    p.H = d.H; p.W = d.W; p.C = d.C; p.heads = d.heads; p.wsz = d.wsz_y; p.wsz_x = d.wsz_x > 0 ? d.wsz_x : d.wsz_y; p.kind = d.kind;
+    p.shift_y = d.kind == 3 ? d.shift_y : 0; p.shift_x = d.kind == 3 ? d.shift_x : 0;
+    const float l2e = d.precision == WX_PREC_BF16 ? 1.4426950408889634f : 1.0f;
+    p.mask_val = d.mask_value * l2e;
+    p.mask_x = (d.kind == 3 && (d.mask_axes & 2)) ? 1 : 0;
+    p.logit_scale = w->logit_dev;
+    // scores: cosine mode has its scale in q (logit_scale); otherwise softmax_scale (x log2 e on the exp2 path)
+    p.scale = w->logit_dev ? 1.0f : d.softmax_scale;                                             // fp32 path: scores * scale
+    p.q_scale = (!w->logit_dev && d.precision == WX_PREC_BF16) ? d.softmax_scale * l2e : 0.f;   // bf16 path: scale rides on q
+    p.bias_head_stride = w->n_bias_stride;
+    if (d.precision == WX_PREC_BF16) wx::launch_window_attn_any<wx::bf16_t>(p, d.head_dim, (hipStream_t)stream);
+    else wx::launch_window_attn_any<float>(p, d.head_dim, (hipStream_t)stream);
+  });
+}
+
+// ---- a stage of Swin V2 (Cr) blocks (BASELINE config 5: the FuXi U-Transformer's stage) -----------------
+struct wx_swin {
+  std::unique_ptr<wx::SwinStageBase> impl;
+};
+int wx_swin_create(const wx_swin_desc* d, int device, wx_swin_handle* out) {
+  return guarded([&] {
+    if (!d || !out) throw wx::ConfigError("null argument");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
+    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16 && d->precision != WX_PREC_FP32_SPLIT) throw wx::ConfigError("swin: unknown precision");
+    if (d->depth < 1 || d->H < 1 || d->W < 1 || d->heads < 1 || d->wsz_y < 1 || d->wsz_x < 1) throw wx::ConfigError("swin: bad geometry");
+    wx::SwinDesc sd{d->H, d->W, d->C, d->heads, d->wsz_y, d->wsz_x, d->depth, d->hidden, d->shift_y, d->shift_x, d->mask_value, d->ln_eps};
+    if (d->mask_axes != 0 && d->mask_axes != 1 && d->mask_axes != 3) throw wx::ConfigError("swin: mask_axes must be 1 (latitude) or 3 (both axes)");
+    sd.mask_axes = d->mask_axes == 3 ? 3 : 1;
+    const wx::Options opt = wx::Options::from_env();
+    auto w = std::make_unique<wx_swin>();
+    remap<wx::ConfigError>([&] {
+      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::SwinStage<wx::bf16_t>>(sd, device, opt);
+      else w->impl = std::make_unique<wx::SwinStage<float>>(sd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
+    });
+    *out = w.release();
+  });
+}
+int wx_swin_load(wx_swin_handle w, int block, const char* name, const float* host, int64_t count) {
+  return guarded([&] {
+    if (!w || !name || !host) throw wx::ConfigError("swin: null argument");
+    remap<wx::ShapeError>([&] { w->impl->load(block, name, host, count); });
+  });
+}
+int wx_swin_finalize(wx_swin_handle w) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null swin handle");
+    remap<wx::StateError>([&] { w->impl->finalize(); });
+  });
+}
+int wx_swin_apply(wx_swin_handle w, const void* x_in_dev, void* x_out_dev, void* stream) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null swin handle");
+    if (!x_in_dev || !x_out_dev) throw wx::ConfigError("swin: null tensor pointer");
+    remap<wx::StateError>([&] { w->impl->apply(x_in_dev, x_out_dev, (hipStream_t)stream); });
+  });
+}
+int wx_swin_flops(wx_swin_handle w, double* flops) {
+  return guarded([&] { if (!w || !flops) throw wx::ConfigError("swin: null argument"); *flops = w->impl->flops(); });
+}
+int wx_swin_destroy(wx_swin_handle w) { return guarded([&] { delete w; }); }
+
+// ---- the FuXi forward (BASELINE config 5; credit/models/fuxi.py:454-500) -----------------------------------------------------------
+struct wx_fuxi {
+  std::unique_ptr<wx::FuxiBase> impl;
+};
+int wx_fuxi_create(const wx_fuxi_desc* d, int device, wx_fuxi_handle* out) {
+  return guarded([&] {
+    if (!d || !out) throw wx::ConfigError("null argument");
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
+    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16 && d->precision != WX_PREC_FP32_SPLIT) throw wx::ConfigError("fuxi: unknown precision");
+    if (d->H < 1 || d->W < 1 || d->C_in < 1 || d->C_out < 1 || d->frames < 1 || d->patch_h < 1 || d->patch_w < 1 || d->dim < 1 || d->heads < 1 ||
+        d->window < 1 || d->depth < 1 || d->groups_down < 1 || d->groups_up < 1)
+      throw wx::ConfigError("fuxi: bad geometry");
+    if (d->stage_variant != WX_STAGE_V2_CR && d->stage_variant != WX_STAGE_TIMM_V2) throw wx::ConfigError("fuxi: unknown stage_variant");
+    wx::FuxiDesc fd{d->H, d->W, d->C_in, d->C_out, d->frames, d->patch_h, d->patch_w, d->dim, d->heads, d->window, d->depth, d->groups_down, d->groups_up};
+    fd.stage_variant = d->stage_variant;
+    const wx::Options opt = wx::Options::from_env();
+    auto w = std::make_unique<wx_fuxi>();
+    remap<wx::ConfigError>([&] {
+      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::FuxiModel<wx::bf16_t>>(fd, device, opt);
+      else w->impl = std::make_unique<wx::FuxiModel<float>>(fd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
+    });
+    *out = w.release();
+  });
+}
+int wx_fuxi_load(wx_fuxi_handle w, const char* name, const float* host, int64_t count) {
+  return guarded([&] {
+    if (!w || !name || !host) throw wx::ConfigError("fuxi: null argument");
+    remap<wx::ShapeError>([&] { w->impl->load(name, host, count); });
+  });
+}
+int wx_fuxi_finalize(wx_fuxi_handle w) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null fuxi handle");
+    remap<wx::StateError>([&] { w->impl->finalize(); });
+  });
+}
+int wx_fuxi_forward(wx_fuxi_handle w, const float* x_dev, float* y_dev, void* stream) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null fuxi handle");
+    if (!x_dev || !y_dev) throw wx::ConfigError("fuxi: null tensor pointer");
+    remap<wx::StateError>([&] { w->impl->forward(x_dev, y_dev, (hipStream_t)stream); });
+  });
+}
+int wx_fuxi_debug_map(wx_fuxi_handle w, const char* name, float* host, int64_t capacity, int64_t shape[3]) {
+  return guarded([&] {
+    if (!w || !name || !shape) throw wx::ConfigError("fuxi: null argument");
+    remap<wx::ShapeError>([&] { w->impl->debug_copy(name, host, capacity, shape); });
+  });
+}
+int wx_fuxi_flops(wx_fuxi_handle w, double* flops) {
+  return guarded([&] { if (!w || !flops) throw wx::ConfigError("fuxi: null argument"); *flops = w->impl->flops(); });
+}
+int wx_fuxi_destroy(wx_fuxi_handle w) { return guarded([&] { delete w; }); }
+
+const char* wx_last_error(void) { return wx::g_last_error.c_str(); }
+#ifndef WX_SOURCE_HASH
+#define WX_SOURCE_HASH "unhashed"
+#endif
+// "wxsrc:<hash of csrc/*.h, wx_engine.hip, include/wxengine.h>" is set by miles-credit_amd/build.py; the Python loader compares
+// it with the sources next to the library and refuses a stale build
+const char* wx_version(void) { return "wxengine 0.2 (gfx950) wxsrc:" WX_SOURCE_HASH; }
+
+}  // extern "C"

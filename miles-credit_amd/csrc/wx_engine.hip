@@ -1,9 +1,11 @@
 // wxengine: MI355X-native CrossFormer/WXFormer forecast step behind the C ABI of include/wxengine.h.
 //
-// Host side: owns the reference-layout state dict, folds it once (spectral norm sigma, LayerNorm
-// affine into the following 1x1 conv, DynamicPositionBias tables, MFMA-friendly K-contiguous weight
-// layout), owns every activation buffer in HBM (token-major H x W x C), and issues the kernels of
-// wx_gemm.h / wx_attn.h / wx_elem.h on the caller's HIP stream.
+// This file: Engine<T>, the object that runs a step -- it owns every activation buffer in HBM (token-major H x W x C) and issues
+// the kernels of wx_gemm.h / wx_attn.h / wx_elem.h on the caller's HIP stream.  The host side around it:
+//   wx_spec.h     what the model is: wx_config checks, derived geometry, the reference-layout state dict, the spectral-norm fold
+//   wx_weights.h  how the weights are laid out: the layer tables and the packer that folds the state dict into the two arenas
+//   wx_rccl.h     RCCL bound at run time for the lat-band transport
+//   wx_abi.h      the extern "C" wrappers of include/wxengine.h
 #include "../../include/wxengine.h"
 
 #include <algorithm>
@@ -37,88 +39,11 @@
 #include "wx_pre.h"
 #include "wx_noise.h"
 #include "wx_options.h"
+#include "wx_spec.h"
+#include "wx_rccl.h"
+#include "wx_weights.h"
 
 namespace wx {
-
-static thread_local std::string g_last_error;
-
-struct ConfigError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct StateError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct MissingError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct ShapeError : std::runtime_error { using std::runtime_error::runtime_error; };
-
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  bool loaded = false;
-  int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
-};
-
-struct ConvW {          // one repacked GEMM operand in the weight arena
-  int64_t wt = -1;      // element offset into the T arena
-  int n = 0, cin = 0, kh = 1, kw = 1;
-  int64_t bias = -1;    // float-arena offsets (-1 = absent)
-  int64_t colsum = -1;
-  int cin_true = 0;     // unpadded channels (flop accounting)
-  double flop_frac = 1.0;   // share of the dense n x kh x kw x cin products that are the model's (merged CrossEmbed: the rest multiply padded zeros)
-  int64_t wt_kb = -1;   // bf16 engine, 1x1 layers with n % 256 == 0: second copy, k-blocked [cin/32][n][32] (wx_gemm_stream.h)
-};
-struct AttnL { ConvW qkv, vonly, out; int64_t bias_tab = -1, bias_tb = -1; int wsz = 0, kind = 0; };
-struct FFL { ConvW w1, w2; int64_t pack = -1, pack_pre = -1, pack_pp = -1, pack_wide = -1; const AttnL* next = nullptr; };  // pack: fused-block chunk layout (wx_ff.h), T-arena offset; pack_pre: the same preceded by the attention's Wout blocks
-struct BlockL { AttnL sa; FFL sf; AttnL la; FFL lf; };
-struct PatchW { int64_t wt = -1, bias = -1, wt16 = -1; int n = 0; };   // LDS-patch CrossEmbed branch (wx_embed.h); wt16: split-bf16 mode, offset in the 16-bit patch arena
-struct StageL {
-  std::vector<ConvW> embed; std::vector<int> embed_k; std::vector<PatchW> patch; std::vector<BlockL> blocks;
-  bool ride4 = false;                            // stage 0: the k = 4 branch rides in the LDS-patch kernel's spare accumulator rows
-  int64_t patch_tab = -1, patch_bias64 = -1;     // float-arena offsets of EmbedPatchParams::slot_tab / bias64
-  ConvW merged;   // launch-bound maps: every CrossEmbed branch zero-padded into the largest kernel's window, one convolution of all output channels
-};
-struct UpL { ConvW convt, convps, sharp, upc, c1, c2; int64_t g1 = -1, b1 = -1, g2 = -1, b2 = -1; int cin = 0, cout = 0; };
-
-
-// RCCL bound at run time (no link dependency: single-GPU users never load it).  In a torch process the already-loaded
-// librccl is found first, so the engine and torch.distributed share one RCCL.
-struct RcclApi {
-  void* lib = nullptr;
-  decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-  decltype(&ncclCommInitRank) CommInitRank = nullptr;
-  decltype(&ncclCommDestroy) CommDestroy = nullptr;
-  decltype(&ncclSend) Send = nullptr;
-  decltype(&ncclRecv) Recv = nullptr;
-  decltype(&ncclGroupStart) GroupStart = nullptr;
-  decltype(&ncclGroupEnd) GroupEnd = nullptr;
-  decltype(&ncclGetErrorString) GetErrorString = nullptr;
-  static RcclApi& get() {
-    static RcclApi api;
-    if (api.lib) return api;
-    for (const char* name : {"librccl.so", "librccl.so.1"}) {
-      api.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL | RTLD_NOLOAD);
-      if (api.lib) break;
-    }
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so"}) {
-      if (api.lib) break;
-      api.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-    }
-    if (!api.lib) throw StateError(std::string("RCCL not found (librccl.so): ") + dlerror());
-    auto sym = [&](const char* n) {
-      void* p = dlsym(api.lib, n);
-      if (!p) throw StateError(std::string("RCCL symbol missing: ") + n);
-      return p;
-    };
-    api.GetUniqueId = reinterpret_cast<decltype(api.GetUniqueId)>(sym("ncclGetUniqueId"));
-    api.CommInitRank = reinterpret_cast<decltype(api.CommInitRank)>(sym("ncclCommInitRank"));
-    api.CommDestroy = reinterpret_cast<decltype(api.CommDestroy)>(sym("ncclCommDestroy"));
-    api.Send = reinterpret_cast<decltype(api.Send)>(sym("ncclSend"));
-    api.Recv = reinterpret_cast<decltype(api.Recv)>(sym("ncclRecv"));
-    api.GroupStart = reinterpret_cast<decltype(api.GroupStart)>(sym("ncclGroupStart"));
-    api.GroupEnd = reinterpret_cast<decltype(api.GroupEnd)>(sym("ncclGroupEnd"));
-    api.GetErrorString = reinterpret_cast<decltype(api.GetErrorString)>(sym("ncclGetErrorString"));
-    return api;
-  }
-  void check(ncclResult_t r, const char* what) const {
-    if (r != ncclSuccess) throw StateError(std::string("RCCL ") + what + ": " + GetErrorString(r));
-  }
-};
 
 struct KernelStatAcc { int64_t launches = 0; double ms = 0, flops = 0, bytes = 0; };
 
@@ -158,7 +83,7 @@ class EngineBase {
 };
 
 template <typename T>
-class Engine : public EngineBase {
+class Engine : public EngineBase, public ModelSpec, public LayerTables {
  public:
   // split_mma (T = float only; wx_config.precision WX_PREC_FP32_SPLIT): fp32 storage, LayerNorm / softmax statistics / GroupNorm as the
   // exact-f32 engine, but every implicit GEMM (wx_gemm.h SPLIT), the stage-0 CrossEmbed (the bf16 patch kernel over K-concatenated
@@ -167,13 +92,10 @@ class Engine : public EngineBase {
   // the reference's fp32 forward: ~1e-5 of max|y| (base weights), 5-7e-5 on the stress families -- inside the stated 1e-4 tolerance.
   bool split_mma = false;
   const Options opt;   // the run-time switches, read once by wx_create (wx_options.h)
-  Engine(const wx_config& c, int dev, const Options& o, bool split = false) : split_mma(split && sizeof(T) == 4), opt(o), cfg(c) {
+  Engine(const wx_config& c, int dev, const Options& o, bool split = false) : ModelSpec(c), split_mma(split && sizeof(T) == 4), opt(o) {
     device = dev;
-    derive();
-    build_spec();
   }
   ~Engine() override {
-    if (device < 0) return;   // host-only instance (wx_band_plan_create): nothing was allocated
     (void)hipSetDevice(device);
     if (b_comm) (void)RcclApi::get().CommDestroy(b_comm);
     if (b_cstream_own && b_cstream) (void)hipStreamDestroy(b_cstream);
@@ -185,823 +107,54 @@ class Engine : public EngineBase {
     for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   }
 
-  // ------------------------------------------------------------------ config
-  wx_config cfg;
-  int C_in = 0, C_out = 0, Hp = 0, Wp = 0, halo = 0, cpad0 = 0;
-  int sh[4], sw[4];           // stage maps
-  int Hd = 0, Wd = 0, Hu = 0, Wu = 0, Ho = 0, Wo = 0, ld_dec = 0;
+  // ------------------------------------------------------------------ state dict (wx_spec.h) and weights (wx_weights.h)
   bool finalized = false;
-
-  void derive() {
-    if (cfg.abi_version != WX_ABI_VERSION) throw ConfigError("wx_config.abi_version mismatch");
-    if (cfg.frames < 1 || cfg.output_frames < 1) throw ConfigError("frames/output_frames must be >= 1");
-    // dim_head (crossformer.py:372-401, a constructor kwarg; every YAML of the reference leaves the default 32): 32 runs the tuned kernels;
-    // 64 / 96 / 128 run the general-head-dimension attention kernel of the Swin mode (launch_window_attn_any) between the plain GEMMs --
-    // the attention block kernel and the fused FeedForward's to_out / to_qkv variants are built around 32-wide heads and stay off
-    if (cfg.dim_head != 32 && cfg.dim_head != 64 && cfg.dim_head != 96 && cfg.dim_head != 128)
-      throw ConfigError("dim_head must be 32, 64, 96 or 128");
-    for (int s = 0; s < 4; ++s)
-      if (cfg.dim[s] % cfg.dim_head) throw ConfigError("every stage width must be a multiple of dim_head");
-    if (cfg.dim_head != 32)   // launch_window_attn_dh: windows of at most 128 tokens
-      for (int s = 0; s < 4; ++s)
-        if (cfg.local_window_size[s] * cfg.local_window_size[s] > 128 || cfg.global_window_size[s] * cfg.global_window_size[s] > 128)
-          throw ConfigError("dim_head != 32 needs windows of at most 128 tokens (the general attention kernel's limit)");
-    if (cfg.arch != WX_ARCH_CROSSFORMER && cfg.arch != WX_ARCH_WXFORMER && cfg.arch != WX_ARCH_CROSSFORMER_UPCONV)
-      throw ConfigError("unknown wx_config.arch");
-    if (cfg.noise_latent_dim < 0 || cfg.noise_latent_dim > 4096) throw ConfigError("noise_latent_dim must be in 0 .. 4096");
-    if (cfg.noise_latent_dim > 0 && cfg.arch == WX_ARCH_WXFORMER)
-      throw ConfigError("noise layers belong to crossformer-ensemble (a legacy CrossFormer subclass): not with the wxformer decoder");
-    C_in = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.input_only_channels) * cfg.frames;
-    C_out = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.output_only_channels) * cfg.output_frames;
-    Hp = cfg.image_height + (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);
-    Wp = cfg.image_width + (cfg.pad_activate ? cfg.pad_lon[0] + cfg.pad_lon[1] : 0);
-    if (cfg.pad_activate && cfg.pad_lat[0] > 0 && cfg.pad_lat[1] == 0)
-      throw ConfigError("pad_lat=[p,0] hits a slicing quirk of the reference (boundary_padding.py:66); unsupported");
-    if (cfg.pad_activate && (cfg.pad_lat[0] > cfg.image_height || cfg.pad_lat[1] > cfg.image_height))
-      throw ConfigError("pad_lat larger than the image");
-    if (cfg.pad_activate == 2 && (cfg.pad_lat[0] >= cfg.image_height || cfg.pad_lat[1] >= cfg.image_height))
-      throw ConfigError("padding mode mirror: pad_lat must be smaller than the image height (reflection without the edge row)");
-    int h = Hp, w = Wp;
-    for (int s = 0; s < 4; ++s) {
-      const int st = cfg.embed_strides[s];
-      if (cfg.n_embed_kernels[s] < 1 || cfg.n_embed_kernels[s] > 4) throw ConfigError("1..4 cross-embed kernels per stage");
-      int oh = -1, ow = -1;
-      for (int b = 0; b < cfg.n_embed_kernels[s]; ++b) {
-        const int k = cfg.embed_kernels[s][b];
-        if (k < st) throw ConfigError("cross-embed kernel smaller than stride");
-        const int pd = (k - st) / 2;
-        // legacy: symmetric padding pd; wxformer: ZeroPad2d(lo = (k-s)/2, hi = (k-s) - lo) then an un-padded conv
-        const int pad_total = cfg.arch == WX_ARCH_WXFORMER ? (k - st) : 2 * pd;
-        const int h2 = (h + pad_total - k) / st + 1, w2 = (w + pad_total - k) / st + 1;
-        if (oh >= 0 && (h2 != oh || w2 != ow)) throw ConfigError("cross-embed branches disagree on output size");
-        oh = h2; ow = w2;
-        if (s == 0) halo = std::max(halo, pad_total - pd);
-      }
-      sh[s] = h = oh; sw[s] = w = ow;
-      if (cfg.dim[s] % 32) throw ConfigError("dim must be a multiple of 32");
-      for (int wsz : {cfg.local_window_size[s], cfg.global_window_size[s]}) {
-        if (wsz < 1 || h % wsz || w % wsz) throw ConfigError("stage map not divisible by window size");
-        if (attn_nkf(wsz) < 0) throw ConfigError("window size > 16 (more than 256 tokens) unsupported");
-      }
-    }
-    for (int s = 0; s < 3; ++s) {
-      if (sh[s] != 2 * sh[s + 1] || sw[s] != 2 * sw[s + 1]) throw ConfigError("stage maps must halve (decoder skip concat)");
-      if (cfg.dim[s + 1] != 2 * cfg.dim[s]) throw ConfigError("dim must double per stage (decoder skip widths)");
-    }
-    cpad0 = ((C_in + 31) / 32) * 32;
-    Hd = sh[3] * 16; Wd = sw[3] * 16;
-    Hu = Hd - (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);
-    Wu = Wd - (cfg.pad_activate ? cfg.pad_lon[0] + cfg.pad_lon[1] : 0);
-    if (Hu < 1 || Wu < 1) throw ConfigError("decoder output smaller than the padding");
-    Ho = cfg.interp ? cfg.image_height : Hu;
-    Wo = cfg.interp ? cfg.image_width : Wu;
-    ld_dec = ((C_out + 7) / 8) * 8;
-    if (cfg.max_batch < 1) cfg.max_batch = 1;
-  }
-
-  // ------------------------------------------------------------------ state dict
-  std::vector<std::string> keys;
-  std::map<std::string, HostTensor> tensors;
-
-  void add_key(const std::string& k, std::vector<int64_t> shape) {
-    keys.push_back(k);
-    HostTensor t;
-    t.shape = std::move(shape);
-    tensors[k] = std::move(t);
-  }
-  void add_conv(const std::string& p, std::vector<int64_t> shape, bool bias, bool transposed = false) {
-    const int64_t nb = transposed ? shape[1] : shape[0];
-    if (cfg.use_spectral_norm) {
-      if (bias) add_key(p + ".bias", {nb});
-      add_key(p + ".weight_orig", shape);
-      int64_t rest = 1;
-      if (transposed) {
-        rest = shape[0];
-        for (size_t i = 2; i < shape.size(); ++i) rest *= shape[i];
-        add_key(p + ".weight_u", {shape[1]});
-      } else {
-        for (size_t i = 1; i < shape.size(); ++i) rest *= shape[i];
-        add_key(p + ".weight_u", {shape[0]});
-      }
-      add_key(p + ".weight_v", {rest});
-    } else {
-      add_key(p + ".weight", shape);
-      if (bias) add_key(p + ".bias", {nb});
-    }
-  }
-  void build_spec() {
-    int dims[5] = {C_in, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
-    for (int s = 0; s < 4; ++s) {
-      const int cin = dims[s], cout = dims[s + 1];
-      std::vector<int> ks(cfg.embed_kernels[s], cfg.embed_kernels[s] + cfg.n_embed_kernels[s]);
-      std::sort(ks.begin(), ks.end());
-      std::vector<int> sc;
-      int acc = 0;
-      for (size_t i = 1; i < ks.size(); ++i) { sc.push_back((int)(cout / (1 << i))); acc += sc.back(); }
-      sc.push_back(cout - acc);
-      for (size_t b = 0; b < ks.size(); ++b)
-        add_conv(embed_key(s, (int)b), {sc[b], cin, ks[b], ks[b]}, true);
-      const int dq = cout / 4;
-      for (int d = 0; d < cfg.depth[s]; ++d) {
-        for (int j = 0; j < 4; ++j) {
-          const std::string p = "layers." + std::to_string(s) + ".1.layers." + std::to_string(d) + "." + std::to_string(j);
-          if (j == 0 || j == 2) {
-            add_key(p + ".norm.g", {1, cout, 1, 1});
-            add_key(p + ".norm.b", {1, cout, 1, 1});
-            add_conv(p + ".to_qkv", {3 * cout, cout, 1, 1}, false);
-            add_conv(p + ".to_out", {cout, cout, 1, 1}, true);
-            add_conv(p + ".dpb.layers.0", {dq, 2}, true);
-            add_key(p + ".dpb.layers.1.weight", {dq});
-            add_key(p + ".dpb.layers.1.bias", {dq});
-            add_conv(p + ".dpb.layers.3", {dq, dq}, true);
-            add_key(p + ".dpb.layers.4.weight", {dq});
-            add_key(p + ".dpb.layers.4.bias", {dq});
-            add_conv(p + ".dpb.layers.6", {dq, dq}, true);
-            add_key(p + ".dpb.layers.7.weight", {dq});
-            add_key(p + ".dpb.layers.7.bias", {dq});
-            add_conv(p + ".dpb.layers.9", {1, dq}, true);
-          } else {
-            add_key(p + ".layers.0.g", {1, cout, 1, 1});
-            add_key(p + ".layers.0.b", {1, cout, 1, 1});
-            add_conv(p + ".layers.1", {4 * cout, cout, 1, 1}, true);
-            add_conv(p + ".layers.4", {cout, 4 * cout, 1, 1}, true);
-          }
-        }
-      }
-    }
-    const int last = cfg.dim[3];
-    const int ups[3][2] = {{last, last / 2}, {2 * (last / 2), last / 4}, {2 * (last / 4), last / 8}};
-    for (int i = 0; i < 3; ++i) {
-      const std::string p = "up_block" + std::to_string(i + 1);
-      if (cfg.arch == WX_ARCH_WXFORMER) {  // UpBlockPS (wxformer/crossformer.py:137-162)
-        add_conv(p + ".conv", {4 * ups[i][1], ups[i][0], 3, 3}, true);
-        add_conv(p + ".sharp", {ups[i][1], ups[i][1], 3, 3}, true);
-      } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // nn.Upsample + Conv2d 3x3 (crossformer.py:87-89)
-        add_conv(p + ".conv", {ups[i][1], ups[i][0], 3, 3}, true);
-      } else {
-        add_conv(p + ".conv", {ups[i][0], ups[i][1], 2, 2}, true, true);
-      }
-      for (int j : {0, 3}) {
-        add_conv(p + ".b." + std::to_string(j), {ups[i][1], ups[i][1], 3, 3}, true);
-        add_key(p + ".b." + std::to_string(j + 1) + ".weight", {ups[i][1]});
-        add_key(p + ".b." + std::to_string(j + 1) + ".bias", {ups[i][1]});
-      }
-    }
-    if (cfg.arch == WX_ARCH_WXFORMER) {  // Sequential(conv3x3 -> PixelShuffle -> conv3x3) (wxformer/crossformer.py:817-830)
-      add_conv("up_block4.0", {4 * C_out, 2 * (last / 8), 3, 3}, true);
-      add_conv("up_block4.2", {C_out, C_out, 3, 3}, true);
-    } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // Sequential(Upsample, Conv2d) (crossformer.py:560-570)
-      add_conv("up_block4.1", {C_out, 2 * (last / 8), 3, 3}, true);
-    } else {
-      add_conv("up_block4", {2 * (last / 8), C_out, 4, 4}, true, true);
-    }
-    // CrossFormerWithNoise (crossformer_ensemble.py): created after apply_spectral_norm, so noise_transform keeps a plain `weight`
-    for (int l = 0; l < 6; ++l) {
-      if (!noise_slot_on(l)) continue;
-      const std::string p = noise_prefix(l);
-      const int c = noise_channels(l);
-      add_key(p + ".modulation", {1, c, 1, 1});
-      add_key(p + ".noise_factor", {1});
-      add_key(p + ".noise_transform.weight", {c, cfg.noise_latent_dim});
-      add_key(p + ".noise_transform.bias", {c});
-    }
-  }
-  // noise slots: 0 - 2 encoder_noise_layers.{0,1,2} (after stage k, width dim[k]); 3 - 5 noise_inject{1,2,3} (after up_block n, width dim[3 - n])
-  bool noise_slot_on(int l) const { return cfg.noise_latent_dim > 0 && (l >= 3 || cfg.encoder_noise); }
-  std::string noise_prefix(int l) const {
-    return l < 3 ? "encoder_noise_layers." + std::to_string(l) : "noise_inject" + std::to_string(l - 2);
-  }
-  int noise_channels(int l) const { return l < 3 ? cfg.dim[l] : cfg.dim[5 - l]; }
-  std::string embed_key(int s, int b) const {
-    return "layers." + std::to_string(s) + ".0.convs." + std::to_string(b) + (cfg.arch == WX_ARCH_WXFORMER ? ".1" : "");
-  }
-
   void load_tensor(const char* key, const float* data, int ndim, const int64_t* shape) override {
-    auto it = tensors.find(key);
-    if (it == tensors.end() && cfg.arch == WX_ARCH_WXFORMER) {
-      // pre-ZeroPad2d checkpoints keep CrossEmbed parameters at convs.<i>.<suffix>; the reference migrates them
-      // to convs.<i>.1.<suffix> on load (wxformer/crossformer.py:247-283) -- do the same
-      const std::string k(key);
-      const size_t pos = k.find(".0.convs.");
-      if (k.rfind("layers.", 0) == 0 && pos != std::string::npos) {
-        const size_t dot = k.find('.', pos + 9);
-        if (dot != std::string::npos && !(k.size() > dot + 2 && isdigit((unsigned char)k[dot + 1]) && k[dot + 2] == '.'))
-          it = tensors.find(k.substr(0, dot) + ".1" + k.substr(dot));
-      }
-    }
-    if (it == tensors.end()) {
-      // reference semantics: load_state_dict(strict=False) ignores unexpected keys (base_model.py:77-80)
-      return;
-    }
-    HostTensor& t = it->second;
-    int64_t n = 1;
-    for (int i = 0; i < ndim; ++i) n *= shape[i];
-    // torch semantics: the shapes must agree.  Only singleton dimensions may differ ((1, C, 1, 1) vs (C,)): the same
-    // element count in another layout ([128, 256, 2, 2] for a [256, 128, 2, 2] ConvTranspose weight) would load scrambled.
-    std::vector<int64_t> got, want;
-    for (int i = 0; i < ndim; ++i) if (shape[i] != 1) got.push_back(shape[i]);
-    for (int64_t d : t.shape) if (d != 1) want.push_back(d);
-    if (n != t.numel() || got != want) {
-      auto fmt = [](const int64_t* d, size_t k) { std::string r = "("; for (size_t i = 0; i < k; ++i) r += (i ? ", " : "") + std::to_string(d[i]); return r + ")"; };
-      throw ShapeError(std::string("size mismatch for ") + key + ": checkpoint " + fmt(shape, (size_t)ndim) + " vs model " +
-                       fmt(t.shape.data(), t.shape.size()));
-    }
-    t.data.assign(data, data + n);
-    t.loaded = true;
+    ModelSpec::load_tensor(key, data, ndim, shape);
     finalized = false;
   }
   int num_tensors() override { return (int)keys.size(); }
-  void tensor_info(int i, const char** key, int* ndim, int64_t shape[8]) override {
-    if (i < 0 || i >= (int)keys.size()) throw ConfigError("tensor index out of range");
-    const HostTensor& t = tensors[keys[i]];
-    *key = keys[i].c_str();
-    *ndim = (int)t.shape.size();
-    for (size_t d = 0; d < t.shape.size() && d < 8; ++d) shape[d] = t.shape[d];
-  }
-  const HostTensor& need(const std::string& k) {
-    auto it = tensors.find(k);
-    if (it == tensors.end() || !it->second.loaded) throw MissingError("state-dict tensor '" + k + "' was not loaded");
-    return it->second;
-  }
-
-  // ------------------------------------------------------------------ weight folding (host)
-  std::vector<T> wt_host;      // T arena
-  std::vector<float> f_host;   // float arena
+  void tensor_info(int i, const char** key, int* ndim, int64_t shape[8]) override { ModelSpec::tensor_info(i, key, ndim, shape); }
   T* wt_dev = nullptr;
   float* f_dev = nullptr;
-  StageL stages[4];
-  UpL ups[3];
-  ConvW up4[4];
-  struct NoiseL { int64_t w = -1, b = -1, mod = -1, nf = -1; };
-  NoiseL nz[6];       // float-arena offsets of the six noise layers (slots as noise_slot_on)
   NoiseState* d_noise = nullptr;   // seed / member0 / step (device: advanced inside captured graphs)
   float* d_style = nullptr;        // [6][dim[3]] styles of the batch row being computed
   std::vector<const float*> noise_tape;   // wx_set_noise_tape: device pointers in the reference's draw order (empty: generator)
   int cur_row = 0;                 // batch row of the forward item being computed
-  ConvW ps4, fin4;   // wxformer head: sub-pixel conv (shuffled rows) and the final 3x3 conv
-  int cpad4 = 0;
   T* ps4_buf = nullptr;
-
-  // eval-mode spectral norm: W / (u . (W_mat v)); W_mat rows = dim 0 (dim 1 for ConvTranspose2d)
-  std::vector<double> folded(const std::string& p, bool transposed) {
-    if (!cfg.use_spectral_norm) {
-      const HostTensor& w = need(p + ".weight");
-      return std::vector<double>(w.data.begin(), w.data.end());
-    }
-    const HostTensor& w = need(p + ".weight_orig");
-    const HostTensor& u = need(p + ".weight_u");
-    const HostTensor& v = need(p + ".weight_v");
-    const int64_t d0 = w.shape[0], d1 = w.shape.size() > 1 ? w.shape[1] : 1;
-    int64_t rest = 1;
-    for (size_t i = 2; i < w.shape.size(); ++i) rest *= w.shape[i];
-    double sigma = 0.0;
-    if (!transposed) {
-      const int64_t cols = d1 * rest;
-      for (int64_t r = 0; r < d0; ++r) {
-        double acc = 0.0;
-        const float* row = w.data.data() + r * cols;
-        for (int64_t c = 0; c < cols; ++c) acc += (double)row[c] * v.data[c];
-        sigma += acc * u.data[r];
-      }
-    } else {
-      // W_mat[o][i*rest + k] = W[i][o][k]
-      for (int64_t o = 0; o < d1; ++o) {
-        double acc = 0.0;
-        for (int64_t i = 0; i < d0; ++i)
-          for (int64_t k = 0; k < rest; ++k) acc += (double)w.data[(i * d1 + o) * rest + k] * v.data[i * rest + k];
-        sigma += acc * u.data[o];
-      }
-    }
-    std::vector<double> out(w.data.size());
-    for (size_t i = 0; i < out.size(); ++i) out[i] = (double)w.data[i] / sigma;
-    return out;
-  }
-  int64_t push_f(const std::vector<float>& v) {
-    // keep every float-arena block 16-byte aligned
-    while (f_host.size() % 4) f_host.push_back(0.f);
-    const int64_t off = (int64_t)f_host.size();
-    f_host.insert(f_host.end(), v.begin(), v.end());
-    // pad every block to a multiple of 128 floats: GEMM epilogues read bias/colsum as whole float4 vectors
-    // for a full 128-channel tile even when the layer has fewer channels
-    while ((f_host.size() - off) % 128) f_host.push_back(0.f);
-    return off;
-  }
-  int64_t push_w(const std::vector<double>& rows, int n, int64_t k) {
-    // 16-byte blocks; split-bf16 arithmetic: whole 32-float K chunks (the split arena re-encodes the arena chunk by chunk)
-    while (wt_host.size() % (split_mma ? 32 : 8)) wt_host.push_back(Elem<T>::from_f(0.f));
-    const int64_t off = (int64_t)wt_host.size();
-    wt_host.resize(off + (int64_t)n * k);
-    for (int64_t i = 0; i < (int64_t)n * k; ++i) wt_host[off + i] = Elem<T>::from_f((float)rows[i]);
-    return off;
-  }
-  // k-blocked copy of a 1x1 layer's ROUNDED arena weights for the persistent GEMM (same values, other order): a K = 32 stage of
-  // 256 output channels is then 16 contiguous KB (full cache lines per LDS-DMA piece instead of half-used ones)
-  void pack_kblocked(ConvW& cw) {
-    if constexpr (sizeof(T) != 2) return;
-    if (!opt.use_stream || cw.kh != 1 || cw.kw != 1 || cw.n % 128 != 0 || cw.cin % 32 != 0 || cw.cin < 512) return;
-    while (wt_host.size() % 8) wt_host.push_back(Elem<T>::from_f(0.f));
-    const int64_t off = (int64_t)wt_host.size();
-    wt_host.resize(off + (int64_t)cw.n * cw.cin);
-    for (int n = 0; n < cw.n; ++n)
-      for (int k = 0; k < cw.cin; ++k)
-        wt_host[off + ((int64_t)(k / 32) * cw.n + n) * 32 + k % 32] = wt_host[cw.wt + (int64_t)n * cw.cin + k];
-    cw.wt_kb = off;
-  }
-  // Conv2d weight W[n][c][kh][kw] (rows [r0, r1)) -> [n][kh][kw][cpad]; optional LayerNorm fold (g, b per input channel)
-  // row_src (optional): output row o takes reference row row_src[o] (-1 = all-zero row) instead of r0 + o
-  // lead_rows / lead_scale: output rows [0, lead_rows) (weights and bias) are multiplied by lead_scale before rounding -- the
-  // attention's 1/sqrt(d) (x log2 e) folded into the q rows of to_qkv, so the score MFMA needs no scaling afterwards
-  ConvW make_conv(const std::string& p, int r0, int r1, int cin, int cpad, int kh, int kw, bool has_bias,
-                  const float* ln_g, const float* ln_b, const std::vector<int>* row_src = nullptr, int lead_rows = 0,
-                  double lead_scale = 1.0) {
-    const std::vector<double> w = folded(p, false);
-    const int n = row_src ? (int)row_src->size() : r1 - r0;
-    const int64_t k = (int64_t)kh * kw * cpad;
-    std::vector<double> rows((size_t)n * k, 0.0);
-    std::vector<float> bias(n, 0.f), colsum;
-    const HostTensor* bt = has_bias ? &need(p + ".bias") : nullptr;
-    for (int o = 0; o < n; ++o) {
-      double tshift = 0.0;
-      const int ro = row_src ? (*row_src)[o] : r0 + o;
-      if (ro < 0) continue;  // zero row (channel padding)
-      for (int c = 0; c < cin; ++c)
-        for (int y = 0; y < kh; ++y)
-          for (int x = 0; x < kw; ++x) {
-            double v = w[(((int64_t)ro * cin + c) * kh + y) * kw + x] * (o < lead_rows ? lead_scale : 1.0);
-            if (ln_b) tshift += v * ln_b[c];
-            if (ln_g) v *= ln_g[c];
-            rows[(size_t)o * k + ((int64_t)y * kw + x) * cpad + c] = v;
-          }
-      bias[o] = (float)(tshift + (bt ? (double)bt->data[ro] * (o < lead_rows ? lead_scale : 1.0) : 0.0));
-    }
-    ConvW cw;
-    cw.n = n; cw.cin = cpad; cw.cin_true = cin; cw.kh = kh; cw.kw = kw;
-    cw.wt = push_w(rows, n, k);
-    if (ln_g) {  // colsum over the ROUNDED weights so that acc - mean*colsum == sum((x-mean)*w) exactly
-      colsum.resize(n);
-      for (int o = 0; o < n; ++o) {
-        double s = 0.0;
-        for (int64_t i = 0; i < k; ++i) s += (double)Elem<T>::to_f(wt_host[cw.wt + (int64_t)o * k + i]);
-        colsum[o] = (float)s;
-      }
-      cw.colsum = push_f(colsum);
-    }
-    if (has_bias || ln_b) cw.bias = push_f(bias);
-    return cw;
-  }
-  // All branches of one CrossEmbed (crossformer.py:128-152: kernel k, stride s, padding (k - s) / 2 -- every branch is centred on the same
-  // window) as ONE convolution with the largest kernel: branch b's taps sit at offset (kmax - k_b) / 2 inside it, zeros around them
-  // (exact: the added products are 0 * x).  Output channels in the reference's concatenation order.
-  ConvW make_embed_merged(int s, const std::vector<int>& ks, const std::vector<int>& cos, int cin, int cpad) {
-    const int kmax = ks.back();
-    int n = 0;
-    for (int co : cos) n += co;
-    const int64_t k = (int64_t)kmax * kmax * cpad;
-    std::vector<double> rows((size_t)n * k, 0.0);
-    std::vector<float> bias(n, 0.f);
-    int o0 = 0;
-    for (size_t b = 0; b < ks.size(); ++b) {
-      const std::string bp = embed_key(s, (int)b);
-      const std::vector<double> w = folded(bp, false);
-      const HostTensor& bt = need(bp + ".bias");
-      const int kb = ks[b], d = (kmax - kb) / 2;
-      for (int o = 0; o < cos[b]; ++o) {
-        for (int c = 0; c < cin; ++c)
-          for (int y = 0; y < kb; ++y)
-            for (int x = 0; x < kb; ++x)
-              rows[(size_t)(o0 + o) * k + ((int64_t)(y + d) * kmax + (x + d)) * cpad + c] = w[(((int64_t)o * cin + c) * kb + y) * kb + x];
-        bias[o0 + o] = bt.data[o];
-      }
-      o0 += cos[b];
-    }
-    ConvW cw;
-    cw.n = n; cw.cin = cpad; cw.cin_true = cin; cw.kh = kmax; cw.kw = kmax;
-    double real = 0.0;
-    for (size_t b = 0; b < ks.size(); ++b) real += (double)cos[b] * ks[b] * ks[b];
-    cw.flop_frac = real / ((double)n * kmax * kmax);
-    cw.wt = push_w(rows, n, k);
-    cw.bias = push_f(bias);
-    return cw;
-  }
-  // Stage-0 branch for embed_patch_kernel: [chunk][ky][kx/4][n-frag][tap g][out 16][CC channels]
-  // `extra`: channels [x0, x0 + xn) of the smaller kernel `xkey` (size xk) as accumulator rows n .. n + xn - 1, their taps zero-padded
-  // into the middle of this k x k window (same centre: crossformer.py:128-152 padding (k - stride) / 2) -- see EmbedPatchParams::slot_tab
-  PatchW make_patch(const std::string& p, int n, int cin, int cpad, int k, const std::string& xkey = "", int xk = 0, int x0 = 0, int xn = 0) {
-    PatchW pw;
-    pw.n = n;
-    if (split_mma) {
-      // split-bf16 mode: the bf16 instantiation of the patch kernel over the K-concatenated operand pair -- weights [W_hi | W_hi | W_lo]
-      // against planes [x_hi | x_lo | x_hi] (pack_input): 3 x cpad / 8 chunks of the bf16 layout, in their own 16-bit arena
-      const std::vector<double> r8 = patch_rows(p, n, cin, cpad, k, 8, xkey, xk, x0, xn);
-      while (sp16_host.size() % 8) sp16_host.push_back(0);
-      pw.wt16 = (int64_t)sp16_host.size();
-      sp16_host.resize(sp16_host.size() + 3 * r8.size());
-      uint16_t* d = sp16_host.data() + pw.wt16;
-      for (size_t i = 0; i < r8.size(); ++i) {
-        const float w = (float)r8[i];
-        const bf16_t hi = f2bf(w), lo = f2bf(w - bf2f(hi));
-        d[i] = hi; d[r8.size() + i] = hi; d[2 * r8.size() + i] = lo;
-      }
-    }
-    const std::vector<double> rows = patch_rows(p, n, cin, cpad, k, 16 / (int)sizeof(T), xkey, xk, x0, xn);
-    pw.wt = push_w(rows, 1, (int64_t)rows.size());
-    return pw;
-  }
-  std::vector<uint16_t> sp16_host;   // split_mma: bf16 patch weights (make_patch)
   uint16_t* sp16_dev = nullptr;
-  std::vector<double> patch_rows(const std::string& p, int n, int cin, int cpad, int k, int CC, const std::string& xkey, int xk, int x0, int xn) {
-    const std::vector<double> w = folded(p, false);
-    const int chunks = cpad / CC, k4n = k / 4, nfr = (k == 8) ? 2 : 1;  // fragment counts the kernel is built for
-    std::vector<double> rows((size_t)chunks * k * k4n * nfr * 64 * CC, 0.0);
-    auto at = [&](int ch, int ky, int kx, int o, int e) -> double& {
-      return rows[(((((size_t)ch * k + ky) * k4n + kx / 4) * nfr + o / 16) * 64 + (kx % 4) * 16 + (o % 16)) * CC + e];
-    };
-    for (int ch = 0; ch < chunks; ++ch)
-      for (int ky = 0; ky < k; ++ky)
-        for (int kx = 0; kx < k; ++kx)
-          for (int o = 0; o < n; ++o)
-            for (int e = 0; e < CC; ++e) {
-              const int c = ch * CC + e;
-              if (c < cin) at(ch, ky, kx, o, e) = w[(((int64_t)o * cin + c) * k + ky) * k + kx];
-            }
-    if (xn > 0) {
-      const std::vector<double> wx = folded(xkey, false);
-      const int d = (k - xk) / 2;
-      for (int ch = 0; ch < chunks; ++ch)
-        for (int ky = 0; ky < xk; ++ky)
-          for (int kx = 0; kx < xk; ++kx)
-            for (int o = 0; o < xn; ++o)
-              for (int e = 0; e < CC; ++e) {
-                const int c = ch * CC + e;
-                if (c < cin) at(ch, ky + d, kx + d, n + o, e) = wx[(((int64_t)(x0 + o) * cin + c) * xk + ky) * xk + kx];
-              }
-    }
-    return rows;
-  }
-  // ConvTranspose2d k2 s2: W[ci][co][dy][dx] -> rows n = (dy*2+dx)*cout + co, K = ci; bias expanded x4
-  ConvW make_convt2(const std::string& p, int cin, int cout) {
-    const std::vector<double> w = folded(p, true);
-    std::vector<double> rows((size_t)4 * cout * cin);
-    for (int ci = 0; ci < cin; ++ci)
-      for (int co = 0; co < cout; ++co)
-        for (int q = 0; q < 4; ++q) rows[((size_t)q * cout + co) * cin + ci] = w[((int64_t)ci * cout + co) * 4 + q];
-    const HostTensor& b = need(p + ".bias");
-    std::vector<float> bias(4 * cout);
-    for (int q = 0; q < 4; ++q)
-      for (int co = 0; co < cout; ++co) bias[q * cout + co] = b.data[co];
-    ConvW cw;
-    cw.n = 4 * cout; cw.cin = cin; cw.cin_true = cin;
-    cw.wt = push_w(rows, 4 * cout, cin);
-    cw.bias = push_f(bias);
-    return cw;
-  }
-  // ConvTranspose2d k4 s2 p1 as four 2x2-tap parity convs: out(2y+py, 2x+px) = sum_{ty,tx} in(y-1+py+ty, x-1+px+tx) W[ci][co][3-py-2ty][3-px-2tx]
-  void make_convt4(const std::string& p, int cin, int cout) {
-    const std::vector<double> w = folded(p, true);
-    const HostTensor& b = need(p + ".bias");
-    for (int py = 0; py < 2; ++py)
-      for (int px = 0; px < 2; ++px) {
-        std::vector<double> rows((size_t)cout * 4 * cin);
-        for (int co = 0; co < cout; ++co)
-          for (int ty = 0; ty < 2; ++ty)
-            for (int tx = 0; tx < 2; ++tx)
-              for (int ci = 0; ci < cin; ++ci)
-                rows[((size_t)co * 4 + ty * 2 + tx) * cin + ci] =
-                    w[(((int64_t)ci * cout + co) * 4 + (3 - py - 2 * ty)) * 4 + (3 - px - 2 * tx)];
-        ConvW cw;
-        cw.n = cout; cw.cin = cin; cw.cin_true = cin; cw.kh = 2; cw.kw = 2;
-        cw.wt = push_w(rows, cout, (int64_t)4 * cin);
-        cw.bias = push_f(std::vector<float>(b.data.begin(), b.data.end()));
-        up4[py * 2 + px] = cw;
-      }
-  }
-  // DynamicPositionBias (crossformer.py:158-176) evaluated on the (2w+1)^2 offsets, gathered with the
-  // reference's stride-(2w-1) indices (crossformer.py:238-245, :284), padded to [NP][NP].
-  int64_t make_bias_table(const std::string& p, int wsz, int dq, int64_t* tb_off = nullptr) {
-    const int side = 2 * wsz + 1, npos = side * side;
-    std::vector<double> w0 = folded(p + ".layers.0", false), w3 = folded(p + ".layers.3", false),
-                        w6 = folded(p + ".layers.6", false), w9 = folded(p + ".layers.9", false);
-    const HostTensor &b0 = need(p + ".layers.0.bias"), &b3 = need(p + ".layers.3.bias"), &b6 = need(p + ".layers.6.bias"),
-                     &b9 = need(p + ".layers.9.bias");
-    const HostTensor* lnw[3] = {&need(p + ".layers.1.weight"), &need(p + ".layers.4.weight"), &need(p + ".layers.7.weight")};
-    const HostTensor* lnb[3] = {&need(p + ".layers.1.bias"), &need(p + ".layers.4.bias"), &need(p + ".layers.7.bias")};
-    std::vector<double> table(npos);
-    std::vector<double> h(dq), h2(dq);
-    auto ln_relu = [&](std::vector<double>& v, int i) {
-      double m = 0, q = 0;
-      for (double x : v) m += x;
-      m /= dq;
-      for (double x : v) q += (x - m) * (x - m);
-      q /= dq;
-      const double r = 1.0 / std::sqrt(q + 1e-5);
-      for (int k = 0; k < dq; ++k) {
-        const double y = (v[k] - m) * r * lnw[i]->data[k] + lnb[i]->data[k];
-        v[k] = y > 0 ? y : 0;
-      }
-    };
-    for (int a = 0; a < side; ++a)
-      for (int b = 0; b < side; ++b) {
-        const double pr = a - wsz, pc = b - wsz;
-        for (int k = 0; k < dq; ++k) h[k] = w0[2 * k] * pr + w0[2 * k + 1] * pc + b0.data[k];
-        ln_relu(h, 0);
-        for (int k = 0; k < dq; ++k) { double s = b3.data[k]; for (int j = 0; j < dq; ++j) s += w3[(size_t)k * dq + j] * h[j]; h2[k] = s; }
-        ln_relu(h2, 1);
-        for (int k = 0; k < dq; ++k) { double s = b6.data[k]; for (int j = 0; j < dq; ++j) s += w6[(size_t)k * dq + j] * h2[j]; h[k] = s; }
-        ln_relu(h, 2);
-        double s = b9.data[0];
-        for (int j = 0; j < dq; ++j) s += w9[j] * h[j];
-        table[a * side + b] = s;
-      }
-    // [NP][NP] table the kernel adds to the scores: padded keys (and, for packed tiles, keys of another window) get
-    // -1e30; the bf16 engine exponentiates with v_exp_f32 (2^x), so its table carries the log2(e) factor
-    const int N1 = wsz * wsz, G = attn_pack(wsz), N = N1 * G, NP = attn_nkf(wsz) * 16;
-    const double pre = sizeof(T) == 2 ? 1.4426950408889634 : 1.0;
-    std::vector<float> padded((size_t)NP * NP, 0.f);
-    for (int i = 0; i < NP; ++i)
-      for (int j = 0; j < NP; ++j) {
-        float v;
-        if (j >= N) v = -1.0e30f;
-        else if (i >= N) v = 0.f;
-        else if (i / N1 != j / N1) v = -1.0e30f;
-        else {
-          const int il = i % N1, jl = j % N1;
-          const int dr = il / wsz - jl / wsz + wsz - 1, dc = il % wsz - jl % wsz + wsz - 1;
-          v = (float)(pre * table[dr * (2 * wsz - 1) + dc]);
-        }
-        padded[(size_t)i * NP + j] = v;
-      }
-    if (tb_off) {  // the generating table itself (flat, first (2w-1)^2 entries are the ones the reference's indices reach)
-      std::vector<float> tb((size_t)(2 * wsz - 1) * (2 * wsz - 1));
-      for (size_t i = 0; i < tb.size(); ++i) tb[i] = (float)(pre * table[i]);
-      *tb_off = push_f(tb);
-    }
-    return push_f(padded);
-  }
-  AttnL make_attn(const std::string& p, int c, int wsz, int kind) {
-    AttnL a;
-    a.wsz = wsz; a.kind = kind;
-    const HostTensor &g = need(p + ".norm.g"), &b = need(p + ".norm.b");
-    if (wsz == 1) {
-      // one token per window: softmax == 1, attention output == v (crossformer.py:286-295) -> only the v rows
-      a.vonly = make_conv(p + ".to_qkv", 2 * c, 3 * c, c, c, 1, 1, false, g.data.data(), b.data.data());
-      pack_kblocked(a.vonly);
-    } else {
-      // bf16 engine: softmax scale (and the log2 e of its exp2) lives in the q rows; the fp32 engine multiplies the scores instead
-      a.qkv = make_conv(p + ".to_qkv", 0, 3 * c, c, c, 1, 1, false, g.data.data(), b.data.data(), nullptr,
-                        sizeof(T) == 2 ? c : 0, 1.4426950408889634 / std::sqrt((double)cfg.dim_head));
-      pack_kblocked(a.qkv);
-      a.bias_tab = make_bias_table(p + ".dpb", wsz, c / 4, &a.bias_tb);
-    }
-    a.out = make_conv(p + ".to_out", 0, c, c, c, 1, 1, true, nullptr, nullptr);
-    pack_kblocked(a.out);
-    return a;
-  }
-  // chunk blocks for ff_fused_kernel, built from the ROUNDED arena weights of w1 / w2 (same values as the unfused path)
-  int64_t pack_ff(const FFL& f, int c, int hidden, const ConvW* wout = nullptr, const ConvW* wqkv = nullptr) {
-    while (wt_host.size() % 8) wt_host.push_back(Elem<T>::from_f(0.f));
-    const int64_t off = (int64_t)wt_host.size();
-    const int nch = hidden / 32, npre = wout ? c / 64 : 0, npost = wqkv ? 3 * c / 64 : 0;
-    const int64_t cb = 64 * (int64_t)c;  // elements per chunk block (128*C bytes of bf16)
-    wt_host.resize(off + (npre + nch + npost) * cb);
-    for (int i = 0; i < npost; ++i)      // Wqkv' rows [64 i, 64 i + 64), k order permuted like W1 (the input sits in accumulator layout)
-      for (int r = 0; r < 64; ++r)
-        for (int sl = 0; sl < c / 8; ++sl)
-          for (int j = 0; j < 8; ++j)
-            wt_host[off + (npre + nch + i) * cb + (int64_t)r * c + (sl ^ (r & 15)) * 8 + j] =
-                wt_host[wqkv->wt + (int64_t)(i * 64 + r) * c + 32 * (sl / 4) + ff_perm(sl % 4, j)];
-    for (int i = 0; i < npre; ++i)       // Wout rows [64 i, 64 i + 64), natural k order, 16-byte slots XOR-swizzled by row
-      for (int r = 0; r < 64; ++r)
-        for (int sl = 0; sl < c / 8; ++sl)
-          for (int j = 0; j < 8; ++j)
-            wt_host[off + i * cb + (int64_t)r * c + (sl ^ (r & 15)) * 8 + j] = wt_host[wout->wt + (int64_t)(i * 64 + r) * c + sl * 8 + j];
-    for (int ch = 0; ch < nch; ++ch) {
-      const int64_t base = off + (npre + ch) * cb;
-      for (int r = 0; r < 32; ++r)
-        for (int sl = 0; sl < c / 8; ++sl) {
-          const int ks = sl / 4, g = sl % 4, phys = sl ^ (r & (c / 8 < 16 ? c / 8 - 1 : 15));   // (C = 64: 8 slots per row)
-          for (int j = 0; j < 8; ++j)
-            wt_host[base + (int64_t)r * c + phys * 8 + j] = wt_host[f.w1.wt + (int64_t)(ch * 32 + r) * c + 32 * ks + ff_perm(g, j)];
-        }
-      for (int o = 0; o < c; ++o)
-        for (int g = 0; g < 4; ++g)
-          for (int j = 0; j < 8; ++j)
-          {
-            const T wv = wt_host[f.w2.wt + (int64_t)o * hidden + ch * 32 + ff_perm(g, j)];
-            // WX_FF_F16: the kernel's GEMM2 runs on f16 operands (hidden activations in f16): the SAME rounded bf16 weight, re-encoded
-            // (exact: 8 significand bits into 11; only magnitudes below 6e-8 are lost)
-            T enc = wv;
-            if constexpr (sizeof(T) == 2) { if (WX_FF_F16) enc = (T)f2h_bits(Elem<T>::to_f(wv)); }
-            wt_host[base + 32 * (int64_t)c + (int64_t)o * 32 + ff_w2_slot(o, g) * 8 + j] = enc;
-          }
-    }
-    return off;
-  }
-  FFL make_ff(const std::string& p, int c, const AttnL* prev = nullptr) {
-    FFL f;
-    const HostTensor &g = need(p + ".layers.0.g"), &b = need(p + ".layers.0.b");
-    f.w1 = make_conv(p + ".layers.1", 0, 4 * c, c, c, 1, 1, true, g.data.data(), b.data.data());
-    pack_kblocked(f.w1);
-    f.w2 = make_conv(p + ".layers.4", 0, c, 4 * c, 4 * c, 1, 1, true, nullptr, nullptr);
-    pack_kblocked(f.w2);
-    if constexpr (sizeof(T) == 2) {
-      if (ff_fused_supported(c, 4 * c)) {
-        f.pack = pack_ff(f, c, 4 * c);
-        if (prev) f.pack_pre = pack_ff(f, c, 4 * c, &prev->out);
-      } else if (ff_plain_supported(c, 4 * c)) {
-        f.pack = pack_ff(f, c, 4 * c);
-      } else if (opt.ff_wide && ff_wide_supported(c, 4 * c)) {
-        f.pack_wide = pack_ff(f, c, 4 * c);   // its own field: every rule that reads `pack` (two-stream stages, row windows) stays as it was
-      }
-    }
-    return f;
-  }
 
   void finalize() override {
     WX_HIP(hipSetDevice(device));
     for (const auto& k : keys) need(k);
-    wt_host.clear(); f_host.clear();
-    int dims[5] = {C_in, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
-    for (int s = 0; s < 4; ++s) {
-      StageL st;
-      std::vector<int> ks(cfg.embed_kernels[s], cfg.embed_kernels[s] + cfg.n_embed_kernels[s]);
-      std::sort(ks.begin(), ks.end());
-      const int cin = dims[s], cout = dims[s + 1];
-      const int cpad = s == 0 ? cpad0 : cin;
-      int acc = 0;
-      std::vector<int> cos;
-      for (size_t b = 0; b < ks.size(); ++b) {
-        const int co = (b + 1 < ks.size()) ? (int)(cout / (1 << (b + 1))) : cout - acc;
-        acc += co;
-        cos.push_back(co);
-      }
-      // stage 0 on the LDS-patch kernel (wx_embed.h): branches k = 32 / 16 / 8 in its accumulator row [16 | 16 | 32]; the k = 4 branch
-      // rides in the rows they leave empty when it fits (1-degree model: 8 + 8 + 16 spare rows = its 32 channels)
-      std::vector<bool> pok(ks.size(), false);
-      int cap[3] = {16, 16, 32}, used[3] = {0, 0, 0}, bidx[3] = {-1, -1, -1}, b4 = -1;
-      for (size_t b = 0; b < ks.size(); ++b) {
-        pok[b] = s == 0 && cfg.embed_strides[0] == 2 && cos[b] % 4 == 0 && ks.back() == 32 &&
-                 ((ks[b] == 32 && cos[b] <= 16) || (ks[b] == 16 && cos[b] <= 16) || (ks[b] == 8 && cos[b] <= 32));
-        if (pok[b]) { const int j = ks[b] == 32 ? 0 : ks[b] == 16 ? 1 : 2; used[j] = cos[b]; bidx[j] = (int)b; }
-        if (ks[b] == 4) b4 = (int)b;
-      }
-      int ride[3] = {0, 0, 0}, ride0[3] = {0, 0, 0};   // k = 4 channels [ride0, ride0 + ride) in the spare rows of branch j
-      if (s == 0 && opt.embed_ride4 && b4 >= 0 && cos[b4] % 4 == 0 && bidx[0] >= 0 && bidx[1] >= 0 && bidx[2] >= 0 &&
-          (cap[0] - used[0]) + (cap[1] - used[1]) + (cap[2] - used[2]) >= cos[b4]) {
-        int left = cos[b4], at4 = 0;
-        for (int j = 0; j < 3; ++j) {
-          ride[j] = std::min(left, cap[j] - used[j]); ride0[j] = at4;
-          at4 += ride[j]; left -= ride[j];
-        }
-        st.ride4 = true;
-      }
-      std::vector<int> choffs;
-      { int o = 0; for (int co : cos) { choffs.push_back(o); o += co; } }
-      for (size_t b = 0; b < ks.size(); ++b) {
-        const std::string bp = embed_key(s, (int)b);
-        const int j = ks[b] == 32 ? 0 : ks[b] == 16 ? 1 : 2;
-        if (pok[b] && st.ride4 && ride[j] > 0) st.patch.push_back(make_patch(bp, cos[b], cin, cpad, ks[b], embed_key(s, b4), 4, ride0[j], ride[j]));
-        else st.patch.push_back(pok[b] ? make_patch(bp, cos[b], cin, cpad, ks[b]) : PatchW());
-        st.embed.push_back(make_conv(bp, 0, cos[b], cin, cpad, ks[b], ks[b], true, nullptr, nullptr));
-        st.embed_k.push_back(ks[b]);
-      }
-      if (s == 0 && bidx[0] >= 0) {   // slot table + bias row of the patch kernel's 64-wide accumulator row
-        std::vector<float> tab(16, -1.f), bias64(64, 0.f);
-        const int row0[3] = {0, 16, 32};
-        for (int j = 0; j < 3; ++j) {
-          if (bidx[j] < 0) continue;
-          const HostTensor& bt = need(embed_key(s, bidx[j]) + ".bias");
-          for (int r = 0; r < used[j]; ++r) {
-            bias64[row0[j] + r] = bt.data[r];
-            if (r % 4 == 0) tab[(row0[j] + r) / 4] = (float)(choffs[bidx[j]] + r);
-          }
-          if (st.ride4) {
-            const HostTensor& b4t = need(embed_key(s, b4) + ".bias");
-            for (int r = 0; r < ride[j]; ++r) {
-              bias64[row0[j] + used[j] + r] = b4t.data[ride0[j] + r];
-              if (r % 4 == 0) tab[(row0[j] + used[j] + r) / 4] = (float)(choffs[b4] + ride0[j] + r);
-            }
-          }
-        }
-        st.patch_tab = push_f(tab);
-        st.patch_bias64 = push_f(bias64);
-      }
-      {   // one launch for the whole CrossEmbed where launches, not FLOPs, are the cost (stages 1-3 of the 1-degree grid)
-        bool same_parity = ks.size() >= 2 && opt.embed_merge && s >= 1;
-        for (int kk : ks) same_parity = same_parity && ((ks.back() - kk) % 2 == 0) && kk >= cfg.embed_strides[s];
-        // launch-bound = the merged GEMM itself is tiny (1-degree grid: 0.75 G products per stage); the 0.25-degree stages 2-3 pass the
-        // token test but are 42 G products each, where the padding costs more than the launch (107 / 123 us against 96 / 100 for the pair)
-        const double products = (double)sh[s] * sw[s] * cout * ks.back() * ks.back() * cin;
-        if (same_parity && small_map_tokens(s) && products <= 4e9 && sh[s] > 0) st.merged = make_embed_merged(s, ks, cos, cin, cpad);
-      }
-      for (int d = 0; d < cfg.depth[s]; ++d) {
-        const std::string p = "layers." + std::to_string(s) + ".1.layers." + std::to_string(d);
-        BlockL bl;
-        bl.sa = make_attn(p + ".0", cout, cfg.local_window_size[s], 0);
-        bl.sf = make_ff(p + ".1", cout, &bl.sa);
-        bl.la = make_attn(p + ".2", cout, cfg.global_window_size[s], 1);
-        bl.lf = make_ff(p + ".3", cout, &bl.la);
-        st.blocks.push_back(bl);
-      }
-      stages[s] = std::move(st);
-      // second pass (block addresses are final now): feed-forward kernels that also run the NEXT attention's to_qkv
-      if constexpr (sizeof(T) == 2) {
-        std::vector<BlockL>& bs = stages[s].blocks;
-        const int c = cfg.dim[s];
-        for (size_t d = 0; d < bs.size(); ++d) {
-          FFL* ffs[2] = {&bs[d].sf, &bs[d].lf};
-          const AttnL* prev[2] = {&bs[d].sa, &bs[d].la};
-          const AttnL* next[2] = {&bs[d].la, d + 1 < bs.size() ? &bs[d + 1].sa : nullptr};
-          for (int k = 0; k < 2; ++k)
-            if (ffs[k]->pack_pre >= 0 && next[k] && next[k]->wsz > 1) {
-              ffs[k]->next = next[k];
-              ffs[k]->pack_pp = pack_ff(*ffs[k], c, 4 * c, &prev[k]->out, &next[k]->qkv);
-            }
-        }
-      } else {   // fp32 storage: the split-bf16 one-launch FeedForward's to_qkv tail (wx_ff_split.h POST) reads the next attention's weights in place
-        std::vector<BlockL>& bs = stages[s].blocks;
-        for (size_t d = 0; d < bs.size(); ++d) {
-          if (bs[d].la.wsz > 1) bs[d].sf.next = &bs[d].la;
-          if (d + 1 < bs.size() && bs[d + 1].sa.wsz > 1) bs[d].lf.next = &bs[d + 1].sa;
-        }
-      }
-    }
-    const int last = cfg.dim[3];
-    const int upc[3][2] = {{last, last / 2}, {2 * (last / 2), last / 4}, {2 * (last / 4), last / 8}};
-    for (int i = 0; i < 3; ++i) {
-      const std::string p = "up_block" + std::to_string(i + 1);
-      UpL u;
-      u.cin = upc[i][0]; u.cout = upc[i][1];
-      if (u.cout % 32) throw ConfigError("decoder widths must be multiples of 32");
-      if (cfg.arch == WX_ARCH_WXFORMER) {
-        // sub-pixel conv: reference channel c*4+q feeds sub-pixel q of channel c (PixelShuffle); rows reordered
-        // to q*cout + c so the ConvT-style scatter epilogue (out_mode 1) performs the shuffle
-        std::vector<int> src(4 * u.cout);
-        for (int q = 0; q < 4; ++q)
-          for (int c = 0; c < u.cout; ++c) src[q * u.cout + c] = c * 4 + q;
-        u.convps = make_conv(p + ".conv", 0, 0, u.cin, u.cin, 3, 3, true, nullptr, nullptr, &src);
-        u.sharp = make_conv(p + ".sharp", 0, u.cout, u.cout, u.cout, 3, 3, true, nullptr, nullptr);
-      } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
-        u.upc = make_conv(p + ".conv", 0, u.cout, u.cin, u.cin, 3, 3, true, nullptr, nullptr);
-      } else {
-        u.convt = make_convt2(p + ".conv", u.cin, u.cout);
-      }
-      u.c1 = make_conv(p + ".b.0", 0, u.cout, u.cout, u.cout, 3, 3, true, nullptr, nullptr);
-      u.c2 = make_conv(p + ".b.3", 0, u.cout, u.cout, u.cout, 3, 3, true, nullptr, nullptr);
-      u.g1 = push_f(need(p + ".b.1.weight").data); u.b1 = push_f(need(p + ".b.1.bias").data);
-      u.g2 = push_f(need(p + ".b.4.weight").data); u.b2 = push_f(need(p + ".b.4.bias").data);
-      ups[i] = u;
-    }
-    if (cfg.arch == WX_ARCH_WXFORMER) {
-      cpad4 = ((C_out + 31) / 32) * 32;  // padded channel count of the shuffled map (zero rows / zero input weights)
-      std::vector<int> src(4 * cpad4, -1);
-      for (int q = 0; q < 4; ++q)
-        for (int c = 0; c < C_out; ++c) src[q * cpad4 + c] = c * 4 + q;
-      ps4 = make_conv("up_block4.0", 0, 0, 2 * (last / 8), 2 * (last / 8), 3, 3, true, nullptr, nullptr, &src);
-      fin4 = make_conv("up_block4.2", 0, C_out, C_out, cpad4, 3, 3, true, nullptr, nullptr);
-    } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
-      up4c = make_conv("up_block4.1", 0, C_out, 2 * (last / 8), 2 * (last / 8), 3, 3, true, nullptr, nullptr);
-    } else {
-      make_convt4("up_block4", 2 * (last / 8), C_out);
-    }
-
-    for (int l = 0; l < 6; ++l) {
-      nz[l] = NoiseL{};
-      if (!noise_slot_on(l)) continue;
-      const std::string p = noise_prefix(l);
-      nz[l].w = push_f(need(p + ".noise_transform.weight").data);
-      nz[l].b = push_f(need(p + ".noise_transform.bias").data);
-      nz[l].mod = push_f(need(p + ".modulation").data);
-      nz[l].nf = push_f(need(p + ".noise_factor").data);
-    }
-
+    WeightPacker<T> pk(*this, *this, opt, split_mma);
+    pk.run();
     // upload
-    if (wt_dev) { (void)hipFree(wt_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)wt_dev)); wt_dev = nullptr; }
-    if (f_dev) { (void)hipFree(f_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)f_dev)); f_dev = nullptr; }
-    wt_dev = (T*)dalloc(wt_host.size() * sizeof(T) + 256);
-    f_dev = (float*)dalloc(f_host.size() * sizeof(float) + 256);
-    WX_HIP(hipMemcpy(wt_dev, wt_host.data(), wt_host.size() * sizeof(T), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy(f_dev, f_host.data(), f_host.size() * sizeof(float), hipMemcpyHostToDevice));
+    dfree(wt_dev);
+    dfree(f_dev);
+    wt_dev = (T*)dalloc(pk.wt_host.size() * sizeof(T) + 256);
+    f_dev = (float*)dalloc(pk.f_host.size() * sizeof(float) + 256);
+    WX_HIP(hipMemcpy(wt_dev, pk.wt_host.data(), pk.wt_host.size() * sizeof(T), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy(f_dev, pk.f_host.data(), pk.f_host.size() * sizeof(float), hipMemcpyHostToDevice));
     if constexpr (sizeof(T) == 4) {
       if (split_mma) {
         // the split arena: same offsets, same bytes per 32-float chunk -- [hi fragments g = 0..3 | lo fragments g = 0..3], fragment g =
         // the eight k values {4 g .. 4 g + 3, 16 + 4 g .. 16 + 4 g + 3} a lane of k-group g feeds to v_mfma_f32_16x16x32_bf16
         // (the same two 16-byte slots of the fp32 activation row the exact-f32 path reads in its two sub-steps).  Every weight row of
         // a layer with cin % 32 == 0 is a whole number of chunks from a chunk-aligned start (push_w); other layers keep the f32 MFMA.
-        while (wt_host.size() % 32) wt_host.push_back(0.f);
-        std::vector<uint16_t> sp(wt_host.size() * 2);
-        split_encode_chunks(wt_host.data(), wt_host.size(), sp.data());
-        if (ws_dev) { (void)hipFree(ws_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)ws_dev)); ws_dev = nullptr; }
+        while (pk.wt_host.size() % 32) pk.wt_host.push_back(0.f);
+        std::vector<uint16_t> sp(pk.wt_host.size() * 2);
+        split_encode_chunks(pk.wt_host.data(), pk.wt_host.size(), sp.data());
+        dfree(ws_dev);
         ws_dev = (T*)dalloc(sp.size() * sizeof(uint16_t) + 256);
         WX_HIP(hipMemcpy(ws_dev, sp.data(), sp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-        if (!sp16_host.empty()) {
-          if (sp16_dev) { (void)hipFree(sp16_dev); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)sp16_dev)); sp16_dev = nullptr; }   // a second wx_finalize_weights: no leak
-          sp16_dev = (uint16_t*)dalloc(sp16_host.size() * sizeof(uint16_t) + 256);
-          WX_HIP(hipMemcpy(sp16_dev, sp16_host.data(), sp16_host.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-          std::vector<uint16_t>().swap(sp16_host);
+        if (!pk.sp16_host.empty()) {
+          dfree(sp16_dev);   // a second wx_finalize_weights: no leak
+          sp16_dev = (uint16_t*)dalloc(pk.sp16_host.size() * sizeof(uint16_t) + 256);
+          WX_HIP(hipMemcpy(sp16_dev, pk.sp16_host.data(), pk.sp16_host.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
       }
     }
-    std::vector<T>().swap(wt_host);
     alloc_activations();
     finalized = true;
   }
@@ -1014,6 +167,13 @@ class Engine : public EngineBase {
     allocs.push_back(p);
     return p;
   }
+  template <typename P>
+  void dfree(P*& p) {
+    if (!p) return;
+    (void)hipFree(p);
+    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)p));
+    p = nullptr;
+  }
   T* ws_dev = nullptr;       // split_mma: the weight arena re-encoded as bf16 (hi, lo) fragments, same offsets as wt_dev
   char* xs_planes = nullptr; // split_mma: the packed input as bf16 planes [x_hi | x_lo] (PackParams::split_planar); the patch kernel's third
                              // chunk group wraps around to x_hi (EmbedPatchParams::plane_wrap)
@@ -1025,7 +185,6 @@ class Engine : public EngineBase {
   T* attn_o = nullptr;       // attention output before to_out
   T* dtmp[4] = {nullptr, nullptr, nullptr, nullptr};  // decoder temporaries
   T* upbuf = nullptr;        // upsample_v_conv variant: 2x bilinear up-sampled map feeding the 3x3 conv
-  ConvW up4c;                // ... its up_block4 conv
   T* dec = nullptr;          // up_block4 output [Hd][Wd][ld_dec]
   float2* rowstat = nullptr;
   char* zero_page = nullptr;
@@ -1648,7 +807,6 @@ class Engine : public EngineBase {
   // qkv_ready: the previous fused feed-forward kernel already wrote this attention's q|k|v into `scratch`
   // the whole attention sub-block in one launch?  (bf16 engine, C = 128 / 256, unsharded maps; q|k|v and the attention output never
   // exist in memory on this path: a debug run captures the sub-block's output only)
-  bool small_map_tokens(int s) const { return (int64_t)sh[s] * sw[s] <= 32768; }
   bool attn_block_ok(const AttnL& a, int s) const {
     if (sizeof(T) != 2 || !opt.attn_block || band_on || attn_kind_override >= 0 || a.bias_tb < 0 || cfg.dim_head != 32) return false;
     if (opt.attn_block == 2) {
@@ -2463,39 +1621,6 @@ class Engine : public EngineBase {
   int b_rows(int s) const { return bplan.g.rows_short(s, b_rank); }
   int b_own_rows() const { return bplan.g.po[b_rank + 1] - bplan.g.po[b_rank]; }
 
-  static BandModel band_model(const Engine& e, int n) {
-    BandModel m;
-    m.n = n; m.C_in = e.C_in; m.H = e.cfg.image_height; m.W = e.cfg.image_width;
-    m.p0 = e.cfg.pad_activate ? e.cfg.pad_lat[0] : 0; m.p1 = e.cfg.pad_activate ? e.cfg.pad_lat[1] : 0;
-    m.Hp = e.Hp; m.halo = e.halo;
-    for (int s = 0; s < 4; ++s) {
-      m.stride[s] = e.cfg.embed_strides[s];
-      m.sh[s] = e.band_on ? e.gsh[s] : e.sh[s]; m.sw[s] = e.sw[s];
-      m.wl[s] = e.cfg.local_window_size[s]; m.wg[s] = e.cfg.global_window_size[s];
-      m.depth[s] = e.cfg.depth[s]; m.dim[s] = e.cfg.dim[s];
-      int lo = 0, hi = 0;
-      for (int b = 0; b < e.cfg.n_embed_kernels[s]; ++b) {
-        const int k = e.cfg.embed_kernels[s][b], pd = (k - m.stride[s]) / 2;
-        lo = std::max(lo, pd);
-        hi = std::max(hi, k - m.stride[s] - pd);
-      }
-      m.emb_lo[s] = lo; m.emb_hi[s] = hi;
-    }
-    m.elem = (int)sizeof(T);
-    for (int i = 0; i < 3; ++i) m.up_cout[i] = e.cfg.dim[2 - i];
-    m.Hd = e.Hd; m.Wd = e.Wd; m.Hu = e.Hu; m.Ho = e.Ho; m.off_y = e.cfg.pad_activate ? e.cfg.pad_lat[0] : 0;
-    m.interp = e.cfg.interp; m.ld_dec = e.ld_dec;
-    m.wxformer = e.cfg.arch == WX_ARCH_WXFORMER; m.cpad4 = ((e.C_out + 31) / 32) * 32;
-    m.n_fix = e.post ? e.post->n_fixers() : 0;
-    return m;
-  }
-  static void band_check_supported(const Engine& e) {
-    if (e.cfg.arch != WX_ARCH_CROSSFORMER && e.cfg.arch != WX_ARCH_WXFORMER)
-      throw ConfigError("lat-band mode: the upsample_v_conv decoder variant is not wired (crossformer and wxformer are)");
-    if (e.cfg.frames != 1 || e.cfg.output_frames != 1) throw ConfigError("lat-band mode needs frames == output_frames == 1");
-    if (e.cfg.dim_head != 32) throw ConfigError("lat-band mode needs dim_head == 32");
-    if (e.cfg.noise_latent_dim > 0) throw ConfigError("lat-band mode: the noise-injection ensemble (noise_latent_dim > 0) is not supported");
-  }
 
   void band_enable(int rank, int n) override {
     if (cfg.pad_activate == 2) throw ConfigError("lat-band mode supports padding mode 'earth' only (the band plan's pole rows)");
@@ -2506,11 +1631,11 @@ class Engine : public EngineBase {
     WX_HIP(hipSetDevice(device));
     if (splitk_bound(true) > splitk_bytes) {   // the band ranks' split-K rule reaches more tiles than the whole-map engine's
       splitk_bytes = splitk_bound(true);
-      if (splitk_buf) { (void)hipFree(splitk_buf); allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)splitk_buf)); splitk_buf = nullptr; }
+      dfree(splitk_buf);
       splitk_buf = (float*)dalloc(splitk_bytes);
     }
     for (int s = 0; s < 4; ++s) gsh[s] = sh[s];
-    bplan.build(band_model(*this, n));
+    bplan.build(band_model(*this, n, (int)sizeof(T), post ? post->n_fixers() : 0));
     b_rank = rank; b_n = n;
     const BandGeom& g = bplan.g;
     if (g.rows_short(0, rank) <= 0) throw ConfigError("lat-band mode: more ranks than window rows at stage 0");
@@ -3218,500 +2343,4 @@ class Engine : public EngineBase {
 
 }  // namespace wx
 
-// ======================================================================================= C ABI
-struct wx_engine {
-  std::unique_ptr<wx::EngineBase> impl;
-};
-
-template <typename F>
-static int guarded(F&& fn) {
-  try {
-    fn();
-    return WX_OK;
-  } catch (const wx::ConfigError& e) { wx::g_last_error = e.what(); return WX_ERR_INVALID;
-  } catch (const wx::StateError& e) { wx::g_last_error = e.what(); return WX_ERR_STATE;
-  } catch (const wx::MissingError& e) { wx::g_last_error = e.what(); return WX_ERR_MISSING;
-  } catch (const wx::ShapeError& e) { wx::g_last_error = e.what(); return WX_ERR_SHAPE;
-  } catch (const wx::HipError& e) { wx::g_last_error = e.what(); return WX_ERR_HIP;
-  } catch (const std::exception& e) { wx::g_last_error = e.what(); return WX_ERR_INVALID; }
-}
-#define WX_NEED(h) if (!(h) || !(h)->impl) throw wx::ConfigError("null engine handle")
-
-extern "C" {
-
-int wx_create(const wx_config* cfg, int device, wx_handle* out) {
-  return guarded([&] {
-    if (!cfg || !out) throw wx::ConfigError("wx_create: null argument");
-    int ndev = 0;
-    WX_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw wx::ConfigError("wx_create: no such GPU device");
-    WX_HIP(hipSetDevice(device));
-    std::unique_ptr<wx_engine> h(new wx_engine);
-    const wx::Options opt = wx::Options::from_env();
-    if (cfg->precision == WX_PREC_FP32) h->impl.reset(new wx::Engine<float>(*cfg, device, opt));
-    else if (cfg->precision == WX_PREC_FP32_SPLIT) h->impl.reset(new wx::Engine<float>(*cfg, device, opt, /*split=*/true));
-    else if (cfg->precision == WX_PREC_BF16) h->impl.reset(new wx::Engine<wx::bf16_t>(*cfg, device, opt));
-    else throw wx::ConfigError("wx_create: unknown precision");
-    *out = h.release();
-  });
-}
-int wx_destroy(wx_handle h) {
-  return guarded([&] { delete h; });
-}
-int wx_load_tensor(wx_handle h, const char* key, const float* data, int ndim, const int64_t* shape) {
-  return guarded([&] { WX_NEED(h); if (!key || !data || !shape) throw wx::ConfigError("wx_load_tensor: null argument"); h->impl->load_tensor(key, data, ndim, shape); });
-}
-int wx_finalize_weights(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->finalize(); }); }
-int wx_num_tensors(wx_handle h) { return (h && h->impl) ? h->impl->num_tensors() : WX_ERR_INVALID; }
-int wx_tensor_info(wx_handle h, int index, const char** key, int* ndim, int64_t shape[8]) {
-  return guarded([&] { WX_NEED(h); h->impl->tensor_info(index, key, ndim, shape); });
-}
-int wx_set_denorm(wx_handle h, const float* mean, const float* stdv, int n) {
-  return guarded([&] { WX_NEED(h); if (!mean || !stdv) throw wx::ConfigError("wx_set_denorm: null argument"); h->impl->set_denorm(mean, stdv, n); });
-}
-int wx_set_tracer_fixer(wx_handle h, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
-  return guarded([&] { WX_NEED(h); if (n > 0 && (!inds || !thres)) throw wx::ConfigError("wx_set_tracer_fixer: null argument"); h->impl->set_tracer(inds, thres, thres_max, n, denorm); });
-}
-int wx_set_layout(wx_handle h, int n_prog, int n_static, int n_dyn) {
-  return guarded([&] { WX_NEED(h); h->impl->set_layout(n_prog, n_static, n_dyn); });
-}
-int wx_set_layout_groups(wx_handle h, int n_groups, const int32_t* kind, const int32_t* x_start, const int32_t* src_start, const int32_t* count) {
-  return guarded([&] { WX_NEED(h); h->impl->set_layout_groups(n_groups, kind, x_start, src_start, count); });
-}
-int wx_forward(wx_handle h, const float* x_dev, float* y_dev, int batch, void* stream) {
-  return guarded([&] { WX_NEED(h); if (!x_dev || !y_dev) throw wx::ConfigError("wx_forward: null pointer"); h->impl->forward(x_dev, y_dev, batch, (hipStream_t)stream); });
-}
-int wx_step(wx_handle h, const float* x_dev, const float* frc_dev, float* y_dev, float* y_phys_dev, float* x_next_dev, void* stream) {
-  return guarded([&] { WX_NEED(h); if (!x_dev) throw wx::ConfigError("wx_step: null input"); h->impl->step(x_dev, frc_dev, y_dev, y_phys_dev, x_next_dev, (hipStream_t)stream); });
-}
-int wx_rollout(wx_handle h, const float* x0_dev, const float* const* frc_dev, int n_steps, float* const* y_phys_dev, float* x_final_dev,
-               void* stream) {
-  return guarded([&] { WX_NEED(h); h->impl->rollout(x0_dev, frc_dev, n_steps, y_phys_dev, x_final_dev, (hipStream_t)stream); });
-}
-int wx_band_enable(wx_handle h, int rank, int nranks) { return guarded([&] { WX_NEED(h); h->impl->band_enable(rank, nranks); }); }
-int wx_band_info(wx_handle h, int* own_row0, int* own_rows, int64_t* send_bytes, int64_t* recv_bytes, int* n_exchanges) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!own_row0 || !own_rows || !send_bytes || !recv_bytes || !n_exchanges) throw wx::ConfigError("wx_band_info: null argument");
-    h->impl->band_info(own_row0, own_rows, send_bytes, recv_bytes, n_exchanges);
-  });
-}
-int wx_band_set_staging(wx_handle h, void* send_dev, int64_t send_bytes, void* recv_dev, int64_t recv_bytes) {
-  return guarded([&] { WX_NEED(h); h->impl->band_set_staging(send_dev, send_bytes, recv_dev, recv_bytes); });
-}
-int wx_band_exchange(wx_handle h, int xid, wx_band_msg* sends, int cap_sends, int* n_sends, wx_band_msg* recvs, int cap_recvs, int* n_recvs) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!sends || !recvs || !n_sends || !n_recvs) throw wx::ConfigError("wx_band_exchange: null argument");
-    h->impl->band_messages_of(xid, sends, cap_sends, n_sends, recvs, cap_recvs, n_recvs);
-  });
-}
-int wx_band_begin(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band, void* stream,
-                  int* next_xid) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!next_xid) throw wx::ConfigError("wx_band_begin: null next_xid");
-    *next_xid = h->impl->band_begin(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream);
-  });
-}
-int wx_band_resume(wx_handle h, int* next_xid) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!next_xid) throw wx::ConfigError("wx_band_resume: null next_xid");
-    *next_xid = h->impl->band_resume();
-  });
-}
-int wx_band_comm_stream(wx_handle h, void* adopt_stream, void** stream_out) {
-  return guarded([&] {
-    WX_NEED(h);
-    void* st = h->impl->band_comm_stream(adopt_stream);
-    if (stream_out) *stream_out = st;
-  });
-}
-int wx_band_rccl_unique_id(uint8_t id[128]) {
-  return guarded([&] {
-    if (!id) throw wx::ConfigError("wx_band_rccl_unique_id: null argument");
-    wx::RcclApi& api = wx::RcclApi::get();
-    ncclUniqueId u;
-    api.check(api.GetUniqueId(&u), "ncclGetUniqueId");
-    static_assert(sizeof(u) == 128, "ncclUniqueId size");
-    std::memcpy(id, &u, 128);
-  });
-}
-int wx_band_rccl_init(wx_handle h, const uint8_t id[128]) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!id) throw wx::ConfigError("wx_band_rccl_init: null argument");
-    ncclUniqueId u;
-    std::memcpy(&u, id, 128);
-    h->impl->band_rccl_init(u);
-  });
-}
-int wx_band_step_rccl(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band,
-                      void* stream) {
-  return guarded([&] { WX_NEED(h); h->impl->band_step_rccl(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream); });
-}
-// host-only plan: a never-finalized engine object supplies the derived geometry (no HIP call is made)
-struct wx_band_plan_s { wx::BandPlan plan; };
-int wx_band_plan_create(const wx_config* cfg, int nranks, wx_band_plan* out) {
-  return guarded([&] {
-    if (!cfg || !out) throw wx::ConfigError("wx_band_plan_create: null argument");
-    if (nranks < 1) throw wx::ConfigError("wx_band_plan_create: nranks must be >= 1");
-    std::unique_ptr<wx_band_plan_s> p(new wx_band_plan_s);
-    const wx::Options opt = wx::Options::from_env();
-    if (cfg->precision == WX_PREC_FP32 || cfg->precision == WX_PREC_FP32_SPLIT) {   // the plan depends on geometry, not on arithmetic
-      wx::Engine<float> e(*cfg, -1, opt);
-      wx::Engine<float>::band_check_supported(e);
-      p->plan.build(wx::Engine<float>::band_model(e, nranks));
-    } else {
-      wx::Engine<wx::bf16_t> e(*cfg, -1, opt);
-      wx::Engine<wx::bf16_t>::band_check_supported(e);
-      p->plan.build(wx::Engine<wx::bf16_t>::band_model(e, nranks));
-    }
-    *out = p.release();
-  });
-}
-int wx_band_plan_destroy(wx_band_plan p) { return guarded([&] { delete p; }); }
-int wx_band_plan_num_exchanges(wx_band_plan p, int* n) {
-  return guarded([&] { if (!p || !n) throw wx::ConfigError("null argument"); *n = (int)p->plan.xs.size(); });
-}
-int wx_band_plan_exchange_name(wx_band_plan p, int xid, const char** name) {
-  return guarded([&] {
-    if (!p || !name || xid < 0 || xid >= (int)p->plan.xs.size()) throw wx::ConfigError("wx_band_plan_exchange_name: bad argument");
-    *name = p->plan.xs[xid].name.c_str();
-  });
-}
-int wx_band_plan_messages(wx_band_plan p, int xid, int rank, wx_band_msg* sends, int cap_sends, int* n_sends, wx_band_msg* recvs,
-                          int cap_recvs, int* n_recvs) {
-  return guarded([&] {
-    if (!p || !sends || !recvs || !n_sends || !n_recvs || xid < 0 || xid >= (int)p->plan.xs.size() || rank < 0 || rank >= p->plan.m.n)
-      throw wx::ConfigError("wx_band_plan_messages: bad argument");
-    std::vector<wx::BandMsg> s, r;
-    wx::band_messages(p->plan.xs[xid], rank, &s, &r);
-    if ((int)s.size() > cap_sends || (int)r.size() > cap_recvs) throw wx::ConfigError("wx_band_plan_messages: arrays too small");
-    for (size_t i = 0; i < s.size(); ++i) sends[i] = wx_band_msg{s[i].peer, s[i].offset, s[i].bytes};
-    for (size_t i = 0; i < r.size(); ++i) recvs[i] = wx_band_msg{r[i].peer, r[i].offset, r[i].bytes};
-    *n_sends = (int)s.size(); *n_recvs = (int)r.size();
-  });
-}
-int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts) {
-  return guarded([&] {
-    if (!p || !starts || which < 0 || which > 8) throw wx::ConfigError("wx_band_plan_partition: bad argument");
-    const std::vector<int>& v = which < 4 ? p->plan.g.ps[which] : which < 8 ? p->plan.g.pl[which - 4] : p->plan.g.po;
-    for (size_t i = 0; i < v.size(); ++i) starts[i] = v[i];
-  });
-}
-int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step) {
-  return guarded([&] { WX_NEED(h); h->impl->set_noise(seed, member0, step); });
-}
-int wx_set_noise_tape(wx_handle h, const float* const* draws, int n) {
-  return guarded([&] { WX_NEED(h); h->impl->set_noise_tape(draws, n); });
-}
-int wx_set_debug(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->set_debug(enable); }); }
-int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]) {
-  return guarded([&] { WX_NEED(h); if (!name || !shape) throw wx::ConfigError("wx_debug_read: null argument"); h->impl->debug_read(name, host_out, capacity, shape); });
-}
-int wx_query(wx_handle h, const char* key, int64_t* value) {
-  return guarded([&] {
-    WX_NEED(h);
-    if (!key || !value) throw wx::ConfigError("wx_query: null argument");
-    if (!h->impl->query(key, value)) throw wx::ConfigError(std::string("wx_query: unknown key '") + key + "'");
-  });
-}
-int wx_profile(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->profile(enable); }); }
-int wx_profile_reset(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->profile_reset(); }); }
-int wx_profile_read(wx_handle h, wx_kernel_stat* out, int capacity, int* count) {
-  return guarded([&] { WX_NEED(h); if (!out || !count) throw wx::ConfigError("wx_profile_read: null argument"); *count = h->impl->profile_read(out, capacity); });
-}
-// ---- pre block (input normalisation + channel concatenation) ---------------------------------------------------------
-struct wx_pre {
-  std::unique_ptr<wx::PreBlock> impl;
-};
-int wx_pre_create(int n_fields, const int32_t* n_levels, int frames, int H, int W, const float* mean, const float* stdv, int device,
-                  wx_pre_handle* out) {
-  return guarded([&] {
-    if (!out || !n_levels) throw wx::ConfigError("wx_pre_create: null argument");
-    int ndev = 0;
-    WX_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw wx::ConfigError("wx_pre_create: no such GPU device");
-    std::unique_ptr<wx_pre> p(new wx_pre);
-    p->impl.reset(new wx::PreBlock(n_fields, n_levels, frames, H, W, mean, stdv, device));
-    *out = p.release();
-  });
-}
-int wx_pre_destroy(wx_pre_handle p) { return guarded([&] { delete p; }); }
-int wx_pre_channels(wx_pre_handle p, int* channels) {
-  return guarded([&] { if (!p || !p->impl || !channels) throw wx::ConfigError("wx_pre_channels: null argument"); *channels = p->impl->channels(); });
-}
-int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, int batch, void* stream) {
-  return guarded([&] {
-    if (!p || !p->impl || !fields_dev || !x_dev) throw wx::ConfigError("wx_pre_apply: null argument");
-    p->impl->apply(fields_dev, x_dev, batch, (hipStream_t)stream);
-  });
-}
-// ---- post block ------------------------------------------------------------------------------------------------
-struct wx_post {
-  std::unique_ptr<wx::PostBlock> impl;
-};
-#define WX_NEEDP(p) if (!(p) || !(p)->impl) throw wx::ConfigError("null post-block handle")
-int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx_post_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_post_create: null argument");
-    int ndev = 0;
-    WX_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) throw wx::ConfigError("wx_post_create: no such GPU device");
-    std::unique_ptr<wx_post> p(new wx_post);
-    p->impl.reset(new wx::PostBlock(H, W, c_in, frames, c_out, device));
-    *out = p.release();
-  });
-}
-int wx_post_destroy(wx_post_handle p) { return guarded([&] { delete p; }); }
-int wx_post_set_band(wx_post_handle p, int row0, int rows) {
-  return guarded([&] { if (!p || !p->impl) throw wx::ConfigError("null post handle"); p->impl->set_band(row0, rows); });
-}
-int wx_post_set_grid_sigma(wx_post_handle p, const float* lat2d, const float* lon2d, const float* coef_a, const float* coef_b,
-                           int n_levels, int midpoint, int sp_ind) {
-  return guarded([&] {
-    WX_NEEDP(p);
-    if (!lat2d || !lon2d || !coef_a || !coef_b) throw wx::ConfigError("wx_post_set_grid_sigma: null argument");
-    p->impl->set_grid_sigma(lat2d, lon2d, coef_a, coef_b, n_levels, midpoint, sp_ind);
-  });
-}
-int wx_post_set_grid(wx_post_handle p, const float* lat2d, const float* lon2d, const float* p_levels, int n_levels, int midpoint) {
-  return guarded([&] { WX_NEEDP(p); if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument"); p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint); });
-}
-int wx_post_set_stats(wx_post_handle p, const float* mi, const float* si, const float* mo, const float* so) {
-  return guarded([&] { WX_NEEDP(p); if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument"); p->impl->set_stats(mi, si, mo, so); });
-}
-int wx_post_add_tracer_fixer(wx_post_handle p, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
-  return guarded([&] { WX_NEEDP(p); if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument"); p->impl->add_tracer(inds, thres, thres_max, n, denorm); });
-}
-int wx_post_add_mass_fixer(wx_post_handle p, int q_start, int fix_level_num, int denorm) {
-  return guarded([&] { WX_NEEDP(p); p->impl->add_mass(q_start, fix_level_num, denorm); });
-}
-int wx_post_add_water_fixer(wx_post_handle p, int q_start, int precip_ind, int evapor_ind, float n_seconds, int denorm) {
-  return guarded([&] { WX_NEEDP(p); p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
-}
-int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, int n_toa,
-                                    const int32_t* toa_inds, const float* toa_signs, int n_srf, const int32_t* srf_inds,
-                                    const float* srf_signs, const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] {
-    WX_NEEDP(p);
-    if (!toa_inds || !toa_signs || !srf_inds || !srf_signs || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_signed: null argument");
-    p->impl->add_energy_signed(T_start, q_start, U_start, V_start, n_toa, toa_inds, toa_signs, n_srf, srf_inds, srf_signs, gph_surf,
-                               n_seconds, denorm);
-  });
-}
-int wx_post_add_energy_fixer_updown(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t flux_inds[9],
-                                    const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] {
-    WX_NEEDP(p);
-    if (!flux_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_updown: null argument");
-    p->impl->add_energy_updown(T_start, q_start, U_start, V_start, flux_inds, gph_surf, n_seconds, denorm);
-  });
-}
-int wx_post_add_energy_fixer(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t rad_inds[6],
-                             const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] { WX_NEEDP(p); if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument"); p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm); });
-}
-int wx_post_apply(wx_post_handle p, const float* x_dev, float* y_dev, void* stream) {
-  return guarded([&] { WX_NEEDP(p); if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer"); p->impl->apply(x_dev, y_dev, (hipStream_t)stream); });
-}
-int wx_attach_postblock(wx_handle h, wx_post_handle p) {
-  return guarded([&] { WX_NEED(h); h->impl->attach_post(p ? p->impl.get() : nullptr); });
-}
-
-// ---- standalone window attention (the Swin / FuXi mode of the attention kernel) -----------------------
-struct wx_winattn {
-  wx_winattn_desc d;
-  int device = 0;
-  int NP = 0;
-  float* bias_dev = nullptr;     // [n_bias_heads][NP][NP], padded keys -1e30, x log2(e) for bf16
-  float* logit_dev = nullptr;    // [heads] or nullptr
-  int64_t n_bias_stride = 0;     // floats between two heads' tables (0: one table shared by every head)
-  ~wx_winattn() {
-    if (bias_dev) (void)hipFree(bias_dev);
-    if (logit_dev) (void)hipFree(logit_dev);
-  }
-};
-int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bias_heads, const float* logit_scale_host, int device,
-                      wx_winattn_handle* out) {
-  return guarded([&] {
-    if (!d || !out) throw wx::ConfigError("null argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
-    const int wsx = d->wsz_x > 0 ? d->wsz_x : d->wsz_y;
-    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16) throw wx::ConfigError("winattn: unknown precision");
-    if (d->head_dim != 32 && d->head_dim != 64 && d->head_dim != 96 && d->head_dim != 128) throw wx::ConfigError("winattn: head_dim must be 32, 64, 96 or 128");
-    if (d->heads < 1 || d->C != d->heads * d->head_dim) throw wx::ConfigError("winattn: C must equal heads * head_dim");
-    if (d->wsz_y < 1 || wsx < 1 || d->H % d->wsz_y || d->W % wsx) throw wx::ConfigError("winattn: the window must divide the token map");
-    if (d->kind != 0 && d->kind != 1 && d->kind != 3) throw wx::ConfigError("winattn: kind must be 0 (block), 1 (dilated) or 3 (shifted block)");
-    if (d->kind == 1 && wsx != d->wsz_y) throw wx::ConfigError("winattn: dilated windows must be square");
-    if (d->kind == 3 && (d->shift_y < 0 || d->shift_y >= d->wsz_y || d->shift_x < 0 || d->shift_x >= wsx)) throw wx::ConfigError("winattn: shift must lie inside the window");
-    const int N = d->wsz_y * wsx;
-    const int nkf = wx::attn_nkf_tokens(N);
-    if (nkf < 0 || nkf > 8) throw wx::ConfigError("winattn: at most 128 tokens per window");
-    if (n_bias_heads != 0 && n_bias_heads != 1 && n_bias_heads != d->heads) throw wx::ConfigError("winattn: bias for 0, 1 or `heads` heads");
-    WX_HIP(hipSetDevice(device));
-    auto w = std::make_unique<wx_winattn>();
-    w->d = *d; w->device = device; w->NP = nkf * 16;
-    const int NP = w->NP, nb = n_bias_heads > 0 ? n_bias_heads : 1;
-    const float l2e = d->precision == WX_PREC_BF16 ? 1.4426950408889634f : 1.0f;   // bf16 softmax runs on exp2
-    std::vector<float> tab((size_t)nb * NP * NP, -1.0e30f);
-    for (int h = 0; h < nb; ++h)
-      for (int q = 0; q < NP; ++q)
-        for (int k = 0; k < N; ++k)
-          tab[((size_t)h * NP + q) * NP + k] = (q < N && bias_host && n_bias_heads > 0) ? bias_host[((size_t)h * N + q) * N + k] * l2e : 0.f;
-    WX_HIP(hipMalloc(&w->bias_dev, tab.size() * sizeof(float)));
-    WX_HIP(hipMemcpy(w->bias_dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
-    w->n_bias_stride = nb > 1 ? (int64_t)NP * NP : 0;
-    if (logit_scale_host) {
-      std::vector<float> ls(d->heads);
-      for (int h = 0; h < d->heads; ++h) ls[h] = logit_scale_host[h] * l2e;
-      WX_HIP(hipMalloc(&w->logit_dev, ls.size() * sizeof(float)));
-      WX_HIP(hipMemcpy(w->logit_dev, ls.data(), ls.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    *out = w.release();
-  });
-}
-int wx_winattn_destroy(wx_winattn_handle w) { return guarded([&] { delete w; }); }
-int wx_winattn_apply(wx_winattn_handle w, const void* qkv_dev, void* out_dev, void* stream) {
-  return guarded([&] {
-    if (!w) throw wx::StateError("null winattn handle");
-    if (!qkv_dev || !out_dev) throw wx::ConfigError("winattn: null tensor pointer");
-    WX_HIP(hipSetDevice(w->device));
-    const wx_winattn_desc& d = w->d;
-    wx::AttnParams p;
-    p.trace = nullptr; p.tb = nullptr; p.pack = 1;
-    p.qkv = qkv_dev; p.ld_qkv = 3 * (int64_t)d.C; p.out = out_dev; p.ld_out = d.C;
-    p.bias = w->bias_dev;
-    p.H = d.H; p.W = d.W; p.C = d.C; p.heads = d.heads; p.wsz = d.wsz_y; p.wsz_x = d.wsz_x > 0 ? d.wsz_x : d.wsz_y; p.kind = d.kind;
-    p.shift_y = d.kind == 3 ? d.shift_y : 0; p.shift_x = d.kind == 3 ? d.shift_x : 0;
-    const float l2e = d.precision == WX_PREC_BF16 ? 1.4426950408889634f : 1.0f;
-    p.mask_val = d.mask_value * l2e;
-    p.mask_x = (d.kind == 3 && (d.mask_axes & 2)) ? 1 : 0;
-    p.logit_scale = w->logit_dev;
-    // scores: cosine mode has its scale in q (logit_scale); otherwise softmax_scale (x log2 e on the exp2 path)
-    p.scale = w->logit_dev ? 1.0f : d.softmax_scale;                                             // fp32 path: scores * scale
-    p.q_scale = (!w->logit_dev && d.precision == WX_PREC_BF16) ? d.softmax_scale * l2e : 0.f;   // bf16 path: scale rides on q
-    p.bias_head_stride = w->n_bias_stride;
-    if (d.precision == WX_PREC_BF16) wx::launch_window_attn_any<wx::bf16_t>(p, d.head_dim, (hipStream_t)stream);
-    else wx::launch_window_attn_any<float>(p, d.head_dim, (hipStream_t)stream);
-  });
-}
-
-// ---- a stage of Swin V2 (Cr) blocks (BASELINE config 5: the FuXi U-Transformer's stage) -----------------
-struct wx_swin {
-  std::unique_ptr<wx::SwinStageBase> impl;
-};
-int wx_swin_create(const wx_swin_desc* d, int device, wx_swin_handle* out) {
-  return guarded([&] {
-    if (!d || !out) throw wx::ConfigError("null argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
-    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16 && d->precision != WX_PREC_FP32_SPLIT) throw wx::ConfigError("swin: unknown precision");
-    if (d->depth < 1 || d->H < 1 || d->W < 1 || d->heads < 1 || d->wsz_y < 1 || d->wsz_x < 1) throw wx::ConfigError("swin: bad geometry");
-    wx::SwinDesc sd{d->H, d->W, d->C, d->heads, d->wsz_y, d->wsz_x, d->depth, d->hidden, d->shift_y, d->shift_x, d->mask_value, d->ln_eps};
-    if (d->mask_axes != 0 && d->mask_axes != 1 && d->mask_axes != 3) throw wx::ConfigError("swin: mask_axes must be 1 (latitude) or 3 (both axes)");
-    sd.mask_axes = d->mask_axes == 3 ? 3 : 1;
-    const wx::Options opt = wx::Options::from_env();
-    auto w = std::make_unique<wx_swin>();
-    try {
-      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::SwinStage<wx::bf16_t>>(sd, device, opt);
-      else w->impl = std::make_unique<wx::SwinStage<float>>(sd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
-    } catch (const std::runtime_error& e) {
-      throw wx::ConfigError(e.what());
-    }
-    *out = w.release();
-  });
-}
-int wx_swin_load(wx_swin_handle w, int block, const char* name, const float* host, int64_t count) {
-  return guarded([&] {
-    if (!w || !name || !host) throw wx::ConfigError("swin: null argument");
-    try { w->impl->load(block, name, host, count); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::ShapeError(e.what()); }
-  });
-}
-int wx_swin_finalize(wx_swin_handle w) {
-  return guarded([&] {
-    if (!w) throw wx::StateError("null swin handle");
-    try { w->impl->finalize(); } catch (const std::runtime_error& e) { throw wx::StateError(e.what()); }
-  });
-}
-int wx_swin_apply(wx_swin_handle w, const void* x_in_dev, void* x_out_dev, void* stream) {
-  return guarded([&] {
-    if (!w) throw wx::StateError("null swin handle");
-    if (!x_in_dev || !x_out_dev) throw wx::ConfigError("swin: null tensor pointer");
-    try { w->impl->apply(x_in_dev, x_out_dev, (hipStream_t)stream); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::StateError(e.what()); }
-  });
-}
-int wx_swin_flops(wx_swin_handle w, double* flops) {
-  return guarded([&] { if (!w || !flops) throw wx::ConfigError("swin: null argument"); *flops = w->impl->flops(); });
-}
-int wx_swin_destroy(wx_swin_handle w) { return guarded([&] { delete w; }); }
-
-// ---- the FuXi forward (BASELINE config 5; credit/models/fuxi.py:454-500) -----------------------------------------------------------
-struct wx_fuxi {
-  std::unique_ptr<wx::FuxiBase> impl;
-};
-int wx_fuxi_create(const wx_fuxi_desc* d, int device, wx_fuxi_handle* out) {
-  return guarded([&] {
-    if (!d || !out) throw wx::ConfigError("null argument");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw wx::HipError("no HIP device visible: wxengine has no CPU fallback");
-    if (d->precision != WX_PREC_FP32 && d->precision != WX_PREC_BF16 && d->precision != WX_PREC_FP32_SPLIT) throw wx::ConfigError("fuxi: unknown precision");
-    if (d->H < 1 || d->W < 1 || d->C_in < 1 || d->C_out < 1 || d->frames < 1 || d->patch_h < 1 || d->patch_w < 1 || d->dim < 1 || d->heads < 1 ||
-        d->window < 1 || d->depth < 1 || d->groups_down < 1 || d->groups_up < 1)
-      throw wx::ConfigError("fuxi: bad geometry");
-    if (d->stage_variant != WX_STAGE_V2_CR && d->stage_variant != WX_STAGE_TIMM_V2) throw wx::ConfigError("fuxi: unknown stage_variant");
-    wx::FuxiDesc fd{d->H, d->W, d->C_in, d->C_out, d->frames, d->patch_h, d->patch_w, d->dim, d->heads, d->window, d->depth, d->groups_down, d->groups_up};
-    fd.stage_variant = d->stage_variant;
-    const wx::Options opt = wx::Options::from_env();
-    auto w = std::make_unique<wx_fuxi>();
-    try {
-      if (d->precision == WX_PREC_BF16) w->impl = std::make_unique<wx::FuxiModel<wx::bf16_t>>(fd, device, opt);
-      else w->impl = std::make_unique<wx::FuxiModel<float>>(fd, device, opt, d->precision == WX_PREC_FP32_SPLIT);
-    } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) {
-      throw wx::ConfigError(e.what());
-    }
-    *out = w.release();
-  });
-}
-int wx_fuxi_load(wx_fuxi_handle w, const char* name, const float* host, int64_t count) {
-  return guarded([&] {
-    if (!w || !name || !host) throw wx::ConfigError("fuxi: null argument");
-    try { w->impl->load(name, host, count); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::ShapeError(e.what()); }
-  });
-}
-int wx_fuxi_finalize(wx_fuxi_handle w) {
-  return guarded([&] {
-    if (!w) throw wx::StateError("null fuxi handle");
-    try { w->impl->finalize(); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::StateError(e.what()); }
-  });
-}
-int wx_fuxi_forward(wx_fuxi_handle w, const float* x_dev, float* y_dev, void* stream) {
-  return guarded([&] {
-    if (!w) throw wx::StateError("null fuxi handle");
-    if (!x_dev || !y_dev) throw wx::ConfigError("fuxi: null tensor pointer");
-    try { w->impl->forward(x_dev, y_dev, (hipStream_t)stream); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::StateError(e.what()); }
-  });
-}
-int wx_fuxi_debug_map(wx_fuxi_handle w, const char* name, float* host, int64_t capacity, int64_t shape[3]) {
-  return guarded([&] {
-    if (!w || !name || !shape) throw wx::ConfigError("fuxi: null argument");
-    try { w->impl->debug_copy(name, host, capacity, shape); } catch (const wx::HipError&) { throw; } catch (const std::runtime_error& e) { throw wx::ShapeError(e.what()); }
-  });
-}
-int wx_fuxi_flops(wx_fuxi_handle w, double* flops) {
-  return guarded([&] { if (!w || !flops) throw wx::ConfigError("fuxi: null argument"); *flops = w->impl->flops(); });
-}
-int wx_fuxi_destroy(wx_fuxi_handle w) { return guarded([&] { delete w; }); }
-
-const char* wx_last_error(void) { return wx::g_last_error.c_str(); }
-#ifndef WX_SOURCE_HASH
-#define WX_SOURCE_HASH "unhashed"
-#endif
-// "wxsrc:<hash of csrc/*.h, wx_engine.hip, include/wxengine.h>" is set by miles-credit_amd/build.py; the Python loader compares
-// it with the sources next to the library and refuses a stale build
-const char* wx_version(void) { return "wxengine 0.2 (gfx950) wxsrc:" WX_SOURCE_HASH; }
-
-}  // extern "C"
+#include "wx_abi.h"

@@ -4,8 +4,8 @@ Host-side mirror of the reference's domain parallelism for the inference path:
   credit/domain_parallel/manager.py:22 DomainParallelManager      -> BandRank (one engine = one band)
   credit/parallel/domain.py:25 shard_spatial / :94 gather_spatial -> split_rows / join_rows (by the engine's own partition)
   credit/domain_parallel/halo_exchange.py:45-79 (batch_isend_irecv of neighbour rows) -> BandRank.exchange (any peers)
-The engine (csrc/wx_band.h, wx_engine.hip) owns the plan: which rows move where at every exchange of a step.  This module
-only moves bytes between staging buffers -- over torch.distributed P2P (backend "nccl" = RCCL over xGMI; "gloo" is staged
+The engine owns the plan (csrc/wx_band.h builds it from the model spec of wx_spec.h, wx_engine.hip executes it): which rows
+move where at every exchange of a step.  This module only moves bytes between staging buffers -- over torch.distributed P2P (backend "nccl" = RCCL over xGMI; "gloo" is staged
 through host memory and is what the single-GPU / CPU-box tests use), or by plain device copies between VIRTUAL ranks that
 live in one process on one GPU (VirtualBands: the parity harness, and a way to run the sharded algorithm without a node).
 
