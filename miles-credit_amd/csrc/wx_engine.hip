@@ -101,7 +101,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (b_cstream_own && b_cstream) (void)hipStreamDestroy(b_cstream);
     if (b_ev_pack) { (void)hipEventDestroy(b_ev_pack); (void)hipEventDestroy(b_ev_done); }
     roll_invalidate();
-    if (side_stream) { (void)hipStreamDestroy(side_stream); (void)hipEventDestroy(ev_fork); (void)hipEventDestroy(ev_join); }
     if (roll_stream) { (void)hipStreamDestroy(roll_stream); (void)hipEventDestroy(roll_ev_in); (void)hipEventDestroy(roll_ev_out); }
     for (void* p : allocs) (void)hipFree(p);
     for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -188,7 +187,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   T* dec = nullptr;          // up_block4 output [Hd][Wd][ld_dec]
   float2* rowstat = nullptr;
   char* zero_page = nullptr;
-  int n_ff_wide = 0;
   float* embed_tail = nullptr;
   size_t embed_tail_bytes = 0;
   float* splitk_buf = nullptr;   // fp32 partial sums of every split-K form (plain, skinny, hidden-split FeedForward): ONE buffer, sized in
@@ -199,7 +197,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     size_t b = (size_t)512 * tile;                                                               // plain rule: S * tiles <= 512
     b = std::max(b, (size_t)std::max(band ? std::max(opt.skinny_tiles, opt.skinny_tiles_band) : opt.skinny_tiles, 1) * (size_t)std::max(opt.skinny_max, 1) * tile); // skinny rule: tiles <= skinny_tiles, S <= skinny_max
     b = std::max(b, (size_t)std::max(opt.ff_split_tiles, 1) * 128 * 256 * (size_t)std::max(opt.ff_split_max, 1) * sizeof(float));   // <= ff_split_tiles pixel tiles of <= 128 px, C <= 256
-    if (band && opt.ff_wide) b = std::max(b, (size_t)(std::max(opt.ff_wide_wgs, 256) + 128) * 64 * 512 * sizeof(float));   // C = 512 hidden split: S * tiles < ff_wide_wgs + tiles, tiles <= 128 of 64 px
     return b;
   }
   float* splitk_scratch(size_t need) {
@@ -221,15 +218,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   float2* gnpart = nullptr;     // [m_tiles][C] GroupNorm partials written by the 3x3 conv epilogue
   int64_t gnpart_elems = 0;
   int64_t n_attn_blk = 0;       // attention sub-blocks of the last forward that ran on the k-blocked layouts
-  // Row window (round 5): attention() / feedforward() / gemm() work on map rows [rw0, rw0 + rwn) of the current stage instead of the whole
-  // map when rwn >= 0 -- the half-maps of the two-stream schedule below.  Every buffer a sub-block touches is indexed by token, so a
-  // window is a pointer offset: the stream, q|k|v and the hidden tensor (scratch, 4 C per token: the halves' regions are disjoint),
-  // attn_o, the LayerNorm partials.  rule_rows: the row count the kernel-selection rules see (the whole map's: a half runs the kernels
-  // the whole map would, so the outputs stay bit-identical to the one-stream step).
-  int rw0 = 0, rwn = -1;
-  int64_t rule_rows = 0;
-  int64_t rw_tok0(int s) const { return rwn >= 0 ? (int64_t)rw0 * sw[s] : 0; }
-  int rw_rows(int s) const { return rwn >= 0 ? rwn : sh[s]; }
   int stat_tiles_ready = 0;     // > 0: `statpart` holds partials of the current stream contents (that many per row)
   double* gn_acc = nullptr;
   float *d_mean = nullptr, *d_std = nullptr, *d_lo = nullptr, *d_hi = nullptr;
@@ -411,20 +399,17 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   int cur_stage = -1;   // appended to kernel-class names while profiling ("gemm_ff1.s2")
 
   void profile(int on) override { prof_on = on != 0; detail_on = on > 1; family_on = on > 2; }
-  int64_t n_two_stream_stages = 0;   // of the last forward
   int64_t n_split_gemms = 0;         // GEMM launches of the last forward that ran split-bf16 arithmetic
   int64_t n_ff_split_pre = 0;        // ... of which with the out-projection in front (three GEMMs)
   int64_t n_ff_split_post = 0;       // ... of which also with the next to_qkv behind (four GEMMs)
   int64_t n_ff_split_fused = 0;      // ... of which FeedForward sub-blocks in one launch (wx_ff_split.h; counted as two GEMMs above)
   int64_t n_launches = 0;            // timed() calls of the last forward (one per kernel launch or launch + finish pair)
   bool query(const std::string& key, int64_t* v) override {
-    if (key == "two_stream_stages") { *v = n_two_stream_stages; return true; }
     if (key == "launches") { *v = n_launches; return true; }
     if (key == "precision") { *v = sizeof(T) == 2 ? WX_PREC_BF16 : (split_mma ? WX_PREC_FP32_SPLIT : WX_PREC_FP32); return true; }
     if (key == "split_gemms") { *v = n_split_gemms; return true; }
     if (key == "gemm8p_launches") { *v = n_gemm8p; return true; }
     if (key == "attn_blk") { *v = n_attn_blk; return true; }
-    if (key == "ff_wide") { *v = n_ff_wide; return true; }
     if (key == "ff_split_fused") { *v = n_ff_split_fused; return true; }
     if (key == "ff_split_pre") { *v = n_ff_split_pre; return true; }
     if (key == "ff_split_post") { *v = n_ff_split_post; return true; }
@@ -575,21 +560,20 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   Route gemm_route(const ConvW& w, const GemmReq& r) const {
     if (sizeof(T) != 2 || !opt.use_dma || opt.dbg_flags) return Route::conv128;
     const int64_t rows = (int64_t)r.out_h * r.out_w;
-    const int64_t sel_rows = rule_rows > 0 ? rule_rows : rows;   // what the selection rules see (row windows: the whole map)
     const bool same_map = r.stride == 1 && r.in_h == r.out_h && r.in_w == r.out_w;
     const bool one = w.kh == 1 && w.kw == 1 && same_map && r.pad_y == 0 && r.pad_x == 0;
     // stride-1 k x k convolutions with a deep K and >= 256 output channels on large maps (the two 3x3 convs of the decoder's first two
     // UpBlocks at 0.25 degrees: K = 4608 / 2304): the eight-phase kernel's conv form (wx_gemm8p.h) -- 127.7 -> 90.1 us and 112.6 -> 102.0 us
     // against the 128 x 128 kernel (tools/gemm8p_probe, profiles/r06_gemm8p_probe_b_conv_form.txt); bitwise the same outputs where the two
     // walk K in the same order.  GroupNorm partials: one per (160-row tile, wave row) = 80 output rows, folded like the 128-row ones.
-    if (opt.use_gemm8p && rwn < 0 && !band_on && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && same_map && r.pad_y == (w.kh - 1) / 2 &&
+    if (opt.use_gemm8p && !band_on && w.kh == w.kw && w.kh > 1 && w.kh * w.kw <= 32 && same_map && r.pad_y == (w.kh - 1) / 2 &&
         r.pad_x == (w.kw - 1) / 2 && !r.rs && r.act == 0 && r.out_mode == 0 && !r.want_stats && w.n % 256 == 0 && w.cin % 64 == 0 &&
         (w.kh * w.kw * w.cin) % 128 == 0 && rows >= opt.gemm8p_min_rows && rows * r.in_ld * 2 < (int64_t)0x7fffff00 && gemm8p_fits(rows, w.n, 2, 5, true) &&
         (!r.want_gn || (opt.fuse_ln && (int64_t)(r.gn_off + gemm8p_conv_gn_tiles(rows, w.n)) * w.n <= gnpart_elems)))
       return Route::gemm8p_conv;
     // ConvTranspose k2 s2 (a 1x1 GEMM with N = 4 cout whose epilogue scatters 2 x 2 pixels; the decoder's three UpBlocks): the same
     // kernel's 1x1 form with the scatter in its epilogue -- 33.4 -> 24.6, 59.3 -> 41.9, 63.1 -> 47.3 us at 0.25 degrees, bitwise equal
-    if (opt.use_gemm8p && rwn < 0 && !band_on && one && !r.rs && !r.res && r.act == 0 && r.out_mode == 1 && !r.want_stats && !r.want_gn &&
+    if (opt.use_gemm8p && !band_on && one && !r.rs && !r.res && r.act == 0 && r.out_mode == 1 && !r.want_stats && !r.want_gn &&
         r.cout > 0 && w.n == 4 * r.cout && r.cout % 64 == 0 && w.cin % 128 == 0 && rows >= opt.gemm8p_min_rows / 4 && gemm8p_fits(rows, w.n, 2, 5, true))
       return Route::gemm8p_convt2;
     // K = 512 layers on maps of a few thousand rows (a lat-band rank's share of the 0.25-degree stage 2: 2 000 - 4 000 tokens): the
@@ -598,19 +582,19 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     // unsharded model keeps the persistent kernel.  Bitwise the same outputs; row partials in N / 32 slots instead of N / 128.
     const bool ln_v = r.rs && !r.res && !r.want_stats && w.colsum >= 0, res_v = !r.rs && r.res && r.want_stats && opt.fuse_ln && r.act == 0;
     if (opt.use_wreg && w.wt_kb >= 0 && one && w.cin == 512 && w.n % WREG_BN == 0 && w.bias >= 0 && r.out_mode == 0 && !r.want_gn && r.blk == KBlk::none &&
-        rwn < 0 && rows >= opt.wreg_min_rows && rows < opt.wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
+        rows >= opt.wreg_min_rows && rows < opt.wreg_max_rows && (ln_v || (res_v && w.n / 32 <= WREG_MAXT)) &&
         wreg_gemm_ok(rows, w.n, w.cin, r.rs ? stat_tiles_ready : 0, ln_v))
       return Route::wreg;
     // residual layers with N = 512 / 1024 (to_out, FeedForward layer 2 of stages 2 and 3): the persistent kernel on 160 x 128 tiles, two
     // workgroups per CU (47.9 vs 58.3 us on layer 2, 21.0 vs 23.2 us on to_out; bitwise equal to the 128 x 128 kernel's output) -- with at
     // most one tile per CU and a deep K (stage 3 of the 0.25-degree model) in its loader / consumer form
     if (opt.use_stream && w.wt_kb >= 0 && one && !r.rs && r.res && r.act == 0 && r.out_mode == 0 && r.want_stats && opt.fuse_ln && !r.want_gn &&
-        (w.n == 512 || w.n == 1024) && w.bias >= 0 && sel_rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin, 128))
-      return opt.use_stream_lc && stream_gemm_lc_pays(sel_rows, w.n, w.cin, 5) ? Route::stream_res_lc : Route::stream_res;
+        (w.n == 512 || w.n == 1024) && w.bias >= 0 && rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin, 128))
+      return opt.use_stream_lc && stream_gemm_lc_pays(rows, w.n, w.cin, 5) ? Route::stream_res_lc : Route::stream_res;
     // LayerNorm-folded 1x1 layers with many rows and K >= 512 (to_qkv, FeedForward layer 1 of stages 2-3): the persistent
     // 128 x 256-tile kernel; measured per shape against the 128 x 128 kernel in tools/gemm_stream_probe
     if (opt.use_stream && w.wt_kb >= 0 && w.n % 256 == 0 && one && r.rs && !r.res && r.out_mode == 0 && !r.want_stats && !r.want_gn &&
-        sel_rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin))
+        rows >= opt.stream_min_rows && stream_gemm_ok(rows, w.n, w.cin))
       return Route::stream_ln;
     return Route::conv128;
   }
@@ -691,9 +675,8 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           });
           return {};
         }
-        const int64_t t0 = rwn >= 0 && cur_stage >= 0 && cur_stage < 4 ? rw_tok0(cur_stage) : 0;   // a row window's rows of `statpart`
         q.stat_slots = w.n / 64;
-        q.stat_out = stat_dst(t0 + rows, q.stat_slots) + t0 * q.stat_slots;
+        q.stat_out = stat_dst(rows, q.stat_slots);
         q.a_blk = r.blk != KBlk::none ? 1 : 0; q.a_rows = q.M;
         const bool lc = route == Route::stream_res_lc;
         cur_family = lc ? "stream_lc" : "stream";
@@ -706,7 +689,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     }
     if (r.blk == KBlk::hidden) throw StateError("k-blocked hidden tensor requested but the GEMM fell back to the row-major kernel");
     if (r.blk == KBlk::attn) throw StateError("k-blocked q|k|v / attention output requested but the GEMM fell back to the row-major kernel");
-    if (rwn >= 0) throw StateError("row-window launch fell to the generic kernel (the two-stream schedule runs on the persistent GEMMs only)");
     if (r.par) {   // the four parity convs of a ConvTranspose k4 s2 p1 (out_mode 2): one launch when the fast path takes it
       if (opt.merge_parity && dma && !opt.dbg_flags && w.n <= 128) {
         p.n_par = 4;
@@ -714,7 +696,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         const double fl4 = 4.0 * 2.0 * m * w.n * w.kh * w.kw * w.cin_true;
         const double by4 = (4.0 * m * w.n + (double)r.in_h * r.in_w * w.cin_true + 4.0 * w.n * w.kh * w.kw * w.cin) * sizeof(T);
         if (p.split) ++n_split_gemms;   // the merged launch
-        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, opt.gemm_cfg, opt.gemm_deep_tiles); });
+        timed(cls, fl4, by4, [&] { launch_conv_gemm<T>(p, zero_page, cur_stream, opt.gemm_cfg); });
         return {};
       }
       for (int q = 0; q < 4; ++q) {
@@ -771,7 +753,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         if (tiles > 512 && rounds < 1.5) p.bn64 = 1;
       }
     }
-    timed(cls, flops, bytes, [&] { launch_conv_gemm<T>(p, opt.use_dma ? zero_page : nullptr, cur_stream, opt.gemm_cfg, opt.gemm_deep_tiles); });
+    timed(cls, flops, bytes, [&] { launch_conv_gemm<T>(p, opt.use_dma ? zero_page : nullptr, cur_stream, opt.gemm_cfg); });
     if (p.stat_out) o.stat_slots = p.partial ? conv_gemm_finish_slots(w.n) : (p.bn64 ? cdiv(w.n, 64) : conv_gemm_n_tiles(w.n));
     return o;
   }
@@ -797,9 +779,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // LayerNorm statistics of the stream: either the partials the last producing GEMM left (stat_tiles_ready > 0)
   // or a fresh two-pass ln_stats launch (stage entry, slow-path producers).
   const float2* stream_stats(const T* x, int64_t ld, int c, int m) {
-    const int64_t t0 = rwn >= 0 && cur_stage >= 0 && cur_stage < 4 ? rw_tok0(cur_stage) : 0;
-    if (stat_tiles_ready > 0) return statpart + t0 * stat_tiles_ready;
-    if (rwn >= 0) throw StateError("row-window launch without LayerNorm partials from its producer");
+    if (stat_tiles_ready > 0) return statpart;
     ln_stats(x, ld, c, m);
     return rowstat;
   }
@@ -821,14 +801,11 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
            (a.kind == 0 || a.kind == 1) && a.qkv.cin == cfg.dim[s] && a.out.cin == cfg.dim[s];
   }
   void attention(const AttnL& a, int s, const std::string& dbg_name, bool defer_out = false, bool qkv_ready = false) {
-    const int c = cfg.dim[s], h = rw_rows(s), w = sw[s], m = h * w;
-    const int64_t ld = stream_ld(s), t0 = rw_tok0(s);
-    T* x = stream_ptr(s) + t0 * ld;
-    T* const scratch = this->scratch + t0 * 4 * c;   // the window's own q|k|v region
-    T* const attn_o = this->attn_o + t0 * c;
+    const int c = cfg.dim[s], h = sh[s], w = sw[s], m = h * w;
+    const int64_t ld = stream_ld(s);
+    T* x = stream_ptr(s);
     if constexpr (sizeof(T) == 2) {
       if (attn_block_ok(a, s)) {
-        if (rwn >= 0) throw StateError("attention block kernel on a row window");
         if (defer_out || qkv_ready) throw StateError("attention block: the fused feed-forward variants must be off for this layer");
         AttnBlockParams bp;
         bp.x = reinterpret_cast<bf16_t*>(x); bp.ld = ld;
@@ -851,9 +828,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     } else {
       // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
       // k-blocked (see KBlk); outputs bitwise the row-major chain's
-      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_on && !band_on && rwn < 0 && cfg.dim_head == 32 &&
+      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_on && !band_on && cfg.dim_head == 32 &&
           !qkv_ready && !defer_out && attn_kind_override < 0 && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
-          (rule_rows > 0 ? rule_rows : (int64_t)m) >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
+          m >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
         blk = KBlk::attn;
         ++n_attn_blk;
       }
@@ -900,7 +877,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   bool ff_split_takes_out(const FFL& f, const AttnL& a) const {
     if (cur_stage < 0 || cur_stage > 3) return false;
     const int c = cfg.dim[cur_stage];
-    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_on && !band_on && rwn < 0 && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
+    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_on && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
   }
   bool ff_takes_out(const FFL& f, const AttnL& a) const {
     if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a);
@@ -911,7 +888,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       if (cur_stage < 0 || cur_stage > 3 || !f.next) return false;
       const int c = cfg.dim[cur_stage];
       const ConvW& q = f.next->qkv;
-      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_on && !band_on && rwn < 0 && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
+      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_on && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
              q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
     }
     return ff_takes_out(f) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, cur_stage));
@@ -926,30 +903,23 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
   //               attention's LayerNorm + to_qkv behind) form
   //   split       bf16, launch-bound maps: the fused block with its hidden dimension split, and the split-K finish kernel
-  //   wide_split  bf16, C = 512 on lat-band ranks (WX_FF_WIDE=1): the same at C = 512
-  //   wide        bf16, C = 512 on the unsharded map (WX_FF_WIDE=2): the plain one-launch block
   //   split_bf16  split-bf16 precision, C = 128 / 256: both layers in one launch (wx_ff_split.h), plain / PRE / POST
   //   chain       ff1 + ff2 on gemm()
-  enum class FFForm { fused, split, wide_split, wide, split_bf16, chain };
+  enum class FFForm { fused, split, split_bf16, chain };
   FFForm ff_form(const FFL& f, int s, const AttnL* pre) const {
     if (sizeof(T) == 2) {
       if (ff_split_ok(f, s, pre)) return FFForm::split;
       if (f.pack >= 0 && opt.fuse_ff && ff_big_enough()) return FFForm::fused;
-      const bool wide_ok = f.pack_wide >= 0 && !pre && opt.fuse_ff && opt.fuse_ln && !opt.dbg_flags && rwn < 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
-      if (wide_ok && band_on && cdiv((int64_t)rw_rows(s) * sw[s], (int64_t)64) <= 128) return FFForm::wide_split;
-      if (wide_ok && !band_on && opt.ff_wide >= 2) return FFForm::wide;
     } else if (ff_split_fused_ok(f, cfg.dim[s])) {
       return FFForm::split_bf16;
     }
     return FFForm::chain;
   }
   void feedforward(const FFL& f, int s, const std::string& dbg_name, const AttnL* pre = nullptr) {
-    const int c = cfg.dim[s], h = rw_rows(s), w = sw[s], m = h * w;
-    const int64_t ld = stream_ld(s), t0 = rw_tok0(s);
-    T* x = stream_ptr(s) + t0 * ld;
-    T* const scratch = this->scratch + t0 * 4 * c;   // the window's own hidden tensor
+    const int c = cfg.dim[s], h = sh[s], w = sw[s], m = h * w;
+    const int64_t ld = stream_ld(s);
+    T* x = stream_ptr(s);
     const FFForm form = ff_form(f, s, pre);
-    if (rwn >= 0 && (pre || form != FFForm::chain)) throw StateError("fused feed-forward on a row window");
     if (pre && form != FFForm::fused && form != FFForm::split_bf16) throw StateError("feedforward: out-projection deferred to a layer that cannot take it");
     if constexpr (sizeof(T) == 2) {
       auto block_params = [&](int64_t pack) {   // the one-launch block's operands
@@ -985,22 +955,11 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         fp.qkv = post ? reinterpret_cast<bf16_t*>(scratch) : nullptr; fp.ld_qkv = 3 * c;
         fp.csq = post ? f_dev + f.next->qkv.colsum : nullptr; fp.bq = post ? f_dev + f.next->qkv.bias : nullptr;
         fp.o = pre ? reinterpret_cast<const bf16_t*>(attn_o) : nullptr; fp.ld_o = c; fp.bo = pre ? f_dev + pre->out.bias : nullptr;
-        fp.stat_out = opt.fuse_ln ? statpart : nullptr; fp.dbg = opt.ff_dbg;
-        timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, (c == 128 && !pre && opt.ff_small_px64 && cdiv(m, 128) < 128) ? 3 : opt.ff_variant); });
+        fp.stat_out = opt.fuse_ln ? statpart : nullptr; fp.dbg = 0;
+        timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, /*px64=*/c == 128 && !pre && opt.ff_small_px64 && cdiv(m, 128) < 128); });
         stat_tiles_ready = opt.fuse_ln ? 1 : 0;
       } else if (form == FFForm::split) {   // launch-bound maps (1-degree grid, C = 128 / 256 stages of 23 - 45 pixel tiles)
         hidden_split(f.pack, std::min(opt.ff_split_max, 4 * c / 32 / 4));
-      } else if (form == FFForm::wide_split) {
-        // C = 512 (wx_ff.h ff_wide_supported) on lat-band ranks: a band of 2 000 - 4 000 stage-2 tokens is 32 - 63 pixel tiles -- S ranges
-        // so that ~ff_wide_wgs workgroups run, instead of ff1 + split-K ff2 + finish
-        ++n_ff_wide;
-        hidden_split(f.pack_wide, std::min(8, std::max(2, (int)cdiv(opt.ff_wide_wgs, (int)cdiv(m, 64)))));
-      } else if (form == FFForm::wide) {   // an experiment: it loses on the unsharded map
-        FFParams fp = block_params(f.pack_wide);
-        fp.stat_out = statpart;
-        ++n_ff_wide;
-        timed("ff_fused", 16.0 * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, 0); });
-        stat_tiles_ready = 1;
       }
     }
     if constexpr (sizeof(T) == 4) {
@@ -1011,7 +970,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         q.w1s = reinterpret_cast<const float*>(ws_dev + f.w1.wt); q.b1 = f_dev + f.w1.bias;
         q.w2s = reinterpret_cast<const float*>(ws_dev + f.w2.wt); q.b2 = f_dev + f.w2.bias;
         q.rowstat = rs; q.stat_tiles = pre ? 0 : stat_tiles_ready; q.stat_inv_c = 1.0f / (float)c;
-        q.stat_out = opt.fuse_ln ? stat_dst(t0 + m, 1) + t0 : nullptr;
+        q.stat_out = opt.fuse_ln ? stat_dst(m, 1) : nullptr;
         if (!pre && q.stat_out && stat_tiles_ready > 1) {
           // the launch would read `statpart` as [M][stat_tiles_ready] in its prologue and write it as [M][1] in its epilogue: workgroup 2j's
           // stores land on the entries workgroup j still has to read, and nothing orders the two (lat-band ranks, WX_NO_FF_SPLIT_PRE,
@@ -1020,7 +979,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           q.rowstat = rowstat; q.stat_tiles = 0;
         }
         if (pre) {
-          q.o = reinterpret_cast<const float*>(attn_o + t0 * c); q.ld_o = c;
+          q.o = reinterpret_cast<const float*>(attn_o); q.ld_o = c;
           q.wos = reinterpret_cast<const float*>(ws_dev + pre->out.wt); q.bo = f_dev + pre->out.bias;
           ++n_split_gemms;
           ++n_ff_split_pre;
@@ -1043,7 +1002,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       const float2* rs = stream_stats(x, ld, c, m);
       // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
       const KBlk blk = sizeof(T) == 2 && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
-                       (rule_rows > 0 ? rule_rows : (int64_t)m) >= opt.stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
+                       m >= opt.stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
       gemm("gemm_ff1", f.w1, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 4 * c, .rs = rs, .act = 1, .blk = blk});
       stat_tiles_ready = gemm("gemm_ff2", f.w2, {.in = scratch, .in_h = h, .in_w = w, .in_ld = 4 * c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
                                                  .blk = blk, .want_stats = true}).stat_slots;
@@ -1211,18 +1170,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           launch_embed_patch<T>(ep, zero_page, cur_stream);
         });
       } else if (s == 0) {
-        // the branch that does not ride in the patch kernel (k = 4 of the 0.25-degree model: 64 channels, its own implicit GEMM) writes a
-        // channel range of the rows nobody else writes and reads the packed input only: on the engine's side stream, beside the patch
-        // launch (whose 625 tiles leave a partly filled last round), joined at the end of this function
-        const bool side = opt.embed_side && patch_on && !band_on && !prof_on && !dbg_on && !opt.dbg_flags && rwn < 0 && !side_open;
-        hipStream_t main_s = cur_stream;
-        if (side) {
-          side_ensure();
-          WX_HIP(hipEventRecord(ev_fork, main_s)); WX_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0));
-          cur_stream = side_stream;
-          side_open = true;
-        }
-        struct Back { Engine* e; hipStream_t s; ~Back() { e->cur_stream = s; } } back{this, main_s};
+        // the branch that does not ride in the patch kernel (k = 4 of the 0.25-degree model: 64 channels, its own implicit GEMM)
         gemm("gemm_embed", st.embed[b], {.in = in, .in_h = in_h, .in_w = Wp + 2 * halo, .in_ld = cpad0, .out = x + choff, .out_ld = ld, .stride = stv,
                                          .pad_y = pd - halo, .pad_x = pd - halo, .out_h = sh[0], .out_w = sw[0]});
       } else {
@@ -1236,130 +1184,10 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       choff += st.embed[b].n;
     }
     if (share) stat_tiles_ready = all_made ? total_slots : 0;
-    side_join();
-  }
-  bool side_open = false;   // a launch of this forward is in flight on side_stream and not joined yet
-  void side_join() {
-    if (!side_open) return;
-    WX_HIP(hipEventRecord(ev_join, side_stream)); WX_HIP(hipStreamWaitEvent(cur_stream, ev_join, 0));
-    side_open = false;
   }
   // a4-a7: the transformer blocks of stage s on the rows the stream currently holds
-  // ---- two-stream half-map schedule (round 5) ------------------------------------------------------------------------------------------
-  // The deep stages' launches leave wave slots idle: the stage-2 short attention is 3 200 tasks for 4 096 slots (one round whose length
-  // is one task's dependent chain), stage 3's GEMMs are one tile per CU -- two forecasts in flight recover 5-7 % from them.
-  // The same slots are filled from ONE forecast: every kernel of a sub-block chain (to_qkv -> attention -> to_out -> FeedForward 1 -> 2)
-  // is row-independent at window-row granularity, so the chain runs as two half-maps of whole window rows on two streams -- the second
-  // (engine-owned) stream forks from and joins the caller's stream through one event pair.  Short sub-blocks split (contiguous window
-  // rows); a dilated long sub-block (window > 1) needs every row of both halves and runs whole on the caller's stream between a join
-  // and the next fork; a 1-token long window (stage 3) is pointwise, so that stage forks once and joins once.  Same kernels, same
-  // tiles per row (rule_rows), so the outputs are bit-identical to the one-stream step (tests/test_variants_gpu.py).
-  // MEASURED (MI355X, C3 bf16, same box, alternating arms, tools/ab_time.py; gpurun_out/r5a): one stream 8.06-8.16 ms/step; two streams
-  // 8.39 (both stages), 8.18 (stage 2 only), 8.30 (stage 3 only), 8.25 / 8.18 with the side stream at low / high priority -- every form
-  // LOSES 1.5-3 %: a half-size launch costs the same prologue / epilogue and loses tile-level balance, the persistent GEMMs fill the
-  // register file (two 256-VGPR waves per SIMD) so the other half's attention only ever backfills a tail, and that is worth less than
-  // the halved launches cost.  (Two whole forecasts in flight gain 5-7 % because their launches keep full size and the overlapping
-  // kernels are of different kinds.)  OFF by default; WX_TWO_STREAM=1 keeps it testable (bit-identical, tests/test_variants_gpu.py).
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool two_stream_ok(int s) const {
-    if (sizeof(T) != 2 || !opt.two_stream || band_on || dbg_on || prof_on || opt.dbg_flags || !opt.use_stream || !opt.use_dma || !opt.fuse_ln) return false;
-    if (cfg.dim_head != 32 || cfg.dim[s] < 512 || (int64_t)sh[s] * sw[s] < opt.stream_min_rows) return false;
-    const StageL& st = stages[s];
-    if (st.blocks.empty()) return false;
-    const int wsz = st.blocks[0].sa.wsz;
-    if (wsz <= 1 || sh[s] / wsz < 2) return false;
-    const bool pointwise_long = st.blocks[0].la.wsz == 1;
-    if ((opt.two_stream == 2 && pointwise_long) || (opt.two_stream == 3 && !pointwise_long)) return false;   // probes: one kind of stage only
-    for (const BlockL& bl : st.blocks)
-      if (attn_block_ok(bl.sa, s) || attn_block_ok(bl.la, s) || bl.sf.pack >= 0 || bl.lf.pack >= 0 || bl.sa.wsz != wsz) return false;
-    return true;
-  }
-  void side_ensure() {
-    if (side_stream) return;
-    if (opt.two_stream_prio != INT_MIN) {   // probe: the side stream at the highest (2) / lowest (any other value) priority
-      int lo = 0, hi = 0;
-      WX_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-      WX_HIP(hipStreamCreateWithPriority(&side_stream, hipStreamNonBlocking, opt.two_stream_prio == 2 ? hi : lo));
-    } else {
-      WX_HIP(hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking));
-    }
-    WX_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
-    WX_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
-  }
-  void stage_blocks_two_stream(int s) {
-    const StageL& st = stages[s];
-    side_ensure();
-    hipStream_t main_s = cur_stream;
-    struct Restore {   // a throw inside a half must not leave the engine on the side stream / inside a row window
-      Engine* e; hipStream_t s;
-      ~Restore() { e->rw0 = 0; e->rwn = -1; e->rule_rows = 0; e->cur_stream = s; }
-    } restore{this, main_s};
-    const int wsz = st.blocks[0].sa.wsz, wr = sh[s] / wsz;
-    const int rows_a = (wr - wr / 2) * wsz, rows_b = sh[s] - rows_a;   // the caller's stream takes the larger half
-    const bool pointwise_long = st.blocks[0].la.wsz == 1;
-    rule_rows = (int64_t)sh[s] * sw[s];
-    auto fork = [&] { WX_HIP(hipEventRecord(ev_fork, main_s)); WX_HIP(hipStreamWaitEvent(side_stream, ev_fork, 0)); };
-    auto join = [&] { WX_HIP(hipEventRecord(ev_join, side_stream)); WX_HIP(hipStreamWaitEvent(main_s, ev_join, 0)); };
-    // the (host-side) LayerNorm-partial bookkeeping of a chain: both halves start from the same state and must end in the same one
-    auto half = [&](int r0, int rn, hipStream_t strm, auto&& body) {
-      const int save_ready = stat_tiles_ready;
-      rw0 = r0; rwn = rn; cur_stream = strm;
-      body();
-      rw0 = 0; rwn = -1; cur_stream = main_s;
-      const int end_ready = stat_tiles_ready;
-      stat_tiles_ready = save_ready;
-      return end_ready;
-    };
-    // A fork is safe only while both halves keep ONE LayerNorm-partial layout: statpart is [token][slots], a half's region starts at
-    // (its first token) x slots, and the residual layers of a half leave dim / 64 slots per row (the persistent GEMM's N tiles).  When the
-    // partials a chain STARTS from have another slot count (stage entry: the CrossEmbed epilogues leave 4 / 8), the regions of the two
-    // layouts overlap between the halves -- half A's first residual layer would write where half B's first to_qkv still has to read (or
-    // the other way round).  Found as a one-in-~25 mismatch of a warm-up rollout on one lease; such a chain runs whole, on the caller's
-    // stream, and leaves the chain's layout for the forks that follow.
-    const int chain_slots = cfg.dim[s] / 64;
-    auto both = [&](auto&& body) {
-      if (stat_tiles_ready != chain_slots) { body(); return; }
-      fork();
-      const auto ea = half(0, rows_a, main_s, body);
-      const auto eb = half(rows_a, rows_b, side_stream, body);
-      join();
-      if (ea != eb) throw StateError("two-stream schedule: the halves left different LayerNorm-partial states");
-      stat_tiles_ready = ea;
-    };
-    if (pointwise_long) {
-      size_t first = 0;
-      if (stat_tiles_ready != chain_slots && !st.blocks.empty()) {   // the stage's first sub-block brings the chain's layout (see `both`)
-        attention(st.blocks[0].sa, s, "");
-        feedforward(st.blocks[0].sf, s, "");
-        first = 1;
-      }
-      both([&] {
-        for (size_t d = 0; d < st.blocks.size(); ++d) {
-          const BlockL& bl = st.blocks[d];
-          if (d >= first) {
-            attention(bl.sa, s, "");
-            feedforward(bl.sf, s, "");
-          }
-          attention(bl.la, s, "");
-          feedforward(bl.lf, s, "");
-        }
-      });
-    } else {
-      for (const BlockL& bl : st.blocks) {
-        both([&] {
-          attention(bl.sa, s, "");
-          feedforward(bl.sf, s, "");
-        });
-        attention(bl.la, s, "");
-        feedforward(bl.lf, s, "");
-      }
-    }
-    rule_rows = 0;
-  }
   void stage_blocks(int s) {
     const StageL& st = stages[s];
-    if (two_stream_ok(s) && stat_tiles_ready > 0) { stage_blocks_two_stream(s); ++n_two_stream_stages; return; }
     const std::string sp = "layers." + std::to_string(s);
     bool qkv_made = false;  // the previous fused kernel already produced this attention's q|k|v
     for (size_t d = 0; d < st.blocks.size(); ++d) {
@@ -1456,14 +1284,12 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     noise_tape.assign(draws, draws + n);
   }
   void core(const float* x_item) {
-    n_two_stream_stages = 0;
     n_gemm8p = 0;
     n_attn_blk = 0;
     n_split_gemms = 0;
     n_ff_split_fused = 0;
     n_ff_split_pre = 0;
     n_ff_split_post = 0;
-    n_ff_wide = 0;
     n_launches = 0;
     // a1: pack + earth halo
     pack_input(x_item, xin, xin_planar, Hp + 2 * halo, 0, Hp, halo, 0, cfg.image_height);
@@ -2139,7 +1965,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     cur_stream = s;
     bx_own = x_own; bfrc_own = frc_own; by = y; by_phys = y_phys; bx_next = x_next;
     b_pc = 0;
-    n_ff_wide = 0;
     return band_run();
   }
   // ---- RCCL transport inside the engine: no host code between the segments of a step besides the launches themselves

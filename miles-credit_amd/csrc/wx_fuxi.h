@@ -337,7 +337,7 @@ struct FuxiModel : FuxiBase {
       const auto it = split_of.find(w);
       if (it != split_of.end() && cin % 32 == 0 && conv_gemm_is_dma<T>(p, zero_page)) { p.split = 1; p.wt = it->second; }
     }
-    launch_conv_gemm<T>(p, zero_page, s, 0, opt.gemm_deep_tiles);
+    launch_conv_gemm<T>(p, zero_page, s, 0);
   }
   // out = SiLU(GroupNorm(x)) [+ res]
   void gn_silu(const T* x, int64_t m, const float* g, const float* b, int groups, const T* res, T* out, int64_t out_ld, hipStream_t s) {

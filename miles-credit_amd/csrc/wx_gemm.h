@@ -1069,13 +1069,10 @@ inline void launch_conv_gemm_kb(const ConvGemmParams& p, hipStream_t stream) {
 }
 
 template <typename T, int BN, int KB>
-inline void launch_conv_gemm_dma(const ConvGemmParams& p, const void* zero_page, hipStream_t stream, int deep_max) {
+inline void launch_conv_gemm_dma(const ConvGemmParams& p, const void* zero_page, hipStream_t stream) {
   const bool one = p.kh == 1 && p.kw == 1 && p.stride == 1 && p.pad_y == 0 && p.pad_x == 0 && p.in_h == p.out_h &&
                    p.in_w == p.out_w;
   const bool three = KB == 64 && (p.dbg & 128);  // experiment switch: 3-stage ring, 3 workgroups/CU
-  // experiment switch (deep_max: Options::gemm_deep_tiles, off by default): launches of <= deep_max tiles on a 4-stage ring, three K stages in flight per CU
-  const bool deep = KB == 128 && !three && !(p.dbg & 512) &&
-                    (int64_t)cdiv(p.out_h * p.out_w, 128) * (p.n_par == 4 ? 4 : cdiv(p.n, BN)) * (p.partial ? p.k_splits : 1) <= deep_max;
   if constexpr (sizeof(T) == 4 && KB == 128) {
     if (p.split) {   // split-bf16 arithmetic (fp32 storage): the same three address forms on the 2-stage ring
       // (a 3- / 4-stage ring with one workgroup per CU: 24.4 -> 29.4 / 30.1 ms per C3 forward, docs/history/r05_negative_results.md)
@@ -1094,14 +1091,11 @@ inline void launch_conv_gemm_dma(const ConvGemmParams& p, const void* zero_page,
       }
     }
     if (three) launch_conv_gemm_dma_v<T, 128, BN, KB, true, (KB == 64 ? 3 : 2)>(p, zero_page, stream);
-    else if (deep) launch_conv_gemm_dma_v<T, 128, BN, KB, true, (KB == 128 ? 4 : 2)>(p, zero_page, stream);
     else launch_conv_gemm_dma_v<T, 128, BN, KB, true, 2>(p, zero_page, stream);
   } else if (p.cin * (int)sizeof(T) / KB >= 8) {
-    if (deep) launch_conv_gemm_dma_v<T, 128, BN, KB, false, (KB == 128 ? 4 : 2), true>(p, zero_page, stream);
-    else launch_conv_gemm_dma_v<T, 128, BN, KB, false, 2, true>(p, zero_page, stream);
+    launch_conv_gemm_dma_v<T, 128, BN, KB, false, 2, true>(p, zero_page, stream);
   } else {
-    if (deep) launch_conv_gemm_dma_v<T, 128, BN, KB, false, (KB == 128 ? 4 : 2), false>(p, zero_page, stream);
-    else launch_conv_gemm_dma_v<T, 128, BN, KB, false, 2, false>(p, zero_page, stream);
+    launch_conv_gemm_dma_v<T, 128, BN, KB, false, 2, false>(p, zero_page, stream);
   }
 }
 
@@ -1128,9 +1122,9 @@ inline bool conv_gemm_is_dma(const ConvGemmParams& p, const void* zero_page) {
 }
 inline int conv_gemm_n_tiles(int n) { return cdiv(n, n >= 96 ? 128 : 64); }
 
-// gemm_cfg: 0 = automatic, 1 = force KB 128 (2 workgroups/CU), 2 = force KB 64 (4 workgroups/CU); deep_max: launch_conv_gemm_dma
+// gemm_cfg: 0 = automatic, 1 = force KB 128 (2 workgroups/CU), 2 = force KB 64 (4 workgroups/CU), 3 = 64-column tiles
 template <typename T>
-inline void launch_conv_gemm(const ConvGemmParams& p, const void* zero_page, hipStream_t stream, int gemm_cfg, int deep_max) {
+inline void launch_conv_gemm(const ConvGemmParams& p, const void* zero_page, hipStream_t stream, int gemm_cfg) {
   const int row_bytes = p.cin * (int)sizeof(T);
   const bool dma_ok = conv_gemm_is_dma<T>(p, zero_page);
   if ((p.stat_out || p.gn_out) && !dma_ok) throw std::runtime_error("conv_gemm: statistics output requested on the slow path");
@@ -1157,11 +1151,11 @@ inline void launch_conv_gemm(const ConvGemmParams& p, const void* zero_page, hip
     if (gemm_cfg == 1 && row_bytes % 128 == 0) kb64 = false;
     if (gemm_cfg == 2 && !p.split) kb64 = true;
     if ((p.n >= 96 || (p.n_par == 4 && p.n > 64)) && gemm_cfg != 3 && !p.bn64) {   // merged parity convs need ONE N-tile per parity: 65..128 channels take BN = 128
-      if (kb64) launch_conv_gemm_dma<T, 128, 64>(p, zero_page, stream, deep_max);
-      else launch_conv_gemm_dma<T, 128, 128>(p, zero_page, stream, deep_max);
+      if (kb64) launch_conv_gemm_dma<T, 128, 64>(p, zero_page, stream);
+      else launch_conv_gemm_dma<T, 128, 128>(p, zero_page, stream);
     } else {
-      if (kb64) launch_conv_gemm_dma<T, 64, 64>(p, zero_page, stream, deep_max);
-      else launch_conv_gemm_dma<T, 64, 128>(p, zero_page, stream, deep_max);
+      if (kb64) launch_conv_gemm_dma<T, 64, 64>(p, zero_page, stream);
+      else launch_conv_gemm_dma<T, 64, 128>(p, zero_page, stream);
     }
     return;
   }

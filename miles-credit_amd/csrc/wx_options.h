@@ -9,7 +9,6 @@
 #include <stdint.h>
 
 #include <algorithm>
-#include <climits>
 #include <cstdlib>
 #include <limits>
 
@@ -36,10 +35,6 @@ struct Options {
   int wreg_min_rows = 1024;
   int wreg_max_rows = 4096;
   int gemm_cfg = 0;                  // launch_conv_gemm: 0 automatic, 1 force KB 128 (2 workgroups/CU), 2 force KB 64 (4 workgroups/CU), 3 64-column tiles
-  // launch_conv_gemm_dma, experiment (WX_GEMM_DEEP_TILES=n: launches of <= n tiles on a 4-stage ring, three K stages in flight per CU).
-  // OFF: on the 1-degree grid's deep stages (4 - 48 tiles, 0.57 us per 128-byte K step) it changed nothing (699 vs 702 steps/s) -- a
-  // lone workgroup's K step is bound by its own ds_read -> MFMA chain, not by the stage in flight; those launches are split over K instead
-  int gemm_deep_tiles = 0;
   bool fuse_ln = true;               // LayerNorm / GroupNorm statistics from the producing GEMM's epilogue
   int dbg_flags = 0;                 // experiment bits handed to the kernels' `dbg` fields; any bit set also turns the fused forms off
 
@@ -53,9 +48,6 @@ struct Options {
   int embed_split_ways = 4;          // ... this many ways (>= 2)
   bool embed_tail_split = true;      // big maps: the partly filled last round of tiles as half-chunk workgroups
   bool stat_share = true;            // stages 1-3: every CrossEmbed branch leaves the LayerNorm partials of its channel range
-  // stage-0 CrossEmbed: the branch outside the patch kernel on the side stream, beside it.  OFF: bit-identical and a tie on MI355X (C3 bf16,
-  // same box, four alternations: 8.084 - 8.185 ms/step with it, 8.066 - 8.100 without) -- the patch launch fills the chip, the 88 us GEMM only moves
-  bool embed_side = false;
 
   // ---- attention
   // LN + to_qkv + window attention + to_out + residual as ONE launch (wx_attn_block.h), bf16 engine.  0 never; 1 wherever the kernel
@@ -73,17 +65,9 @@ struct Options {
   bool fuse_out = true;              // ... with the attention's out-projection in front
   bool fuse_qkv = true;              // ... and the next attention's LayerNorm + to_qkv behind
   int ff_min_wgs = 256;              // fused feed-forward only when it yields at least this many workgroups
-  int ff_variant = 0;                // launch_ff_fused tile variant of the plain block (experiment)
-  int ff_dbg = 0;                    // FFParams::dbg (experiment bits)
   bool ff_small_px64 = true;         // C = 128 plain block on 64-pixel tiles when the map yields < 128 tiles of 128 (1-degree stage 1: 21.5 -> 15.5 us)
   int ff_split_max = 8;              // hidden ranges of the split fused FeedForward (0 / 1: off)
   int ff_split_tiles = 32;           // ... pixel tiles, at most
-  // C = 512 (wx_ff.h ff_wide_supported), round 6 -- built, measured, OFF (0): the form is LDS-read-bound and loses both ways.
-  // 1: the chunk blocks are packed (+ 4 MB per FeedForward) and lat-band ranks run the FeedForward of their stage-2 band (2 000 - 4 000
-  // tokens) as the hidden-split fused block + the split-K finish kernel instead of ff1 + split-K ff2 + finish (71 vs 52 us per block);
-  // 2: the unsharded map runs the plain fused block as well (213 vs 104 us per block)
-  int ff_wide = 0;
-  int ff_wide_wgs = 256;             // hidden ranges S: the fewest that yield this many workgroups (<= 8)
   bool ff_split_fused = true;        // split-bf16 precision: the C = 128 / 256 FeedForward as one launch (wx_ff_split.h)
   bool ff_split_256 = true;          // ... at C = 256 too
   bool ff_split_pre = true;          // ... with the attention's out-projection in front (its PRE form)
@@ -92,10 +76,6 @@ struct Options {
 
   // ---- GroupNorm, schedule, graphs
   int gn_fold_max_tiles = 16;        // 12 tiles: 13 -> 9 us; 45 tiles: 13 -> 17 us (the serial fold in every workgroup)
-  // two-stream half-map schedule of the deep stages (Engine::two_stream_ok).  OFF: every form LOSES 1.5-3 % on MI355X (C3 bf16: one
-  // stream 8.06-8.16 ms/step, two streams 8.18-8.39).  0 off; 1 on where it applies; 2 / 3: stages with a dilated / pointwise long window only (probes)
-  int two_stream = 0;
-  int two_stream_prio = INT_MIN;     // probe, side stream priority: INT_MIN (unset) a plain stream; 2 the highest; any other value the lowest
   // WX_GRAPH=1 replays each step from a captured hipGraph.  OFF by default, on measurement (MI355X, 1-degree model, 48 steps): eager
   // 557.7 steps/s (1.79 ms/step, ~170 launches), graph replay 484.8 (2.06 ms): on this stack the cost between two dependent kernels is
   // the device-side dispatch boundary (~1.5 us, MI355X_MICROARCH.md "boundary": eager == hipGraph), not host launch time, so a graph
@@ -143,7 +123,6 @@ struct Options {
     num(o.wreg_min_rows, "WX_WREG_MIN_ROWS");
     num(o.wreg_max_rows, "WX_WREG_MAX_ROWS");
     num(o.gemm_cfg, "WX_GEMM_CFG");
-    num(o.gemm_deep_tiles, "WX_GEMM_DEEP_TILES");
     flag(o.fuse_ln, "WX_NO_LNFUSE", NO);
     num(o.dbg_flags, "WX_DBG");
     flag(o.use_patch, "WX_NO_PATCH", NO);
@@ -155,7 +134,6 @@ struct Options {
     num(o.embed_split_ways, "WX_EMBED_SPLIT", 2);
     flag(o.embed_tail_split, "WX_NO_EMBED_TAIL_SPLIT", NO);
     flag(o.stat_share, "WX_NO_EMBED_STATS", NO);
-    flag(o.embed_side, "WX_EMBED_SIDE");
     num(o.attn_block, "WX_ATTN_BLOCK");
     flag(o.attn_pack2, "WX_NO_ATTN_PACK2", NO);
     flag(o.attn_blk_on, "WX_NO_ATTN_BLK", NO);
@@ -165,21 +143,15 @@ struct Options {
     flag(o.fuse_out, "WX_NO_OUTFUSE", NO);
     flag(o.fuse_qkv, "WX_NO_QKVFUSE", NO);
     num(o.ff_min_wgs, "WX_FF_MIN_WGS");
-    num(o.ff_variant, "WX_FF_VARIANT");
-    num(o.ff_dbg, "WX_FF_DBG");
     flag(o.ff_small_px64, "WX_FF_PX64");
     num(o.ff_split_max, "WX_FF_SPLIT");
     num(o.ff_split_tiles, "WX_FF_SPLIT_TILES");
-    num(o.ff_wide, "WX_FF_WIDE");
-    num(o.ff_wide_wgs, "WX_FF_WIDE_WGS");
     flag(o.ff_split_fused, "WX_NO_FF_SPLIT_FUSED", NO);
     flag(o.ff_split_256, "WX_NO_FF_SPLIT_256", NO);
     flag(o.ff_split_pre, "WX_NO_FF_SPLIT_PRE", NO);
     flag(o.ff_split_post, "WX_NO_FF_SPLIT_POST", NO);
     num(o.ff_split_tw, "WX_FF_SPLIT_TW");
     num(o.gn_fold_max_tiles, "WX_GN_FOLD_TILES");
-    num(o.two_stream, "WX_TWO_STREAM");
-    num(o.two_stream_prio, "WX_TWO_STREAM_PRIO");
     num(o.graph_mode, "WX_GRAPH");
     flag(o.band_split, "WX_BAND_SPLIT");
     flag(o.band_overlap, "WX_BAND_OVERLAP");

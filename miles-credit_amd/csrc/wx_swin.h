@@ -279,7 +279,7 @@ struct SwinStage : SwinStageBase {
       const auto it = split_of.find(w);
       if (it != split_of.end() && K % 32 == 0 && conv_gemm_is_dma<T>(p, zero_page)) { p.split = 1; p.wt = it->second; }
     }
-    launch_conv_gemm<T>(p, zero_page, s, 0, opt.gemm_deep_tiles);
+    launch_conv_gemm<T>(p, zero_page, s, 0);
   }
   void apply(const void* x_in, void* x_out, hipStream_t s) override {
     if (!ready) throw std::runtime_error("swin: call wx_swin_finalize after loading every tensor");

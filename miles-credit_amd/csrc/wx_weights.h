@@ -26,7 +26,7 @@ struct ConvW {          // one repacked GEMM operand in the weight arena
   int64_t wt_kb = -1;   // bf16 engine, 1x1 layers with n % 256 == 0: second copy, k-blocked [cin/32][n][32] (wx_gemm_stream.h)
 };
 struct AttnL { ConvW qkv, vonly, out; int64_t bias_tab = -1, bias_tb = -1; int wsz = 0, kind = 0; };
-struct FFL { ConvW w1, w2; int64_t pack = -1, pack_pre = -1, pack_pp = -1, pack_wide = -1; const AttnL* next = nullptr; };  // pack: fused-block chunk layout (wx_ff.h), T-arena offset; pack_pre: the same preceded by the attention's Wout blocks
+struct FFL { ConvW w1, w2; int64_t pack = -1, pack_pre = -1, pack_pp = -1; const AttnL* next = nullptr; };  // pack: fused-block chunk layout (wx_ff.h), T-arena offset; pack_pre: the same preceded by the attention's Wout blocks
 struct BlockL { AttnL sa; FFL sf; AttnL la; FFL lf; };
 struct PatchW { int64_t wt = -1, bias = -1, wt16 = -1; int n = 0; };   // LDS-patch CrossEmbed branch (wx_embed.h); wt16: split-bf16 mode, offset in the 16-bit patch arena
 struct StageL {
@@ -394,8 +394,6 @@ struct WeightPacker {
         if (prev) f.pack_pre = pack_ff(f, c, 4 * c, &prev->out);
       } else if (ff_plain_supported(c, 4 * c)) {
         f.pack = pack_ff(f, c, 4 * c);
-      } else if (opt.ff_wide && ff_wide_supported(c, 4 * c)) {
-        f.pack_wide = pack_ff(f, c, 4 * c);   // its own field: every rule that reads `pack` (two-stream stages, row windows) stays as it was
       }
     }
     return f;

@@ -422,7 +422,7 @@ class WXEngine:
         return int(v.value)
 
     def info(self) -> dict:
-        return {k: self.query(k) for k in ("two_stream_stages", "launches", "precision", "split_gemms")}
+        return {k: self.query(k) for k in ("launches", "precision", "split_gemms")}
 
     def profile(self, on) -> None:
         """0 off, 1 per kernel class, 2 per kernel class and stage ("gemm_ff1.s2")."""

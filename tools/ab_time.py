@@ -3,7 +3,7 @@
 own environment (the switches are read at wx_create); the arms are timed alternately for several rounds with the benchmark's own loop
 (wx_rollout: forward + tracer fixer + de-normalise + next-input assembly), so box-to-box spread (+-3 %) cancels.
 
-    python tools/ab_time.py --config C3 --arm base: --arm one:WX_TWO_STREAM=0 --rounds 3 --steps 20
+    python tools/ab_time.py --config C3 --arm base: --arm graph:WX_GRAPH=1 --rounds 3 --steps 20
 """
 import argparse
 import os

@@ -374,7 +374,7 @@ int main(int argc, char** argv) {
       std::memset(&g, 0, sizeof(g));
       g.a = x; g.lda = c.C; g.w = w; g.M = M; g.N = N; g.K = K; g.bias = bias; g.out = y1; g.out_ld = N; g.sink = sink; g.xcd_part = 1;
       g.gn_out = g1; g.in_h = c.H; g.in_w = c.W; g.cin = c.C; g.kh = g.kw = 3; g.pad_y = g.pad_x = 1;
-      auto run_prod = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0, 0); };
+      auto run_prod = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0); };
       g.xcd_part = getenv("WX_XCD_PART") ? atoi(getenv("WX_XCD_PART")) : 1;
 
       auto run_8p = [&] { launch_gemm8p_conv(g, st); };
@@ -480,7 +480,7 @@ int main(int argc, char** argv) {
       g.scat_w = c.W; g.cout = c.cout;
       Gemm8pParams gf = g;
       gf.xcd_part = 0;
-      auto run_prod = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0, 0); };
+      auto run_prod = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0); };
       auto run_5x = [&] { launch_gemm8p_convt2<5>(g, st); };
       auto run_8f = [&] { launch_gemm8p_convt2<8>(gf, st); };
       WX_HIP(hipMemset(y0, 0, on * 2));

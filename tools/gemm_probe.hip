@@ -74,13 +74,13 @@ int main(int argc, char** argv) {
 
   hipStream_t st;
   WX_HIP(hipStreamCreate(&st));
-  for (int i = 0; i < 3; ++i) launch_conv_gemm<elem_t>(p, zero, st, cfg, 0);
+  for (int i = 0; i < 3; ++i) launch_conv_gemm<elem_t>(p, zero, st, cfg);
   hipEvent_t e0, e1;
   WX_HIP(hipEventCreate(&e0));
   WX_HIP(hipEventCreate(&e1));
   const int reps = 20;
   WX_HIP(hipEventRecord(e0, st));
-  for (int i = 0; i < reps; ++i) launch_conv_gemm<elem_t>(p, zero, st, cfg, 0);
+  for (int i = 0; i < reps; ++i) launch_conv_gemm<elem_t>(p, zero, st, cfg);
   WX_HIP(hipEventRecord(e1, st));
   WX_HIP(hipStreamSynchronize(st));
   float ms;
@@ -96,7 +96,7 @@ int main(int argc, char** argv) {
   unsigned long long* tr = (unsigned long long*)dalloc(blocks * 128);
   WX_HIP(hipMemset(tr, 0, blocks * 128));
   p.trace = tr;
-  launch_conv_gemm<elem_t>(p, zero, st, cfg, 0);
+  launch_conv_gemm<elem_t>(p, zero, st, cfg);
   WX_HIP(hipStreamSynchronize(st));
   std::vector<unsigned long long> h(blocks * 16);
   WX_HIP(hipMemcpy(h.data(), tr, blocks * 128, hipMemcpyDeviceToHost));

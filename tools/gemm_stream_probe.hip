@@ -136,7 +136,7 @@ int main(int argc, char** argv) {
     q.stat_out = res ? so1 : nullptr; q.stat_slots = 2 * (N / 256);
     q.res = res ? rs : nullptr; q.res_ld = N; q.out = y1; q.out_ld = N; q.sink = sink;
 
-    auto run_old = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0, 0); };
+    auto run_old = [&] { launch_conv_gemm<uint16_t>(p, zero, st, 0); };
     auto run_53 = [&] { launch_gemm_stream<5, 3>(q, s.variant, st); };
     auto run_52 = [&] { launch_gemm_stream<5, 2>(q, s.variant, st); };
     auto run_43 = [&] { launch_gemm_stream<4, 3>(q, s.variant, st); };
