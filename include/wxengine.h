@@ -67,7 +67,10 @@ typedef struct wx_config {
   int32_t image_height, image_width;
   int32_t frames, output_frames;
   int32_t channels, surface_channels, input_only_channels, output_only_channels, levels;
-  int32_t dim[4], depth[4], dim_head;   /* dim_head: 32 (reference default, tuned kernels) or 64 / 96 / 128 (general attention kernel); must divide every dim[s] */
+  int32_t dim[4], depth[4], dim_head;   /* dim_head: 32 (reference default, tuned kernels) or 64 / 128 (general attention kernel); must divide every dim[s].
+                                         * 96 exists for wx_winattn_create / wx_swin_create only: no width wx_create takes is a multiple of it.
+                                         * dim[s]: a multiple of 32 that doubles per stage and that the LayerNorm kernels take -- 32 / 64 / 128 at
+                                         * stage 0 (dim[3] <= 1024), and 256 (dim[3] = 2048) with WX_PREC_BF16; anything else is WX_ERR_INVALID at wx_create */
   int32_t global_window_size[4], local_window_size[4];
   int32_t n_embed_kernels[4];       /* branches per stage (<= 4) */
   int32_t embed_kernels[4][4];      /* cross_embed_kernel_sizes */
@@ -416,6 +419,9 @@ typedef struct wx_kernel_stat {
  *   "launches"           kernel launches of the last forward
  *   "gemm8p_launches"    ... of which ran on the eight-phase kernel (wx_gemm8p.h: the decoder's deep-K convolutions, round 6)
  *   "attn_blk"           attention sub-blocks of the last forward whose q|k|v and attention output travelled k-blocked (round 6)
+ *   "attn_nkf_mask"      bit n set: the last forward launched window_attn_kernel with NKF == n key fragments of 16 tokens (n in 1, 2, 4,
+ *                        7, 8, 10, 12, 14, 16: windows of <= 16, 32, 64, 112, 128, 160, 192, 224, 256 tokens)
+ *   "attn_block_nkf_mask" ... attn_block_kernel (the one-launch attention sub-block, bf16) with NKF == n (n in 1, 2, 4, 7, 8)
  *   "precision"          the wx_config precision the engine was created with
  *   "split_gemms"        GEMM launches of the last forward that ran split-bf16 arithmetic (WX_PREC_FP32_SPLIT)
  *   "ff_split_fused"     ... of whose FeedForward sub-blocks ran as ONE launch (wx_ff_split.h; each counts two split GEMMs), and of those

@@ -46,6 +46,9 @@ extern "C" {
 int wx_create(const wx_config* cfg, int device, wx_handle* out) {
   return guarded([&] {
     if (!cfg || !out) throw wx::ConfigError("wx_create: null argument");
+    if (cfg->precision != WX_PREC_FP32 && cfg->precision != WX_PREC_FP32_SPLIT && cfg->precision != WX_PREC_BF16)
+      throw wx::ConfigError("wx_create: unknown precision");
+    { const wx::ModelSpec check(*cfg); }   // the config's own faults first: they need no device to be told
     need_device(device, "wx_create");
     WX_HIP(hipSetDevice(device));
     std::unique_ptr<wx_engine> h(new wx_engine);
@@ -342,6 +345,8 @@ int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bi
     if (d->kind == 1 && wsx != d->wsz_y) throw wx::ConfigError("winattn: dilated windows must be square");
     if (d->kind == 3 && (d->shift_y < 0 || d->shift_y >= d->wsz_y || d->shift_x < 0 || d->shift_x >= wsx)) throw wx::ConfigError("winattn: shift must lie inside the window");
     const int N = d->wsz_y * wsx;
+    if (wx::attn_nkf_tokens(N) > 0 && !wx::window_attn_lds_ok(d->precision == WX_PREC_BF16 ? 2 : 4, wx::attn_nkf_tokens(N), d->head_dim))
+      throw wx::ConfigError("winattn: head_dim x window size exceeds the kernel's 160 KB of LDS (fp32: head_dim 96 / 128 take windows of at most 64 tokens)");
     const int nkf = wx::attn_nkf_tokens(N);
     if (nkf < 0 || nkf > 8) throw wx::ConfigError("winattn: at most 128 tokens per window");
     if (n_bias_heads != 0 && n_bias_heads != 1 && n_bias_heads != d->heads) throw wx::ConfigError("winattn: bias for 0, 1 or `heads` heads");

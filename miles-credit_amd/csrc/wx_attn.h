@@ -334,7 +334,10 @@ __global__ __launch_bounds__(256, attn_min_waves(NKF, DH, int(sizeof(T)), SW)) v
         const int b = t >> 2, r = t & 3, by = b / (B2W / 2), bx = b - by * (B2W / 2);
         ty = 2 * by + (r >> 1); tx = 2 * bx + (r & 1);
       }
-      s_bk[t] = t < N ? 4 * (ty * side + tx) : -2048;
+      // a padded key: 2048 bytes past the query's own entry, where the table holds -1e30 -- for windows of up to 11 x 11 (NKF <= 8:
+      // 2 w (w - 1) + 512 >= (2 w - 1)^2 and 4 w (w - 1) + 512 < TBN).  Larger windows leave no such offset in a 1024-entry table:
+      // their padded keys read entry 0 and the lookup below writes -1e30 itself
+      s_bk[t] = t < N ? 4 * (ty * side + tx) : (NKF > 8 ? 0 : -2048);
     }
   }
   if constexpr (!SPLIT) attn_lds_barrier();
@@ -627,6 +630,12 @@ __global__ __launch_bounds__(256, attn_min_waves(NKF, DH, int(sizeof(T)), SW)) v
           const int4 bk = *reinterpret_cast<const int4*>(s_bk + j * 16 + g * 4);
           bt[j] = make_float4(*reinterpret_cast<const float*>(tbb - bk.x), *reinterpret_cast<const float*>(tbb - bk.y),
                               *reinterpret_cast<const float*>(tbb - bk.z), *reinterpret_cast<const float*>(tbb - bk.w));
+          if constexpr (NKF > 8) {   // 12 x 12 .. 15 x 15 windows: the padded keys of the partly filled fragments (see s_bk)
+            const int k0 = j * 16 + g * 4;
+            if (k0 + 3 >= N)
+              bt[j] = make_float4(k0 < N ? bt[j].x : -1.0e30f, k0 + 1 < N ? bt[j].y : -1.0e30f, k0 + 2 < N ? bt[j].z : -1.0e30f,
+                                  k0 + 3 < N ? bt[j].w : -1.0e30f);
+          }
         }
       }
     }
@@ -869,6 +878,12 @@ inline int attn_nkf_tokens(int n) {
   if (n <= 224) return 14;
   if (n <= 256) return 16;
   return -1;
+}
+// dynamic LDS of window_attn_kernel<T, NKF, false, BT, DH> (launch_window_attn_n: four waves, each with its V image) against the 160 KB
+// a workgroup can ask for: fp32 storage with wide heads stops at 64 tokens (head_dim 128), 96 tokens never (head_dim 96: 64 tokens)
+inline bool window_attn_lds_ok(int elem, int nkf, int head_dim, bool bias_table = false) {
+  const int cols = elem == 2 ? ((nkf + 1) / 2) * 32 : nkf * 16 + 4;
+  return (size_t)4 * head_dim * cols * elem + (bias_table ? 1024 * 4 + nkf * 16 * 4 : 0) + (size_t)nkf * 16 * 4 <= (size_t)160 * 1024;
 }
 inline int attn_pack(int wsz) { const int n = wsz * wsz; return n <= 8 ? 16 / n : 1; }
 inline int attn_nkf(int wsz) { return attn_nkf_tokens(wsz * wsz * attn_pack(wsz)); }

@@ -21,9 +21,11 @@ struct HipError : std::runtime_error {
 #define WX_HIP(expr)                                                                            \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess)                                                                       \
+    if (_e != hipSuccess) {                                                                     \
+      (void)hipGetLastError(); /* or the next launch's check reports this failure as its own */ \
       throw ::wx::HipError(std::string(#expr) + " failed: " + hipGetErrorString(_e) + " at " + \
                            __FILE__ + ":" + std::to_string(__LINE__));                          \
+    }                                                                                           \
   } while (0)
 
 // ---- scalar conversions ---------------------------------------------------

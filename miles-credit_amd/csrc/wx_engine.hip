@@ -404,12 +404,16 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   int64_t n_ff_split_post = 0;       // ... of which also with the next to_qkv behind (four GEMMs)
   int64_t n_ff_split_fused = 0;      // ... of which FeedForward sub-blocks in one launch (wx_ff_split.h; counted as two GEMMs above)
   int64_t n_launches = 0;            // timed() calls of the last forward (one per kernel launch or launch + finish pair)
+  int64_t attn_nkf_mask = 0;         // bit n: the last forward launched window_attn_kernel with NKF == n key fragments
+  int64_t attn_block_nkf_mask = 0;   // ... attn_block_kernel with NKF == n
   bool query(const std::string& key, int64_t* v) override {
     if (key == "launches") { *v = n_launches; return true; }
     if (key == "precision") { *v = sizeof(T) == 2 ? WX_PREC_BF16 : (split_mma ? WX_PREC_FP32_SPLIT : WX_PREC_FP32); return true; }
     if (key == "split_gemms") { *v = n_split_gemms; return true; }
     if (key == "gemm8p_launches") { *v = n_gemm8p; return true; }
     if (key == "attn_blk") { *v = n_attn_blk; return true; }
+    if (key == "attn_nkf_mask") { *v = attn_nkf_mask; return true; }
+    if (key == "attn_block_nkf_mask") { *v = attn_block_nkf_mask; return true; }
     if (key == "ff_split_fused") { *v = n_ff_split_fused; return true; }
     if (key == "ff_split_pre") { *v = n_ff_split_pre; return true; }
     if (key == "ff_split_post") { *v = n_ff_split_post; return true; }
@@ -769,7 +773,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     constexpr int VEC = 16 / (int)sizeof(T);
     const int pieces = c / VEC;
     const int lpt = pieces >= 64 ? 64 : pieces;
-    if (pieces / lpt > 4 || (lpt & (lpt - 1))) throw ConfigError("LayerNorm width unsupported (need power-of-two pieces, C <= 1024 fp32)");
+    if (!ln_width_ok(c, (int)sizeof(T))) throw StateError("ln_stats: a width ModelSpec::derive() should have refused");
     const int pix_per_block = 4 * (64 / lpt);
     timed("ln_stats", 0.0, (double)m * c * sizeof(T), [&] {
       hipLaunchKernelGGL(ln_stats_kernel<T>, dim3(cdiv(m, pix_per_block)), dim3(256), 0, cur_stream, x, ld, c, m, 1e-5f, rowstat);
@@ -815,6 +819,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         bp.pack = a.wsz == 2 ? 4 : 1;
         const double n = (double)a.wsz * a.wsz;
         bp.stat_out = opt.fuse_ln && !opt.dbg_flags ? stat_dst(m, c / 32) : nullptr;
+        attn_block_nkf_mask |= (int64_t)1 << attn_nkf_tokens(a.wsz * a.wsz * bp.pack);
         timed("attn_block", 8.0 * m * c * c + 4.0 * m * n * c, 2.0 * m * c * sizeof(T), [&] { launch_attn_block(c, bp, cur_stream); });
         stat_tiles_ready = bp.stat_out ? c / 32 : 0;
         capture(dbg_name, x, h, w, c, ld, w);
@@ -844,6 +849,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       p.mma3 = split_mma ? 1 : 0;
       p.blk = blk == KBlk::attn ? 1 : 0;
       const double n = (double)a.wsz * a.wsz;
+      attn_nkf_mask |= (int64_t)1 << attn_nkf_tokens(a.wsz * a.wsz * p.pack);
       timed("window_attn", 4.0 * m * n * c, 4.0 * m * c * sizeof(T), [&] {
         if (cfg.dim_head == 32) launch_window_attn<T>(p, cur_stream, opt.attn_split, opt.attn_no_b2);
         else launch_window_attn_any<T>(p, cfg.dim_head, cur_stream);   // [NP][NP] bias table shared by the heads (bias_head_stride 0)
@@ -1012,7 +1018,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // -> gn_acc[2c] (sum, sum sq) in fp64; tiles > 0: the producing conv's epilogue left that many per-tile (sum, sum sq) in gnpart
   void gn_local_stats(const T* x, int c, int64_t m, int tiles) {
     constexpr int VEC = 16 / (int)sizeof(T);
-    if (c / VEC > 256) throw ConfigError("GroupNorm width unsupported");
+    if (!gn_width_ok(c, (int)sizeof(T))) throw StateError("gn_stats: a width ModelSpec::derive() should have refused");
     if (tiles > 0) {  // just fold them
       timed("gn_stats", 0.0, (double)tiles * c * 8.0, [&] {
         hipLaunchKernelGGL(gn_fold_partials_kernel, dim3(c), dim3(256), 0, cur_stream, gnpart, tiles, c, gn_acc);
@@ -1291,6 +1297,8 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     n_ff_split_pre = 0;
     n_ff_split_post = 0;
     n_launches = 0;
+    attn_nkf_mask = 0;
+    attn_block_nkf_mask = 0;
     // a1: pack + earth halo
     pack_input(x_item, xin, xin_planar, Hp + 2 * halo, 0, Hp, halo, 0, cfg.image_height);
     capture("pad", xin + ((int64_t)halo * (Wp + 2 * halo) + halo) * cpad0, Hp, Wp, C_in, cpad0, Wp + 2 * halo);
@@ -1374,7 +1382,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       WX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_mark_device(attr_done_mask);
     }
-    if (lds > 160 * 1024) throw ConfigError("too many output channels for the tail kernel");
+    if (!tail_channels_ok(C_out)) throw StateError("tail: a channel count ModelSpec::derive() should have refused");
     const double plane = (double)Ho * Wo * C_out;
     timed("tail", 0.0, plane * (2.0 * sizeof(T) + 4.0 * ((y ? 1 : 0) + (y_phys ? 1 : 0)) + (x_next ? 4.0 : 0.0)), [&] {
       hipLaunchKernelGGL(tail_kernel<T>, dim3(cdiv(Wo, 64), Ho), dim3(256), lds, cur_stream, p);

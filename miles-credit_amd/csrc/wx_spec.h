@@ -27,6 +27,22 @@ struct HostTensor {
   int64_t numel() const { int64_t n = 1; for (auto s : shape) n *= s; return n; }
 };
 
+// ------------------------------------------------------------------ shape limits of the kernels, known from the config alone
+// `elem`: bytes per stored activation element (4: WX_PREC_FP32 / WX_PREC_FP32_SPLIT, 2: WX_PREC_BF16).  ModelSpec::derive() refuses a
+// config that misses one of them, so wx_create returns either an engine whose forward runs or WX_ERR_INVALID with the reason.
+// LayerNorm (ln_stats_kernel, wx_elem.h): min(64, pieces) lanes share a row of C / (16 / elem) 16-byte pieces -- a power of two of
+// them (the butterfly reduction), every lane the same number of pieces, at most four
+inline bool ln_width_ok(int c, int elem) {
+  const int vec = 16 / elem;
+  if (c < vec || c % vec) return false;
+  const int pieces = c / vec, lpt = pieces >= 64 ? 64 : pieces;
+  return !(lpt & (lpt - 1)) && pieces % lpt == 0 && pieces / lpt <= 4;
+}
+// GroupNorm (gn_stats_kernel): one thread per 16-byte piece of a row, 256 threads
+inline bool gn_width_ok(int c, int elem) { return c / (16 / elem) <= 256; }
+// tail kernel: a [C_out][65] fp32 tile in 160 KB of LDS
+inline bool tail_channels_ok(int c_out) { return (size_t)c_out * 65 * sizeof(float) <= (size_t)160 * 1024; }
+
 struct ModelSpec {
   explicit ModelSpec(const wx_config& c) : cfg(c) {
     derive();
@@ -43,10 +59,12 @@ struct ModelSpec {
     if (cfg.abi_version != WX_ABI_VERSION) throw ConfigError("wx_config.abi_version mismatch");
     if (cfg.frames < 1 || cfg.output_frames < 1) throw ConfigError("frames/output_frames must be >= 1");
     // dim_head (crossformer.py:372-401, a constructor kwarg; every YAML of the reference leaves the default 32): 32 runs the tuned kernels;
-    // 64 / 96 / 128 run the general-head-dimension attention kernel of the Swin mode (launch_window_attn_any) between the plain GEMMs --
+    // 64 / 128 run the general-head-dimension attention kernel of the Swin mode (launch_window_attn_any) between the plain GEMMs --
     // the attention block kernel and the fused FeedForward's to_out / to_qkv variants are built around 32-wide heads and stay off
-    if (cfg.dim_head != 32 && cfg.dim_head != 64 && cfg.dim_head != 96 && cfg.dim_head != 128)
-      throw ConfigError("dim_head must be 32, 64, 96 or 128");
+    if (cfg.dim_head == 96)   // a width with LayerNorm's power-of-two pieces (32, 64, 128, ...) is never a multiple of 96
+      throw ConfigError("dim_head 96 is for wx_winattn_create / wx_swin_create only: no stage width the LayerNorm kernels take is a multiple of 96");
+    if (cfg.dim_head != 32 && cfg.dim_head != 64 && cfg.dim_head != 128)
+      throw ConfigError("dim_head must be 32, 64 or 128");
     for (int s = 0; s < 4; ++s)
       if (cfg.dim[s] % cfg.dim_head) throw ConfigError("every stage width must be a multiple of dim_head");
     if (cfg.dim_head != 32)   // launch_window_attn_dh: windows of at most 128 tokens
@@ -95,6 +113,20 @@ struct ModelSpec {
       if (sh[s] != 2 * sh[s + 1] || sw[s] != 2 * sw[s + 1]) throw ConfigError("stage maps must halve (decoder skip concat)");
       if (cfg.dim[s + 1] != 2 * cfg.dim[s]) throw ConfigError("dim must double per stage (decoder skip widths)");
     }
+    // the widths the kernels take (thrown by the first forward / by finalize before: LayerNorm, GroupNorm, decoder, tail)
+    const int elem = cfg.precision == WX_PREC_BF16 ? 2 : 4;
+    for (int s = 0; s < 4; ++s)
+      if (!ln_width_ok(cfg.dim[s], elem)) throw ConfigError("LayerNorm width unsupported (need power-of-two pieces, C <= 1024 fp32)");
+    for (int i = 1; i <= 3; ++i) {   // up block i: dim[3] / 2^i output channels
+      const int c = cfg.dim[3] >> i;
+      if (c % 32) throw ConfigError("decoder widths must be multiples of 32");
+      if (!gn_width_ok(c, elem)) throw ConfigError("GroupNorm width unsupported");
+    }
+    if (!tail_channels_ok(C_out)) throw ConfigError("too many output channels for the tail kernel");
+    for (int s = 0; s < 4; ++s)
+      for (int wsz : {cfg.local_window_size[s], cfg.global_window_size[s]})
+        if (wsz > 1 && !window_attn_lds_ok(elem, attn_nkf(wsz), cfg.dim_head, false))
+          throw ConfigError("window attention: dim_head x window size exceeds the kernel's 160 KB of LDS (fp32 storage: dim_head 128 takes windows of at most 64 tokens)");
     cpad0 = ((C_in + 31) / 32) * 32;
     Hd = sh[3] * 16; Wd = sw[3] * 16;
     Hu = Hd - (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);

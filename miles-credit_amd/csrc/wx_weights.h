@@ -511,7 +511,7 @@ struct WeightPacker {
       const std::string p = "up_block" + std::to_string(i + 1);
       UpL u;
       u.cin = upc[i][0]; u.cout = upc[i][1];
-      if (u.cout % 32) throw ConfigError("decoder widths must be multiples of 32");
+      if (u.cout % 32) throw StateError("decoder: a width ModelSpec::derive() should have refused");
       if (cfg.arch == WX_ARCH_WXFORMER) {
         // sub-pixel conv: reference channel c*4+q feeds sub-pixel q of channel c (PixelShuffle); rows reordered
         // to q*cout + c so the ConvT-style scatter epilogue (out_mode 1) performs the shuffle

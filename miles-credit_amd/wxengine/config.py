@@ -63,7 +63,8 @@ class WXConfig:
 
     # ------------------------------------------------------------------ #
     @classmethod
-    def from_model_conf(cls, model_conf: Dict, arch: str = "crossformer") -> "WXConfig":
+    def from_model_conf(cls, model_conf: Dict, arch: str = "crossformer", precision: Optional[str] = None) -> "WXConfig":
+        """precision ("fp32" / "fp32s" / "bf16"): also apply the limits of that storage type (check_precision)."""
         mc = dict(model_conf)
         mc.pop("type", None)
         pad = mc.pop("padding_conf", None) or {"activate": False}
@@ -90,6 +91,8 @@ class WXConfig:
             c.pad_lat = _tup(pl, 2) if not isinstance(pl, int) else (pl, pl)
             c.pad_lon = _tup(pw, 2) if not isinstance(pw, int) else (pw, pw)
         c.validate()
+        if precision is not None:
+            c.check_precision(precision)
         return c
 
     # ------------------------------------------------------------------ #
@@ -117,8 +120,11 @@ class WXConfig:
             for kind, wsz in (("local", self.local_window_size[s]), ("global", self.global_window_size[s])):
                 if h % wsz or w % wsz:
                     raise ValueError(f"stage {s} map {h}x{w} not divisible by {kind} window {wsz}")
-        if self.dim_head not in (32, 64, 96, 128):
-            raise ValueError("dim_head must be 32 (the reference default: the tuned kernels), 64, 96 or 128 (general attention kernel)")
+        if self.dim_head == 96:
+            raise ValueError("dim_head 96 is for the standalone window attention / Swin operators only: no stage width the "
+                             "LayerNorm kernels take is a multiple of 96")
+        if self.dim_head not in (32, 64, 128):
+            raise ValueError("dim_head must be 32 (the reference default: the tuned kernels), 64 or 128 (general attention kernel)")
         for d in self.dim:
             if d % self.dim_head:
                 raise ValueError("dim must be a multiple of dim_head")
@@ -132,6 +138,43 @@ class WXConfig:
                 raise ValueError(f"stage {s} map {hw[s]} is not 2x stage {s + 1} map {hw[s + 1]} (decoder skip concat)")
         if tuple(self.dim[s + 1] for s in range(3)) != tuple(2 * self.dim[s] for s in range(3)):
             raise ValueError("dim must double per stage (decoder skip widths)")
+        # the widths the kernels take in at least one precision (csrc/wx_spec.h ModelSpec::derive(); check_precision() narrows it)
+        self.check_precision("bf16")
+
+    def check_precision(self, precision: str):
+        """The shape limits that depend on the storage type (4-byte elements for "fp32" / "fp32s", 2-byte for "bf16"): the mirror of
+        ln_width_ok / gn_width_ok / tail_channels_ok in csrc/wx_spec.h, with wx_create's wording."""
+        if precision not in ("fp32", "fp32s", "bf16"):
+            raise ValueError(f"unknown precision {precision!r}")
+        vec = 8 if precision == "bf16" else 4
+
+        def ln_ok(c):
+            if c < vec or c % vec:
+                return False
+            pieces = c // vec
+            lpt = min(64, pieces)
+            return lpt & (lpt - 1) == 0 and pieces % lpt == 0 and pieces // lpt <= 4
+        for c in self.dim:
+            if c % 32:
+                raise ValueError("dim must be a multiple of 32")
+            if not ln_ok(c):
+                raise ValueError("LayerNorm width unsupported (need power-of-two pieces, C <= 1024 fp32)")
+        for i in (1, 2, 3):
+            c = self.dim[-1] >> i
+            if c % 32:
+                raise ValueError("decoder widths must be multiples of 32")
+            if c // vec > 256:
+                raise ValueError("GroupNorm width unsupported")
+        if self.output_channels * 65 * 4 > 160 * 1024:
+            raise ValueError("too many output channels for the tail kernel")
+        elem = 16 // vec
+        for w in tuple(self.local_window_size) + tuple(self.global_window_size):
+            n = w * w * (16 // (w * w) if w * w <= 8 else 1)
+            nkf = next(k for k, cap in ((1, 16), (2, 32), (4, 64), (7, 112), (8, 128), (10, 160), (12, 192), (14, 224), (16, 256)) if n <= cap)
+            cols = ((nkf + 1) // 2) * 32 if elem == 2 else nkf * 16 + 4
+            if w > 1 and 4 * self.dim_head * cols * elem + nkf * 64 > 160 * 1024:
+                raise ValueError("window attention: dim_head x window size exceeds the kernel's 160 KB of LDS (fp32 storage: dim_head 128 "
+                                 "takes windows of at most 64 tokens)")
 
     # ------------------------------------------------------------------ #
     @property

@@ -111,3 +111,86 @@ def gen2loop_batches(cfg, n_steps=3, seed=77):
     ic = {"input": {"era5": {k: field(nl, 1.5, 0.3) for k, nl in inp}}}
     frcs = [{"input": {"era5": {k: field(1) for k, _ in inp[-2:]}}} for _ in range(n_steps - 1)]
     return ic, frcs, mean, std
+
+
+# ------------------------------------------------------------------ acceptance classes of wx_create
+# One tiny config per class of model that ModelSpec::derive() (csrc/wx_spec.h) / WXConfig.validate() accept and that the named configs
+# do not span (tests/test_accepted_configs_gpu.py runs each against the fp64 oracle; tests/test_oracle_vs_reference.py pins the oracle
+# itself to the reference at the same shapes).  Strides [2, 2, 2, 2]: the stage maps are (8, 4, 2, 1) x (h3, w3).
+#   W  window sides 6, 7, 9, 11 - 15 at dim_head 32: a swept side w sits on maps of >= 2 windows per axis, as the local AND the global
+#      window of stages 0 - 2 (widths 32 / 64 / 128); the 256-wide stage 3 takes w again where the map allows (6, 7), else a small one
+#   H  dim_head 64 / 128 (the general-head-width kernel) at 36 / 49, 81 and 121 tokens
+#   E  CrossEmbed kernel sets    F  interp / use_spectral_norm off, also with the PixelShuffle and upsample_v_conv decoders
+# `nkf`: the key-fragment counts (16 tokens each, attn_nkf_tokens in csrc/wx_attn.h) the class claims to run; `embed`: the launches per
+# forward that csrc/wx_weights.h:run() / Engine::cross_embed must choose, as {profile(2) kernel class: launches}.
+_SMALL = dict(frames=1, channels=2, surface_channels=2, input_only_channels=2, output_only_channels=1, levels=2, patch_width=1,
+              patch_height=1, cross_embed_kernel_sizes=[[4, 8, 16, 32], [2, 4], [2, 4], [2, 4]], cross_embed_strides=[2, 2, 2, 2],
+              dim=[32, 64, 128, 256], depth=[1, 1, 1, 1], interp=True, use_spectral_norm=True)
+_T0_PAD = dict(image_height=37, image_width=72, padding_conf=dict(activate=True, mode="earth", pad_lat=[6, 6], pad_lon=[12, 12]),
+               global_window_size=[4, 2, 2, 1], local_window_size=3)     # padded 49 x 96 -> 24 x 48 ... 3 x 6; decoder output 36 x 72
+
+
+def _sq(h3, lw, gw, **kw):
+    return dict(_SMALL, image_height=16 * h3, image_width=16 * h3, local_window_size=list(lw), global_window_size=list(gw), **kw)
+
+
+ACCEPTED_CONFIGS = {
+    # ---- W (stage maps 8 h3, 4 h3, 2 h3, h3)
+    "W6_12": dict(cls="W", swept=(6, 12), nkf={4, 10}, mc=_sq(12, (12, 6, 12, 6), (6, 12, 6, 6))),     # 36 of 64 tokens; 144 of 160
+    "W7_14": dict(cls="W", swept=(7, 14), nkf={4, 14}, mc=_sq(14, (14, 7, 14, 7), (7, 14, 7, 7))),     # 49 of 64; 196 of 224
+    "W9": dict(cls="W", swept=(9,), nkf={1, 7}, mc=_sq(9, (9, 9, 9, 3), (9, 9, 9, 3))),                # 81 of 112 (and 9 of 16 at stage 3)
+    "W11": dict(cls="W", swept=(11,), nkf={8}, mc=_sq(11, (11, 11, 11, 1), (11, 11, 11, 1))),          # 121 of 128
+    "W13": dict(cls="W", swept=(13,), nkf={12}, mc=_sq(13, (13, 13, 13, 1), (13, 13, 13, 1))),         # 169 of 192
+    "W15": dict(cls="W", swept=(15,), nkf={2, 16}, mc=_sq(15, (15, 15, 15, 5), (15, 15, 15, 5))),      # 225 of 256 (and 25 of 32 at stage 3)
+    # ---- H
+    "H64w6": dict(cls="H", swept=(6,), nkf={4}, mc=_sq(6, (6, 6, 6, 3), (6, 6, 6, 3), dim=[64, 128, 256, 512], dim_head=64)),
+    "H64w9": dict(cls="H", swept=(9,), nkf={7}, mc=_sq(9, (9, 9, 9, 3), (9, 9, 9, 3), dim=[64, 128, 256, 512], dim_head=64)),
+    "H64w11": dict(cls="H", swept=(11,), nkf={8}, mc=_sq(11, (11, 11, 11, 1), (11, 11, 11, 1), dim=[64, 128, 256, 512], dim_head=64)),
+    "H128w7": dict(cls="H", swept=(7,), nkf={4}, mc=_sq(7, (7, 7, 7, 1), (7, 7, 7, 1), dim=[128, 256, 512, 1024], dim_head=128)),
+    # 128-wide heads in fp32 storage stop at 64 tokens (four 128 x (16 NKF + 4) fp32 V images pass 160 KB of LDS): bf16 only, and
+    # REJECTED_CONFIGS holds the fp32 side
+    "H128w9": dict(cls="H", precs=("bf16",), swept=(9,), nkf={7}, mc=_sq(9, (9, 9, 9, 3), (9, 9, 9, 3), dim=[128, 256, 512, 1024], dim_head=128)),
+    "H128w11": dict(cls="H", precs=("bf16",), swept=(11,), nkf={8}, mc=_sq(11, (11, 11, 11, 1), (11, 11, 11, 1), dim=[128, 256, 512, 1024], dim_head=128)),
+    # ---- E (4 x 4 stage-3 map; windows as ODD_CONFIGS["w2"])
+    "E1": dict(cls="E", mc=_sq(4, (2, 2, 2, 2), (4, 4, 2, 2), cross_embed_kernel_sizes=[[4], [2], [2], [2]]),
+               embed={"embed_patch": 0, "gemm_embed.s0": 1, "gemm_embed.s1": 1, "gemm_embed.s2": 1, "gemm_embed.s3": 1}),
+    "E3": dict(cls="E", mc=_sq(4, (2, 2, 2, 2), (4, 4, 2, 2), cross_embed_kernel_sizes=[[4, 8, 16, 32], [2, 4, 8], [2, 4, 8], [2, 4, 8]]),
+               embed={"embed_patch": 1, "gemm_embed.s0": 0, "gemm_embed.s1": 1, "gemm_embed.s2": 1, "gemm_embed.s3": 1}),   # merged as three
+    "Eno4": dict(cls="E", mc=_sq(4, (2, 2, 2, 2), (4, 4, 2, 2), cross_embed_kernel_sizes=[[8, 16, 32], [2, 4], [2, 4], [2, 4]]),
+                 embed={"embed_patch": 1, "gemm_embed.s0": 0, "gemm_embed.s1": 1}),
+    "Eno32": dict(cls="E", mc=_sq(4, (2, 2, 2, 2), (4, 4, 2, 2), cross_embed_kernel_sizes=[[4, 16], [2, 4], [2, 4], [2, 4]]),
+                  embed={"embed_patch": 0, "gemm_embed.s0": 2, "gemm_embed.s1": 1}),
+    # stage-0 stride 4: 128 x 128 image -> 32 / 16 / 8 / 4 maps, decoder output 64 x 64, resized to the image by interp
+    "Es4": dict(cls="E", mc=dict(_sq(8, (2, 2, 2, 2), (4, 4, 2, 2)), cross_embed_strides=[4, 2, 2, 2]),
+                embed={"embed_patch": 0, "gemm_embed.s0": 4, "gemm_embed.s1": 1}),
+    # ---- F
+    "Fi_eq": dict(cls="F", mc=_sq(4, (2, 2, 2, 2), (4, 4, 2, 2), interp=False)),                       # decoder output == image
+    "Fi_ne": dict(cls="F", mc=dict(_SMALL, **_T0_PAD, interp=False)),                                 # 36 x 72 out of a 37 x 72 image
+    "Fsn": dict(cls="F", mc=dict(_SMALL, **_T0_PAD, use_spectral_norm=False)),
+    "Fw": dict(cls="F", arch="wxformer", mc=dict(_SMALL, **_T0_PAD, interp=False, use_spectral_norm=False)),
+    "Fu": dict(cls="F", mc=dict(_SMALL, **_T0_PAD, interp=False, use_spectral_norm=False, upsample_v_conv=True)),
+}
+
+
+def accepted_precisions(name):
+    return ACCEPTED_CONFIGS[name].get("precs", ("fp32", "fp32s", "bf16"))
+
+
+def accepted_config(name, precision=None):
+    from wxengine.config import WXConfig
+    e = ACCEPTED_CONFIGS[name]
+    return WXConfig.from_model_conf(e["mc"], arch=e.get("arch", "crossformer"), precision=precision)
+
+
+# what wx_create must refuse when the engine is created (tests/test_abi_cpu.py): (model conf, precision, words of the reason)
+REJECTED_CONFIGS = {
+    "dim96": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), dim=[96, 192, 384, 768]), "bf16", "LayerNorm width unsupported"),
+    "dim2048_fp32": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), dim=[256, 512, 1024, 2048]), "fp32", "LayerNorm width unsupported"),
+    "dim2048_fp32s": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), dim=[256, 512, 1024, 2048]), "fp32s", "LayerNorm width unsupported"),
+    # 72 of 288 / 4 fp32 pieces: one per lane would leave eight unread (the statistics were silently wrong before the check)
+    "dim288_fp32": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), dim=[288, 576, 1152, 2304]), "fp32", "LayerNorm width unsupported"),
+    "dim_head96": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), dim=[96, 192, 384, 768], dim_head=96), "bf16", "dim_head 96"),
+    "dh128_w9_fp32": (ACCEPTED_CONFIGS["H128w9"]["mc"], "fp32", "exceeds the kernel's 160 KB of LDS"),
+    "dh128_w11_fp32s": (ACCEPTED_CONFIGS["H128w11"]["mc"], "fp32s", "exceeds the kernel's 160 KB of LDS"),
+    "c_out631": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), levels=314), "bf16", "too many output channels for the tail kernel"),
+}

@@ -115,13 +115,61 @@ def test_config_validation_errors():
         WXConfig.from_model_conf(dict(base, padding_conf=dict(activate=True, mode="mirror", pad_lat=[37, 6], pad_lon=[12, 12])))
     with pytest.raises(ValueError):
         WXConfig.from_model_conf(dict(base, patch_height=2, patch_width=2))
-    # dim_head (crossformer.py:372-401): 32 / 64 / 96 / 128, dividing every stage width
+    # dim_head (crossformer.py:372-401): 32 / 64 / 128, dividing every stage width (96: the standalone attention operators only --
+    # no width the LayerNorm kernels take is a multiple of it; test_create_time_rejections_python)
     wide = WXConfig.from_model_conf(dict(base, dim=[64, 128, 256, 512], dim_head=64))
     assert wide.heads == (1, 2, 4, 8) and E.make_c_config(wide, "bf16").dim_head == 64
     with pytest.raises(ValueError):
         WXConfig.from_model_conf(dict(base, dim_head=64))               # 32 is not a multiple of 64
     with pytest.raises(ValueError):
         WXConfig.from_model_conf(dict(base, dim=[48, 96, 192, 384], dim_head=48))
+
+
+def test_create_time_rejections_python():
+    """WXConfig mirrors ModelSpec::derive(): what no kernel can run is refused when the config is built, with wx_create's words."""
+    from synth_batches import ACCEPTED_CONFIGS, REJECTED_CONFIGS, accepted_config, accepted_precisions
+    for name, (mc, prec, why) in REJECTED_CONFIGS.items():
+        with pytest.raises(ValueError, match=why):
+            WXConfig.from_model_conf(mc, precision=prec)
+    # the 2048-wide model is a bf16 model: accepted there, and by from_model_conf without a precision
+    wide = WXConfig.from_model_conf(REJECTED_CONFIGS["dim2048_fp32"][0])
+    wide.check_precision("bf16")
+    with pytest.raises(ValueError, match="LayerNorm width"):
+        wide.check_precision("fp32")
+    for name in ACCEPTED_CONFIGS:
+        for prec in accepted_precisions(name):
+            accepted_config(name, prec)
+
+
+def test_create_time_rejections_c_abi(lib):
+    """wx_create checks the config before it looks for a device: a shape no kernel runs is WX_ERR_INVALID with the reason at create
+    time (it used to pass wx_create, load and finalize, and throw inside the first wx_forward); every acceptance class gets past the
+    config check -- to an engine where a GPU is present, to the device error where none is."""
+    from synth_batches import ACCEPTED_CONFIGS, REJECTED_CONFIGS, accepted_config, accepted_precisions
+    have_gpu = torch.cuda.is_available()
+    for name, (mc, prec, why) in REJECTED_CONFIGS.items():
+        # the ABI's own check: the struct is built from an unvalidated WXConfig (the Python mirror would refuse first)
+        cfg = WXConfig(**{k: tuple(tuple(x) if isinstance(x, list) else x for x in v) if isinstance(v, list) else v for k, v in mc.items()})
+        h = ctypes.c_void_p()
+        cc = E.make_c_config(cfg, prec)
+        assert lib.wx_create(ctypes.byref(cc), 0, ctypes.byref(h)) == -1, name      # WX_ERR_INVALID
+        assert why.encode() in lib.wx_last_error(), (name, lib.wx_last_error())
+        assert not h.value
+    for name in ACCEPTED_CONFIGS:
+        for prec in accepted_precisions(name):
+            h = ctypes.c_void_p()
+            cc = E.make_c_config(accepted_config(name), prec)
+            st = lib.wx_create(ctypes.byref(cc), 0, ctypes.byref(h))
+            if have_gpu:
+                assert st == 0, (name, prec, lib.wx_last_error())
+                lib.wx_destroy(h)
+            else:
+                assert st != 0 and st != -1, (name, prec, lib.wx_last_error())       # not a config error: the missing device
+    # the plan builder shares the check (host only)
+    plan = ctypes.c_void_p()
+    cc = E.make_c_config(accepted_config("W9"), "bf16")
+    cc.dim[0], cc.dim[1], cc.dim[2], cc.dim[3] = 96, 192, 384, 768
+    assert lib.wx_band_plan_create(ctypes.byref(cc), 2, ctypes.byref(plan)) == -1 and b"LayerNorm width" in lib.wx_last_error()
 
 
 def test_named_configs_match_survey_parameter_counts():

@@ -100,6 +100,52 @@ def test_hip_window_attention_dot_product_mode_and_errors():
         op(qkv.cuda())                                         # wrong dtype for a bf16 operator
 
 
+# head widths x window shapes of the general kernel (launch_window_attn_dh): 1, 2, 4 (36 of 64 tokens), 4 (full), 7 (81 of 112), 7 (full),
+# 8 (121 of 128) and 8 (full) key fragments of 16 tokens.  head_dim 96 has no other route: no width the CrossFormer engine takes is a
+# multiple of it.
+SWEEP_WINDOWS = [(4, 4), (4, 6), (6, 6), (8, 8), (9, 9), (7, 16), (11, 11), (8, 16)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("ws", SWEEP_WINDOWS, ids=lambda w: f"{w[0]}x{w[1]}")
+@pytest.mark.parametrize("hd", [32, 64, 96, 128])
+def test_hip_window_attention_every_head_width_and_fragment_count(hd, ws, prec):
+    """Two windows per axis, unshifted and shifted by window // 2 (kind 3, seam mask), cosine attention with a per-head bias table and
+    logit scale, and plain dot-product attention without either: against the fp64 oracle on the q | k | v the operator sees (bf16:
+    the rounded ones).  Gates of test_hip_window_attention_vs_reference_golden: fp32 max err <= 1e-4 * max|ref|; bf16 against the
+    oracle on the same rounded inputs rel-L2 <= 1e-2 (and max err <= 5e-2 * max|ref|)."""
+    from wxengine.swin import WindowAttention
+    heads, N = 2, ws[0] * ws[1]
+    feat = (2 * ws[0], 2 * ws[1])
+    gen = torch.Generator().manual_seed(1000 * hd + 17 * ws[0] + ws[1])
+    dt = torch.float32 if prec == "fp32" else torch.bfloat16
+    qkv = torch.randn(feat[0], feat[1], 3 * heads * hd, generator=gen).to(dt)
+    bias = torch.randn(heads, N, N, generator=gen) * 0.5
+    scale = torch.tensor([4.0, 11.0])          # effective (exponentiated) logit scales
+    if prec == "fp32" and hd >= 96 and N > 64:
+        # four fp32 V images of head_dim x (tokens + 4) pass the 160 KB of LDS a workgroup can have: refused when the operator is
+        # created (it used to be created and to fail at its first launch)
+        from wxengine.engine import WXEngineError
+        with pytest.raises(WXEngineError, match="160 KB of LDS"):
+            WindowAttention(feat, heads, hd, ws, (0, 0), bias=bias.numpy(), logit_scale=scale.numpy(), precision=prec)
+        return
+    for shift in ((0, 0), (ws[0] // 2, ws[1] // 2)):
+        for b, ls in ((bias, scale), (None, None)):
+            op = WindowAttention(feat, heads, hd, ws, shift, bias=None if b is None else b.numpy(),
+                                 logit_scale=None if ls is None else ls.numpy(), precision=prec)
+            out = op(qkv.cuda().contiguous()).float().cpu().double()
+            ref = S.window_attention_core(qkv.double(), heads, ws, shift, None if b is None else b.double(), None if ls is None else ls.double())
+            err, l2 = ((out - ref).abs().max() / ref.abs().max()).item(), ((out - ref).norm() / ref.norm()).item()
+            what = f"hd {hd} window {ws} shift {shift} {'cosine + bias' if b is not None else 'dot product'} {prec}"
+            print(f"\n[winattn] {what}: max err / max|ref| {err:.3e} rel-L2 {l2:.3e}")
+            assert torch.isfinite(out).all()
+            if prec == "fp32":
+                assert err <= 1e-4, what + f": max err {err:.3e}"
+            else:
+                assert l2 <= 1e-2 and err <= 5e-2, what + f": rel-L2 {l2:.3e} max err {err:.3e}"
+
+
 @pytest.mark.gpu
 def test_fuxi_sized_throughput_smoke():
     """BASELINE config 5 shape (fuxi_6h: dim 1024, 8 heads of 128, window 7, 84 x 168 tokens after padding): finite, and a timing line
