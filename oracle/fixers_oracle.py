@@ -1,17 +1,27 @@
 """CPU ORACLE (test infrastructure) for the conservation fixers of the in-model / outside-model PostBlock
-(SURVEY.md §8(a) a12), pressure-level grids.
+(SURVEY.md §8(a) a12), pressure-level and hybrid sigma-pressure grids.
 
-Restates credit/postblock/gen1.py (GlobalMassFixer :280-391, GlobalWaterFixer :489-569,
-GlobalEnergyFixer :704-822) on top of credit/physics_core.py (physics_pressure_level :75-297).
-torch CPU; `dtype` selects fp32 (what the engine computes in, with fp64 global sums) or fp64.
-Pinned by tests/golden/fixers_demo.npz (the reference classes run on their own `simple_demo` grid,
-tools/make_goldens.py --only fixers).
+Restates credit/postblock/gen1.py (TracerFixer :111-167, GlobalMassFixer :280-391, GlobalWaterFixer :489-569,
+GlobalEnergyFixer :704-822, GlobalEnergyFixerUpDown :944-1025) on top of credit/physics_core.py
+(physics_pressure_level :75-297).  torch CPU; every function computes in the dtype of the tensors it is handed: fp32
+(what the reference and the engine compute in, the global sums in fp64) or, with fp64 tensors, statistics and grid
+(`dtype=torch.float64`), the high-precision reference of tests/test_fixers_sweep_gpu.py.
+
+`stats = {"in": (mean, std), "out": (mean, std)}` is the reference's `denorm: True`: `t * std + mean` before the fixer
+(its inverse_transform / inverse_transform_input) and `(t - mean) / std` after (transform_array), around the same code.
+
+Pinned to the reference's own classes, run on their `simple_demo` grid by tools/make_goldens.py:
+  tests/golden/fixers_demo.npz (--only fixers), fixers_updown.npz (--only updown), fixers_sigma.npz (--only sigma) and
+  fixers_frames2.npz (--only frames2: an `x` of two different frames -- the fixers read the LAST one, gen1.py:303).
+`energy_fixer_signed` (R_T / F_S as signed sums of up to 4 / 8 flux channels: the form the device block runs) is pinned to
+`energy_fixer` / `energy_fixer_updown` / `energy_fixer_sigma` bit for bit at their term lists (tests/test_fixers_oracle.py).
 
 Hybrid sigma-pressure grids (physics_hybrid_sigma_level :300-520; fixer branches gen1.py:306-375, 527-533, 783-788) are
-restated by SigmaGrid + the *_sigma functions and pinned by tests/golden/fixers_sigma.npz.
+restated by SigmaGrid + the *_sigma functions.
 
 Not reproduced (documented): `concat_fix`'s quirk that DROPS the channels after the
-fixed block when it ends at N_vars-2 (gen1.py:1063-1071) — this restatement always keeps every channel.
+fixed block when it ends at N_vars-2 (gen1.py:1063-1071) -- this restatement always keeps every channel; and
+`tracer_fixer(stats=...)` de-normalises only the channels it clamps (the reference round-trips the whole tensor).
 """
 from __future__ import annotations
 
@@ -312,4 +322,75 @@ def energy_fixer_updown(y, x, grid: Grid, T_start: int, q_start: int, U_start: i
         mean, std = stats["out"]
         T_new = (T_new - mean[sl].view(-1, 1, 1)) / std[sl].view(-1, 1, 1)
     y[sl] = T_new
+    return y
+
+
+def energy_fixer_signed(y, x, grid, T_start: int, q_start: int, U_start: int, V_start: int, n_lev: int, toa, surf,
+                        gph_surf: torch.Tensor, n_seconds: float, stats: Optional[Dict] = None, sp_ind: Optional[int] = None):
+    """The energy fixer with R_T = sum_k sign_k * y[ind_k] over `toa` = [(ind, sign), ...] (1..4 terms) and F_S likewise over
+    `surf` (1..8 terms), each summed left to right; `grid` is a Grid, or a SigmaGrid with the surface-pressure channel `sp_ind`.
+    GlobalEnergyFixer is toa = 2 x (+), surf = 4 x (+); GlobalEnergyFixerUpDown toa = (+ - -), surf = (+ - + - - -)."""
+    assert 1 <= len(toa) <= 4 and 1 <= len(surf) <= 8
+    sigma = isinstance(grid, SigmaGrid)
+    y = y.clone()
+
+    def lev(t, s, which):
+        sl = slice(s, s + n_lev)
+        return _den(t[sl], *stats[which], sl) if stats else t[sl]
+
+    def one(t, i, which="out"):
+        sl = slice(i, i + 1)
+        return (_den(t[sl], *stats[which], sl) if stats else t[sl])[0]
+
+    def signed_sum(terms):
+        acc = terms[0][1] * one(y, terms[0][0])
+        for i, s in terms[1:]:
+            acc = acc + s * one(y, i)
+        return acc
+
+    def integral(e, sp):
+        return grid.integral(e, sp) if sigma else column_integral(e, grid.p, grid.midpoint)
+
+    T0, q0, U0, V0 = (lev(x, s, "in") for s in (T_start, q_start, U_start, V_start))
+    T1, q1, U1, V1 = (lev(y, s, "out") for s in (T_start, q_start, U_start, V_start))
+    sp_in, sp_pr = (one(x, sp_ind, "in"), one(y, sp_ind)) if sigma else (None, None)
+    cp0 = (1 - q0) * CP_DRY + q0 * CP_VAPOR
+    cp1 = (1 - q1) * CP_DRY + q1 * CP_VAPOR
+    g = gph_surf.to(y.dtype)
+    eq0 = LH_WATER * q0 + g + 0.5 * (U0 ** 2 + V0 ** 2)
+    eq1 = LH_WATER * q1 + g + 0.5 * (U1 ** 2 + V1 ** 2)
+    r_t = grid.wsum(signed_sum(list(toa)) / n_seconds)
+    f_s = grid.wsum(signed_sum(list(surf)) / n_seconds)
+    e0 = cp0 * T0 + eq0
+    e1 = cp1 * T1 + eq1
+    te0 = grid.wsum(integral(e0, sp_in) / GRAVITY)
+    te1 = grid.wsum(integral(e1, sp_pr) / GRAVITY)
+    ratio = ((n_seconds * (r_t - f_s) + te0) / te1).to(y.dtype)
+    T_new = (e1 * ratio - eq1) / cp1
+    sl = slice(T_start, T_start + n_lev)
+    if stats:
+        mean, std = stats["out"]
+        T_new = (T_new - mean[sl].view(-1, 1, 1)) / std[sl].view(-1, 1, 1)
+    y[sl] = T_new
+    return y
+
+
+def tracer_fixer(y: torch.Tensor, inds: Sequence[int], thres: Sequence[float], thres_max: Optional[Sequence[float]] = None,
+                 stats: Optional[Dict] = None) -> torch.Tensor:
+    """TracerFixer (gen1.py:136-167): per listed channel, values < thres become thres, then values >= thres_max become
+    thres_max; in physical units when `stats` is given.  The thresholds are rounded to y's dtype, as the comparison does."""
+    y = y.clone()
+    for k, ch in enumerate(inds):
+        v = y[ch]
+        if stats:
+            mean, std = stats["out"]
+            v = v * std[ch] + mean[ch]
+        lo = torch.tensor(float(thres[k]), dtype=y.dtype)
+        v = torch.where(v < lo, lo, v)
+        if thres_max is not None:
+            hi = torch.tensor(float(thres_max[k]), dtype=y.dtype)
+            v = torch.where(v >= hi, hi, v)
+        if stats:
+            v = (v - mean[ch]) / std[ch]
+        y[ch] = v
     return y

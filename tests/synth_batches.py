@@ -194,3 +194,182 @@ REJECTED_CONFIGS = {
     "dh128_w11_fp32s": (ACCEPTED_CONFIGS["H128w11"]["mc"], "fp32s", "exceeds the kernel's 160 KB of LDS"),
     "c_out631": (dict(_sq(4, (2, 2, 2, 2), (4, 4, 2, 2)), levels=314), "bf16", "too many output channels for the tail kernel"),
 }
+
+
+# ------------------------------------------------------------------ the device PostBlock against the fp64 oracle
+# tests/test_fixers_sweep_gpu.py runs every case on the GPU; tests/test_fixers_oracle.py runs the same table through the oracle in
+# fp32 and fp64 (the conditioning test).  Grids: G9 = 33 x 67 (2 211 cells: 9 workgroups, 163 live lanes in the last), G257 =
+# 181 x 363 (65 703 cells: 257 workgroups, so thread 0 of fix_sum_kernel takes a second trip; 167 live lanes in the last).
+# Channel layout of a case with nl carried levels (levels - 1 when midpoint):
+#   x [4 nl + 3]:  T | q | U | V | SP | 2 input-only          y [4 nl + 15]:  T | q | U | V | SP | 4 TOA | 8 surface | precip | evapor
+FIXER_GRIDS = {"G9": (33, 67, 5.25), "G257": (181, 363, 0.75)}     # rows, columns, longitude step (degrees, exact in fp32)
+FIXER_GATES = {"single": 5e-5, "chain": 1e-4, "chain_precip": 2e-3}  # max|got - ref| / max|ref| over the owned block (tests/test_fixers_gpu.py)
+SIGNED_48 = dict(toa=(1.0, -1.0, 0.5, -1.0), surf=(1.0, -1.0, 1.0, -1.0, -1.0, -1.0, 2.5, -0.25))   # mixed signs, non-unit magnitudes
+SIGNED_11 = dict(toa=(-0.75,), surf=(1.0,))
+_FIX_BASE = dict(grid="G9", orient="ns", sigma=False, midpoint=False, denorm=False, frames=1, levels=13, fix=3)
+
+
+def _fixer_cases():
+    """name -> case.  Base: G9, north-to-south, pressure, trapz, denorm off, 1 frame, 13 levels, fix_level_num 3; one or two axes
+    move per row.  fix_level_num = 1 stays out: the reference's own denominator is then an empty integral (gen1.py:264-270)."""
+    rows = []
+
+    def add(fixer, **kw):
+        c = dict(_FIX_BASE, fixer=fixer, **kw)
+        name = "-".join([c["grid"], "sig" if c["sigma"] else "prs", fixer] + [f"{k}{int(v) if not isinstance(v, str) else v}" for k, v in kw.items()
+                                                                              if k not in ("grid", "sigma")])
+        rows.append((name, c))
+
+    for grid in ("G9", "G257"):
+        big = grid == "G257"
+        for sigma in (False, True):
+            g = dict(grid=grid, sigma=sigma)
+            for fixer in ("mass", "water", "energy", "signed48", "chain"):     # the fixers and the chain at the base case
+                add(fixer, **g)
+            add("mass", midpoint=True, **g)
+            add("chain", midpoint=True, denorm=True, frames=2, **g)
+            add("water", denorm=True, frames=3, **g)
+            add("energy", denorm=True, midpoint=True, **g)
+            add("signed48", denorm=True, frames=2, levels=2, **g)
+            if not sigma:                                       # fix_level_num: the sigma mass fixer rescales SP and has none
+                add("mass", fix=2, frames=2, **g)
+                add("mass", fix=13, **g)
+            if not big:                                         # 64 levels: G9 only
+                add("mass", levels=64, fix=64, midpoint=True, **g)
+                add("energy", levels=64, denorm=True, **g)
+    add("updown")
+    add("signed11")
+    add("updown", denorm=True, midpoint=True)
+    add("mass", levels=2, fix=2, denorm=True)
+    add("mass", levels=64, fix=2)
+    add("chain", orient="sn")                                   # south-to-north rows
+    add("chain", orient="wrap", sigma=True, denorm=True)        # longitudes from 200 degrees through 360
+    return dict(rows)
+
+
+FIXER_CASES = _fixer_cases()
+
+
+def fixer_case_inputs(name):
+    """Everything a case needs, as fp32 numpy arrays (what the engine is handed; the fp64 oracle promotes the same numbers)."""
+    c = FIXER_CASES[name]
+    H, W, dlon = FIXER_GRIDS[c["grid"]]
+    L = c["levels"]
+    nl = L - 1 if c["midpoint"] else L
+    g = np.random.Generator(np.random.Philox(key=[sorted(FIXER_CASES).index(name), 41]))
+    # G9 runs pole to pole (cells of next to no area at both ends); G257 from the pole to the equator, so that its LAST workgroup
+    # -- the 257th partial, which only the second trip of fix_sum_kernel's stride loop adds -- holds cells of the largest area
+    lat = np.linspace(90.0, -90.0 if c["grid"] == "G9" else 0.0, H)
+    if c["orient"] == "sn":
+        lat = lat[::-1]
+    lon = np.arange(W) * dlon
+    if c["orient"] == "wrap":
+        lon = (200.0 + lon) % 360.0           # the (-pi, pi] wrap of d_lambda sits inside every row
+    lon2d, lat2d = np.meshgrid(lon.astype(np.float32), lat.astype(np.float32))
+    eta = np.linspace(0.0, 1.0, L)
+    p = np.round(2000.0 + 99000.0 * eta)                                 # Pa, integers: exact in fp32
+    coef_a = np.round(2000.0 * (1.0 - eta) + 40000.0 * eta * (1.0 - eta))
+    coef_b = (eta ** 2).astype(np.float32)
+
+    def state(dT, fq, dsp):
+        return [250.0 + dT + 30.0 * g.standard_normal((nl, H, W)), fq * np.abs(0.004 + 0.004 * g.standard_normal((nl, H, W))),
+                12.0 * g.standard_normal((nl, H, W)), 8.0 * g.standard_normal((nl, H, W)), 1.0e5 + dsp + 2.0e3 * g.standard_normal((1, H, W))]
+    x = np.concatenate(state(0.0, 1.0, 0.0) + [g.standard_normal((2, H, W))], 0)
+    y_state = state(2.0, 1.3, -500.0)   # a warmer, moister, lighter prediction: every fixer has a correction far above its gate to make
+    # flux channels of distinct, non-zero global means (J/m2): dropping or mis-signing any one term moves the energy ratio visibly
+    flux = (1.0 + 0.3 * np.arange(12))[:, None, None] * 1.0e6 + 5.0e5 * g.standard_normal((12, H, W))
+    # precipitation / evaporation of one sign and large against the change of column water: the water ratio
+    # (-d(TWC) - E) / P is then a quotient of sums that do not cancel
+    # (and it rains four times as much at the equator as at the poles: a sum that loses some rows gives another ratio)
+    precip = (np.abs(1.0e-2 * g.standard_normal((1, H, W))) + 1.0e-3) * (1.0 + 3.0 * np.cos(np.deg2rad(lat))[None, :, None] ** 2)
+    evapor = -np.abs(5.0e-3 * g.standard_normal((1, H, W)))
+    y = np.concatenate(y_state + [flux, precip, evapor], 0)
+    lay = dict(nl=nl, T=0, q=nl, U=2 * nl, V=3 * nl, sp=4 * nl, toa=[4 * nl + 1 + k for k in range(4)],
+               surf=[4 * nl + 5 + k for k in range(8)], precip=4 * nl + 13, evapor=4 * nl + 14, c_in=4 * nl + 3, c_out=4 * nl + 15)
+    stats = None
+    if c["denorm"]:   # four distinct vectors, distinct per channel: mean_in != mean_out and std_in != std_out everywhere
+        def vec(n):
+            blk = [(250.0, 30.0)] * nl + [(4e-3, 4e-3)] * nl + [(1.0, 12.0)] * nl + [(-1.0, 8.0)] * nl + [(1.0e5, 2.0e3)]
+            blk += [(0.1, 1.0)] * 2 if n == lay["c_in"] else [(1.0e5, 2.0e6)] * 12 + [(8e-3, 6e-3), (-4e-3, 3e-3)]
+            k = np.arange(n)
+            return np.array([b[0] for b in blk]) + 0.01 * k * np.array([b[1] for b in blk]), np.array([b[1] for b in blk]) * (1.0 + 0.01 * k)
+        mo, so = vec(lay["c_out"])
+        mi, si = vec(lay["c_in"])
+        mi, si = mi + 0.3 * si, 1.25 * si
+        stats = tuple(v.astype(np.float32) for v in (mi, si, mo, so))
+        x = (x - stats[0][:, None, None].astype(np.float64)) / stats[1][:, None, None]
+        y = (y - stats[2][:, None, None].astype(np.float64)) / stats[3][:, None, None]
+    xf = np.full((lay["c_in"], c["frames"], H, W), np.nan, np.float32)   # earlier frames NaN: a read of the wrong frame shows
+    xf[:, -1] = x
+    return dict(case=c, lay=lay, lat2d=lat2d, lon2d=lon2d, p=p.astype(np.float32), coef_a=coef_a.astype(np.float32), coef_b=coef_b,
+                gph=(500.0 + 200.0 * g.standard_normal((H, W))).astype(np.float32), x=xf, y=y.astype(np.float32), stats=stats,
+                n_seconds=6 * 3600.0, tracer=dict(inds=list(range(nl, 2 * nl)) + [lay["precip"]], thres=[5e-4] * nl + [2e-3],
+                                                  thres_max=[1.2e-2] * nl + [6.0e-2]))
+
+
+def fixer_case_terms(inp):
+    """[(toa terms), (surface terms)] as (channel, sign) lists of the case's energy fixer, or None."""
+    lay, fixer = inp["lay"], inp["case"]["fixer"]
+    t, s = lay["toa"], lay["surf"]
+    if fixer in ("energy", "chain"):
+        return [(t[0], 1.0), (t[1], 1.0)], [(s[k], 1.0) for k in range(4)]
+    if fixer == "updown":
+        return [(t[0], 1.0), (t[1], -1.0), (t[2], -1.0)], list(zip(s[:6], (1.0, -1.0, 1.0, -1.0, -1.0, -1.0)))
+    if fixer == "signed48":
+        return list(zip(t, SIGNED_48["toa"])), list(zip(s, SIGNED_48["surf"]))
+    if fixer == "signed11":
+        return [(t[3], SIGNED_11["toa"][0])], [(s[7], SIGNED_11["surf"][0])]
+    return None
+
+
+def fixer_case_oracle(inp, dtype, terms=None):
+    """The case through oracle/fixers_oracle.py in `dtype` (fp32: the fp32 grid, as the reference computes); `terms` replaces the
+    case's own flux terms."""
+    from oracle import fixers_oracle as F
+    c, lay = inp["case"], inp["lay"]
+    t = lambda a: torch.from_numpy(np.asarray(a)).to(dtype)   # noqa: E731
+    x, y, gph = t(inp["x"][:, -1]), t(inp["y"]), t(inp["gph"])
+    st = inp["stats"]
+    stats = None if st is None else {"in": (t(st[0]), t(st[1])), "out": (t(st[2]), t(st[3]))}
+    nl, ns, q, sp = lay["nl"], inp["n_seconds"], lay["q"], lay["sp"]
+    if c["sigma"]:
+        grid = F.SigmaGrid(inp["lat2d"], inp["lon2d"], inp["coef_a"], inp["coef_b"], midpoint=c["midpoint"], dtype=dtype)
+        mass = lambda v: F.mass_fixer_sigma(v, x, grid, q, nl, sp, stats)   # noqa: E731
+        water = lambda v: F.water_fixer_sigma(v, x, grid, q, nl, lay["precip"], lay["evapor"], sp, ns, stats)   # noqa: E731
+    else:
+        grid = F.Grid(inp["lat2d"], inp["lon2d"], inp["p"], midpoint=c["midpoint"], dtype=dtype)
+        mass = lambda v: F.mass_fixer(v, x, grid, q, nl, c["fix"], stats)   # noqa: E731
+        water = lambda v: F.water_fixer(v, x, grid, q, nl, lay["precip"], lay["evapor"], ns, stats)   # noqa: E731
+    terms = terms or fixer_case_terms(inp)
+    energy = lambda v: F.energy_fixer_signed(v, x, grid, lay["T"], q, lay["U"], lay["V"], nl, terms[0], terms[1], gph, ns, stats,   # noqa: E731
+                                             sp if c["sigma"] else None)
+    if c["fixer"] == "mass":
+        return mass(y)
+    if c["fixer"] == "water":
+        return water(y)
+    if c["fixer"] == "chain":
+        tr = inp["tracer"]
+        return energy(water(mass(F.tracer_fixer(y, tr["inds"], tr["thres"], tr["thres_max"], stats))))
+    return energy(y)
+
+
+def fixer_case_owned(inp):
+    """[(channel slice, gate)] of the blocks the case's fixers own; every other channel must come back bit-identical."""
+    c, lay = inp["case"], inp["lay"]
+    nl = lay["nl"]
+    T, q, sp, pr = slice(0, nl), slice(nl, 2 * nl), slice(lay["sp"], lay["sp"] + 1), slice(lay["precip"], lay["precip"] + 1)
+    one = FIXER_GATES["single"]
+    if c["fixer"] == "mass":
+        return [(sp if c["sigma"] else q, one)]
+    if c["fixer"] == "water":
+        return [(pr, one)]
+    if c["fixer"] == "chain":   # the tracer clamps q and precipitation; the mass fixer then owns q (pressure) or SP (sigma)
+        return [(T, FIXER_GATES["chain"]), (q, FIXER_GATES["chain"]), (pr, FIXER_GATES["chain_precip"])] + (
+            [(sp, FIXER_GATES["chain"])] if c["sigma"] else [])
+    return [(T, one)]
+
+
+def fixer_block_error(got, ref, blk):
+    """max|got - ref| / max|ref| over a channel block, in the units the tensor is stored in."""
+    got, ref = np.asarray(got, np.float64)[blk], np.asarray(ref, np.float64)[blk]
+    return float(np.abs(got - ref).max() / np.abs(ref).max())

@@ -599,6 +599,63 @@ def fixers_golden():
     np.savez_compressed(os.path.join(GOLD, "fixers_demo.npz"), **out)
 
 
+def fixers_frames2_golden():
+    """The three fixers handed an `x` of two DIFFERENT frames (they read x_input[:, ..., -1, ...], gen1.py:303, :515, :744):
+    inputs [C, 2, H, W] and outputs only.  Frame 0 is a different state altogether, so reading it cannot pass."""
+    from credit.postblock.gen1 import GlobalEnergyFixer, GlobalMassFixer, GlobalWaterFixer
+    x_np, y_np = fixer_inputs(seed=17)
+    x_np[:, 0] = x_np[:, 0] * 1.5 + 1.0     # frame 0: another magnitude as well as other noise
+    out = {"x": x_np, "y": y_np}
+    L = 7
+    for midpoint in (False, True):
+        nl = L - 1 if midpoint else L
+        tag = "mid" if midpoint else "trapz"
+        xs = np.concatenate([x_np[b * L:b * L + nl] for b in range(4)], 0)
+        ys = np.concatenate([y_np[b * L:b * L + nl] for b in range(4)] + [y_np[28:]], 0)
+        x = torch.from_numpy(xs)[None]             # [1, 4 nl, 2, H, W]
+        y = torch.from_numpy(ys)[None, :, None]
+        base = {"simple_demo": True, "denorm": False, "grid_type": "pressure", "midpoint": midpoint,
+                "activate": True, "activate_outside_model": False}
+        q_inds = list(range(nl, 2 * nl))
+        conf_m = {"global_mass_fixer": dict(base, fix_level_num=3, q_inds=q_inds), "data": {"lead_time_periods": 6}}
+        conf_w = {"global_water_fixer": dict(base, q_inds=q_inds, precip_ind=4 * nl + 6, evapor_ind=4 * nl + 7),
+                  "data": {"lead_time_periods": 6}}
+        conf_e = {"global_energy_fixer": dict(base, T_inds=list(range(0, nl)), q_inds=q_inds,
+                                              U_inds=list(range(2 * nl, 3 * nl)), V_inds=list(range(3 * nl, 4 * nl)),
+                                              TOA_rad_inds=[4 * nl, 4 * nl + 1], surf_rad_inds=[4 * nl + 2, 4 * nl + 3],
+                                              surf_flux_inds=[4 * nl + 4, 4 * nl + 5]), "data": {"lead_time_periods": 6}}
+        with torch.no_grad():
+            ym = GlobalMassFixer(conf_m)({"y_pred": y.clone(), "x": x.clone()})["y_pred"]
+            yw = GlobalWaterFixer(conf_w)({"y_pred": y.clone(), "x": x.clone()})["y_pred"]
+            ye = GlobalEnergyFixer(conf_e)({"y_pred": y.clone(), "x": x.clone()})["y_pred"]
+            yc = GlobalEnergyFixer(conf_e)(GlobalWaterFixer(conf_w)(GlobalMassFixer(conf_m)(
+                {"y_pred": y.clone(), "x": x.clone()})))["y_pred"]
+        # only the channels a fixer (or the chain) may change are stored: the rest equal y
+        out[f"{tag}_mass"] = ym[0, nl:2 * nl, 0].numpy()
+        out[f"{tag}_water"] = yw[0, 4 * nl + 6, 0].numpy()
+        out[f"{tag}_energy"] = ye[0, :nl, 0].numpy()
+        out[f"{tag}_chain"] = np.concatenate([yc[0, :2 * nl, 0].numpy(), yc[0, 4 * nl + 6:4 * nl + 7, 0].numpy()], 0)
+        for name, t in (("mass", ym), ("water", yw), ("energy", ye), ("chain", yc)):
+            assert t.shape == y.shape, (name, t.shape)
+        print(f"[golden] two-frame fixers {tag}: mass dq max {float((ym - y).abs().max()):.3e}  water dP max "
+              f"{float((yw - y).abs().max()):.3e}  energy dT max {float((ye - y).abs().max()):.3e}")
+    # TracerFixer (gen1.py:136-167) on the q block and the precipitation of the same y; each threshold IS a value of its channel,
+    # so `<` against `<=` and `>=` against `>` are both exercised at equality
+    from credit.postblock.gen1 import TracerFixer
+    inds = list(range(L, 2 * L)) + [4 * L + 6]
+    pairs = [sorted((float(y_np[c, 2, 3]), float(y_np[c, 5, 7]))) for c in inds]
+    conf_t = {"tracer_fixer": {"tracer_inds": inds, "tracer_thres": [p[0] for p in pairs], "tracer_thres_max": [p[1] for p in pairs],
+                               "denorm": False}}
+    with torch.no_grad():
+        yt = TracerFixer(conf_t)({"y_pred": torch.from_numpy(y_np.copy())[None, :, None]})["y_pred"]
+    out["tracer_inds"] = np.array(inds, np.int32)
+    out["tracer_thres"] = np.array([p[0] for p in pairs], np.float64)
+    out["tracer_thres_max"] = np.array([p[1] for p in pairs], np.float64)
+    out["tracer"] = yt[0, inds, 0].numpy()
+    print(f"[golden] tracer fixer: {int((yt[0, :, 0] != torch.from_numpy(y_np)).sum())} values clamped")
+    np.savez_compressed(os.path.join(GOLD, "fixers_frames2.npz"), **out)
+
+
 def fixers_updown_golden():
     """GlobalEnergyFixerUpDown of the reference on its simple_demo grid (gen1.py:866-879), trapz and midpoint.
     Channel layout of y: [T|q|U|V] + 9 flux channels [TOA dn solar, TOA up solar, OLR, surf dn solar, surf up solar, surf dn LW,
@@ -936,7 +993,7 @@ def state_specs_golden():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="pad,T0,T1,blocks,specs,glue,swin,swinblock,fuxi,attend,rollC1,rollC3S,rollC3,T0M,layout,fixers,sigma,updown,pre,gen2,rec,asm,gen2loop,fuxi_timm,C1,C3S,C3,T0W,C1W,T0U,T0F,RT,stress")
+    ap.add_argument("--only", default="pad,T0,T1,blocks,specs,glue,swin,swinblock,fuxi,attend,rollC1,rollC3S,rollC3,T0M,layout,fixers,frames2,sigma,updown,pre,gen2,rec,asm,gen2loop,fuxi_timm,C1,C3S,C3,T0W,C1W,T0U,T0F,RT,stress")
     args = ap.parse_args()
     os.makedirs(GOLD, exist_ok=True)
     torch.set_num_threads(os.cpu_count() or 1)
@@ -965,6 +1022,8 @@ def main():
             layout_golden()
         elif item == "fixers":
             fixers_golden()
+        elif item == "frames2":
+            fixers_frames2_golden()
         elif item == "sigma":
             fixers_sigma_golden()
         elif item == "updown":
