@@ -334,6 +334,40 @@ int wx_post_set_band(wx_post_handle p, int row0, int rows);
  * take ownership. */
 int wx_attach_postblock(wx_handle h, wx_post_handle p);
 
+/* ---- pressure-level products on the device (csrc/wx_diag.h) ----------------------------------------------------------
+ * The three diagnostics of the gen-2 post-block chain in ONE launch, one thread per column, on the named tensors as they lie in
+ * memory ([B][n_levels][n_time][H][W] float32 contiguous; 2-D variables [B][1][n_time][H][W]):
+ *   wx_diag_create / wx_diag_destroy  <-> GeopotentialDiagnostic.__init__ (credit/postblock/geopotential.py:132-172),
+ *                         PressureInterpDiagnostic.__init__ (credit/postblock/pressure_interp.py:189-241), MSLPDiagnostic.__init__
+ *                         (credit/postblock/mslp.py:117-132); 2 <= n_levels <= 137
+ *   wx_diag_set_levels    <-> the hybrid coefficients those constructors read from `level_info_file`: a_half / b_half [n_levels + 1]
+ *                         (geopotential.py:162-171, p = a + b sp on the interfaces, non-positive -> 0.57 Pa, :32-33) with its
+ *                         `flip_vertical` (:70-82), and a_mid / b_mid [n_levels] (pressure_interp.py:225-234); host pointers,
+ *                         either pair may be NULL when no requested product needs it.  Levels stored surface -> top are detected
+ *                         from a_mid + b_mid * 101325 Pa as :237-241 does and handled by index arithmetic.
+ *   wx_diag_set_pressure_levels <-> `pressure_levels` (in Pa here, any order, 1 <= n_plev <= 64) and `temp_height` (:191, :202)
+ *   wx_diag_apply         <-> the three forward()s: geopotential (geopotential.py:37-83), interp_column_to_pressure_levels
+ *                         (pressure_interp.py:44-130 over _interp_utils.py:14-40: linear in log p, constant extrapolation of
+ *                         `fields`, Trenberth Eq. 16 / 15 below ground for T and Z) and mslp_from_surface_pressure (mslp.py:33-80).
+ *       T, q, fields[f]   [B][n_levels][n_time][H][W]      sp, t_near_surface  [B][1][n_time][H][W]
+ *       phis              [B][1][phis_n_time][H][W], phis_n_time = 1 or n_time
+ *       z_model_out       [B][n_levels][n_time][H][W]: the model-level geopotential, or NULL
+ *       plev_out          HOST array of n_fields + 2 device pointers [B][n_plev][n_time][H][W]: the fields, then T, then Z; or NULL
+ *       mslp_out          [B][1][n_time][H][W], or NULL
+ *     A NULL output switches that product off; a product whose inputs or coefficients are missing is WX_ERR_INVALID with the
+ *     reason in wx_last_error().  The geopotential that feeds the interpolation stays on the chip.  Chain form (the reference's
+ *     separate blocks, where the interpolation takes `geopotential_var` from the batch): with q == NULL and plev_out given,
+ *     z_model_out is READ as the model-level geopotential instead of written; the results equal the fused launch bit for bit. */
+typedef struct wx_diag* wx_diag_handle;
+int wx_diag_create(int H, int W, int n_levels, int device, wx_diag_handle* out);
+int wx_diag_destroy(wx_diag_handle d);
+int wx_diag_set_levels(wx_diag_handle d, const float* a_half, const float* b_half, const float* a_mid, const float* b_mid,
+                       int flip_vertical);
+int wx_diag_set_pressure_levels(wx_diag_handle d, const float* p_pa, int n_plev, float temp_height);
+int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const float* q, const float* sp, const float* phis,
+                  int phis_n_time, const float* t_near_surface, const float* const* fields, int n_fields, float* z_model_out,
+                  float* const* plev_out, float* mslp_out, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

@@ -317,6 +317,40 @@ int wx_attach_postblock(wx_handle h, wx_post_handle p) {
   return guarded([&] { WX_NEED(h); h->impl->attach_post(p ? p->impl.get() : nullptr); });
 }
 
+// ---- pressure-level products (geopotential, model -> pressure levels, MSLP; csrc/wx_diag.h) ------------------------------------
+struct wx_diag {
+  std::unique_ptr<wx::Diag> impl;
+};
+#define WX_NEEDD(d) if (!(d) || !(d)->impl) throw wx::ConfigError("null diagnostics handle")
+int wx_diag_create(int H, int W, int n_levels, int device, wx_diag_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_diag_create: null argument");
+    if (n_levels < 2 || n_levels > wx::kDiagMaxLevels) throw wx::ConfigError("wx_diag_create: n_levels must be 2 .. 137");   // needs no device to be told
+    need_device(device, "wx_diag_create");
+    std::unique_ptr<wx_diag> d(new wx_diag);
+    remap<wx::ConfigError>([&] { d->impl.reset(new wx::Diag(H, W, n_levels, device)); });
+    *out = d.release();
+  });
+}
+int wx_diag_destroy(wx_diag_handle d) { return guarded([&] { delete d; }); }
+int wx_diag_set_levels(wx_diag_handle d, const float* a_half, const float* b_half, const float* a_mid, const float* b_mid, int flip_vertical) {
+  return guarded([&] { WX_NEEDD(d); remap<wx::ConfigError>([&] { d->impl->set_levels(a_half, b_half, a_mid, b_mid, flip_vertical); }); });
+}
+int wx_diag_set_pressure_levels(wx_diag_handle d, const float* p_pa, int n_plev, float temp_height) {
+  return guarded([&] { WX_NEEDD(d); remap<wx::ConfigError>([&] { d->impl->set_pressure_levels(p_pa, n_plev, temp_height); }); });
+}
+int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const float* q, const float* sp, const float* phis,
+                  int phis_n_time, const float* t_near_surface, const float* const* fields, int n_fields, float* z_model_out,
+                  float* const* plev_out, float* mslp_out, void* stream) {
+  return guarded([&] {
+    WX_NEEDD(d);
+    remap<wx::ConfigError>([&] {
+      d->impl->apply(batch, n_time, T, q, sp, phis, phis_n_time, t_near_surface, fields, n_fields, z_model_out, plev_out, mslp_out,
+                     (hipStream_t)stream);
+    });
+  });
+}
+
 // ---- standalone window attention (the Swin / FuXi mode of the attention kernel) -----------------------
 struct wx_winattn {
   wx_winattn_desc d;

@@ -116,6 +116,12 @@ _PROTOTYPES = {
     "wx_post_add_energy_fixer": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_int], C.c_int),
     "wx_post_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "wx_attach_postblock": ([C.c_void_p, C.c_void_p], C.c_int),
+    "wx_diag_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_diag_destroy": ([C.c_void_p], C.c_int),
+    "wx_diag_set_levels": ([C.c_void_p] + [C.POINTER(C.c_float)] * 4 + [C.c_int], C.c_int),
+    "wx_diag_set_pressure_levels": ([C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float], C.c_int),
+    "wx_diag_apply": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                       C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p], C.c_int),
     "wx_winattn_create": ([C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_winattn_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "wx_winattn_destroy": ([C.c_void_p], C.c_int),
@@ -547,3 +553,103 @@ class WXPostBlock:
         _check(self.lib.wx_post_apply(self._p, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return y
+
+
+class WXDiag:
+    """Device-side pressure-level products (include/wxengine.h wx_diag_*, csrc/wx_diag.h): model-level geopotential, model ->
+    pressure levels and MSLP of one set of named tensors in one launch.  The blocks of wxengine/diagnostics.py sit on top."""
+
+    def __init__(self, H: int, W: int, n_levels: int, device: int = 0):
+        import torch
+        self.lib = load_library()
+        if not torch.cuda.is_available():
+            raise WXEngineError("no GPU visible: the pressure-level products have no CPU fallback")
+        self.H, self.W, self.L, self.device = int(H), int(W), int(n_levels), int(device)
+        self._d = C.c_void_p()
+        _check(self.lib.wx_diag_create(self.H, self.W, self.L, self.device, C.byref(self._d)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_d", None) and self._d.value:
+                self.lib.wx_diag_destroy(self._d)
+                self._d = C.c_void_p()
+        except Exception:
+            pass
+
+    def set_levels(self, a_half=None, b_half=None, a_mid=None, b_mid=None, flip_vertical: bool = True):
+        """Hybrid coefficients in the stored level order: a_half / b_half [n_levels + 1] for the geopotential, a_mid / b_mid
+        [n_levels] for the interpolation; either pair may be None."""
+        fp = C.POINTER(C.c_float)
+        arrs = []
+        for name, a, n in (("a_half", a_half, self.L + 1), ("b_half", b_half, self.L + 1), ("a_mid", a_mid, self.L), ("b_mid", b_mid, self.L)):
+            if a is None:
+                arrs.append(None)
+                continue
+            a = _fp(a).ravel()
+            if a.size != n:
+                raise WXEngineError(f"n_levels mismatch: {name} has {a.size} entries, the block was created for {self.L} levels ({n} expected)")
+            arrs.append(a)
+        _check(self.lib.wx_diag_set_levels(self._d, *[None if a is None else a.ctypes.data_as(fp) for a in arrs], int(bool(flip_vertical))))
+
+    def set_pressure_levels(self, p_pa, temp_height: float = 150.0):
+        p = _fp(p_pa).ravel()
+        _check(self.lib.wx_diag_set_pressure_levels(self._d, p.ctypes.data_as(C.POINTER(C.c_float)), p.size, float(temp_height)))
+        self.n_plev = p.size
+
+    def apply(self, sp, phis, T=None, q=None, t_ns=None, fields=(), z_in=None, want_z=False, want_plev=False, want_mslp=False):
+        """Named tensors [B, n_levels, n_time, H, W] (sp / t_ns: one level; phis: one level, n_time 1 or that of sp) -> dict with
+        "z" [B, n_levels, n_time, H, W], "plev" (list: every field, then T, then Z, each [B, n_plev, n_time, H, W]) and "mslp"
+        [B, 1, n_time, H, W] for the products asked for.  `z_in`: chain form, the interpolation reads this geopotential instead of
+        integrating T and q.  The tensors are read where they lie: views into a larger tensor are taken as they are, and when the
+        batch items of such a view are not adjacent in memory every item is one launch.  Nothing is copied."""
+        import torch
+        fields = list(fields)
+        named = [("sp", sp, 1), ("phis", phis, 1), ("T", T, self.L), ("q", q, self.L), ("t_ns", t_ns, 1), ("z_in", z_in, self.L)]
+        named += [(f"fields[{i}]", f, self.L) for i, f in enumerate(fields)]
+        if sp is None or sp.dim() != 5:
+            raise WXEngineError("sp must be a [B, 1, n_time, H, W] tensor")
+        B, _, nT = sp.shape[:3]
+        for name, t, nl in named:
+            if t is None:
+                continue
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 5):
+                raise WXEngineError(f"{name} must be a float32 [B, n_levels, n_time, H, W] tensor on the GPU")
+            if t.device.index != self.device:
+                raise WXEngineError(f"{name} is on cuda:{t.device.index} but this block was created for cuda:{self.device}")
+            if nl == self.L and t.shape[1] != self.L:
+                raise WXEngineError(f"n_levels mismatch: {name} has {t.shape[1]} levels, the block was created for {self.L}")
+            want = (B, nl, nT, self.H, self.W)
+            if name == "phis":
+                if t.shape[0] not in (1, B) or t.shape[2] not in (1, nT) or (t.shape[1], t.shape[3], t.shape[4]) != (1, self.H, self.W):
+                    raise WXEngineError(f"phis has shape {tuple(t.shape)}, expected [{B} or 1, 1, {nT} or 1, {self.H}, {self.W}]")
+            elif tuple(t.shape) != want:
+                raise WXEngineError(f"{name} has shape {tuple(t.shape)}, expected {list(want)}")
+        kw = dict(dtype=torch.float32, device=sp.device)
+        out = {}
+        if want_z:
+            out["z"] = torch.empty((B, self.L, nT, self.H, self.W), **kw)
+        if want_plev:
+            out["plev"] = [torch.empty((B, getattr(self, "n_plev", 0) or 1, nT, self.H, self.W), **kw) for _ in range(len(fields) + 2)]
+        if want_mslp:
+            out["mslp"] = torch.empty((B, 1, nT, self.H, self.W), **kw)
+        ins = [t for _, t, _ in named if t is not None]
+        whole = all(t.is_contiguous() for t in ins) and phis.shape[0] == B
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        for b in ([None] if whole else range(B)):
+            def item(t, shared=False):
+                if t is None or b is None:
+                    return t
+                t = t[0:1] if (shared and t.shape[0] == 1) else t[b:b + 1]
+                if not t.is_contiguous():
+                    raise WXEngineError("a batch item of every input must be contiguous [n_levels, n_time, H, W] memory")
+                return t
+            z_arg = item(out["z"]) if want_z else (item(z_in) if want_plev else None)
+            f_arr = (C.c_void_p * max(len(fields), 1))(*[item(f).data_ptr() for f in fields])
+            p_arr = (C.c_void_p * (len(fields) + 2))(*[item(t).data_ptr() for t in out["plev"]]) if want_plev else None
+            q_arg = None if (z_in is not None and not want_z) else q
+            with torch.cuda.device(self.device):
+                _check(self.lib.wx_diag_apply(self._d, B if b is None else 1, nT, ptr(item(T)), ptr(item(q_arg)), ptr(item(sp)),
+                                              ptr(item(phis, shared=True)), int(phis.shape[2]), ptr(item(t_ns)), f_arr, len(fields),
+                                              ptr(z_arg), p_arr, ptr(item(out["mslp"])) if want_mslp else None, stream))
+        return out

@@ -110,6 +110,7 @@ def run_forecast(model, ic_batch: dict, forcing_batches: Iterable[dict], n_steps
     import torch
     full: dict = {"ic_preprocessed": {"input": ic_batch["input"]}, "x_physical": ic_batch["input"],
                   "metadata": {"target": {"_channel_map": target_channel_map}}}
+    full["ic_raw"] = ic_batch["input"]   # rollout_utils.py:261: where the diagnostics blocks find the static fields (PHIS)
     pre = DevicePreblock(ic_batch["input"], mean, std)   # lives on the device of the IC tensors
     router = RolloutRouter(ic_batch["input"])
     full["metadata"]["input"] = {"_channel_map": pre.channel_map}

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag]
 """
 import argparse
 import os
@@ -747,6 +747,110 @@ def conservation_golden():
     np.savez_compressed(os.path.join(GOLD, "conservation_gen2.npz"), **out)
 
 
+def diag_golden():
+    """Pressure-level products: the reference's GeopotentialDiagnostic -> PressureInterpDiagnostic -> MSLPDiagnostic chain (and with
+    them its three column functions, credit/postblock/{geopotential,pressure_interp,mslp}.py) run unmodified in fp32 and in fp64 on
+    every case of tests/diag_cases.py.  The classes read their coefficients through xarray, which is absent: a stand-in `xarray`
+    module in sys.modules whose open_dataset serves the case's arrays takes its place.  Written per case: diag_<case>.npz (the 2-D
+    inputs, coefficients, SHA-256 of every regenerated input, the fp32 outputs and d_ref = the reference's own fp32-against-fp64
+    distance per output variable) and diag_<case>_f64.npz (the fp64 outputs as float32 differences from the fp32 ones).
+    The generator refuses to write a fixture in which a discrete choice could flip between fp32 and fp64."""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from diag_cases import DIAG_CASES, FIELD_ORDER, KEYS, SRC, case_inputs, distance, input_digest, output_names
+    coef = {}
+
+    class _DS:
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+        def __getitem__(self, name):
+            return types.SimpleNamespace(values=coef[name])
+    standin = types.ModuleType("xarray")
+    standin.open_dataset = lambda _path, **_kw: _DS()
+    sys.modules["xarray"] = standin
+    import credit.postblock.geopotential as RG
+    import credit.postblock.mslp as RM
+    import credit.postblock.pressure_interp as RP
+    RG.xr = RP.xr = standin   # in case an earlier item of this run imported them over the hollow stand-in
+
+    for name, c in DIAG_CASES.items():
+        inp = case_inputs(name)
+        coef.update(a_half=inp["a_half"], b_half=inp["b_half"], a_model=inp["a_mid"], b_model=inp["b_mid"])
+        fields = [KEYS[f] for f in FIELD_ORDER[:c["n_fields"]]]
+        blocks = [RG.GeopotentialDiagnostic(output_name=KEYS["z"], surface_geopotential_var=KEYS["phis"], surface_pressure_var=KEYS["sp"],
+                                            temperature_var=KEYS["T"], specific_humidity_var=KEYS["q"], flip_vertical=c["flip_vertical"]),
+                  RP.PressureInterpDiagnostic(pressure_levels=c["plev"], interp_variables=fields, temperature_var=KEYS["T"],
+                                              geopotential_var=KEYS["z"], surface_pressure_var=KEYS["sp"],
+                                              surface_geopotential_var=KEYS["phis"]),
+                  RM.MSLPDiagnostic(output_name=KEYS["mslp"], surface_pressure_var=KEYS["sp"], temperature_var=KEYS["t2m"],
+                                    surface_geopotential_var=KEYS["phis"])]
+        res = {}
+        for dtype in (torch.float32, torch.float64):
+            t = {k: torch.from_numpy(inp[k]).to(dtype) for k in ("T", "q", "u", "v", "sp", "t2m", "phis")}
+            batch = {"y_processed": {SRC: {KEYS[k]: t[k] for k in ("T", "q", "u", "v", "sp", "t2m")}},
+                     # GeopotentialDiagnostic.forward flattens PHIS without expanding it (geopotential.py:205-209), so the reference
+                     # gets the static plane repeated over n_time; the device blocks take it with n_time == 1
+                     "ic_raw": {SRC: {KEYS["phis"]: t["phis"].expand(-1, -1, c["T"], -1, -1)}}}
+            with torch.no_grad():
+                for blk in blocks:
+                    batch = blk(batch)
+            y = batch["y_processed"][SRC]
+            pres = lambda k: y[f"{SRC}/derived_diagnostic/3d/{KEYS[k].split('/')[-1]}_PRES"]   # noqa: E731
+            out = {"z_model": y[KEYS["z"]], "mslp": y[KEYS["mslp"]], "plev_T": pres("T"), "plev_Z": pres("z")}
+            for f in FIELD_ORDER[:c["n_fields"]]:
+                out[f"plev_{f}"] = pres(f)
+            assert all(v.dtype == dtype for v in out.values()), name
+            res[dtype] = {k: v.contiguous().numpy() for k, v in out.items()}
+        # ---- no discrete choice may flip between the two precisions
+        th = 150.0
+        picks = []
+        for dtype in (torch.float32, torch.float64):
+            z = torch.from_numpy(res[dtype]["z_model"])
+            d = torch.abs((z - torch.from_numpy(inp["phis"]).to(dtype)) / 9.80665 - th)
+            if c["s2t"]:
+                d = d.flip(1)
+            picks.append(torch.argmin(d, dim=1))
+            two = torch.sort(d, dim=1).values[:, :2]
+            assert float((two[:, 1] - two[:, 0]).min()) >= 0.5, f"{name}: two levels within 0.5 m of being nearest to {th} m"
+        assert torch.equal(picks[0], picks[1]), f"{name}: fp32 and fp64 choose different temp_height levels"
+        for dt in (np.float32, np.float64):
+            sh = inp["phis"].astype(dt) / dt(9.80665)
+            assert min(np.abs(sh - 2000.0).min(), np.abs(sh - 2500.0).min()) >= 0.01, f"{name}: a surface height sits on a regime boundary"
+            t2 = inp["t2m"].astype(dt)
+            tto = t2 + dt(0.0065) * sh
+            for thr in (290.5, 255.0):
+                assert min(np.abs(t2 - thr).min(), np.abs(tto - thr).min()) >= 1e-3, f"{name}: a temperature sits on {thr} K"
+        sh = inp["phis"] / np.float32(9.80665)
+        t2, hb = inp["t2m"], np.broadcast_to(sh, inp["t2m"].shape)
+        cover = {"phis == 0": (inp["phis"] == 0).any(), "< 2000 m": ((sh > 0) & (sh < 2000)).any(), "2000 - 2500 m": ((sh >= 2000) & (sh <= 2500)).any(),
+                 "> 2500 m": (sh > 2500).any(), "mslp case 1": ((t2 <= 290.5) & (t2 + 0.0065 * hb > 290.5)).any(), "mslp warm": (t2 > 290.5).any(),
+                 "mslp cold": (t2 < 255.0).any(), "below ground": (inp["plev_pa"].max() > inp["sp"]).any(), "sp range": inp["sp"].min() < 56000 and inp["sp"].max() > 100000}
+        assert all(cover.values()), (name, cover)
+        fix = {k: inp[k] for k in ("sp", "t2m", "phis", "a_half", "b_half", "a_mid", "b_mid", "plev_pa")}
+        f64 = {}
+        for k in ("T", "q", "u", "v", "sp", "t2m", "phis"):
+            fix[f"sha256:{k}"] = np.array(input_digest(inp[k]))
+        d_ref = {}
+        for v in output_names(name):
+            a32, a64 = res[torch.float32][v], res[torch.float64][v]
+            assert np.isfinite(a32).all() and np.isfinite(a64).all(), (name, v)
+            fix[f"f32:{v}"] = a32
+            f64[f"d64:{v}"] = (a64 - a32.astype(np.float64)).astype(np.float32)
+            d_ref[v] = distance(a32, a64)
+            fix[f"d_ref:{v}"] = np.float64(d_ref[v])
+        np.savez_compressed(os.path.join(GOLD, f"diag_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"diag_{name}_f64.npz"), **f64)
+        sizes = [os.path.getsize(os.path.join(GOLD, f"diag_{name}{s}.npz")) for s in ("", "_f64")]
+        assert max(sizes) < 1000000, (name, sizes)
+        print(f"[golden] diag {name}: {inp['sp'].size} columns, files {sizes[0] // 1024} + {sizes[1] // 1024} KB, T range "
+              f"{res[torch.float32]['plev_T'].min():.1f} .. {res[torch.float32]['plev_T'].max():.1f} K, d_ref "
+              + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()))
+
+
 def reconstruct_golden():
     """Reconstruct -> FlattenToTensor of the reference (no scaler) on a synthetic y_pred + channel map."""
     from credit.postblock.reconstruct import FlattenToTensor, Reconstruct
@@ -1032,6 +1136,8 @@ def main():
             preblock_golden()
         elif item == "gen2":
             conservation_golden()
+        elif item == "diag":        # pressure-level products: geopotential, p-level interpolation, MSLP
+            diag_golden()
         elif item == "rec":
             reconstruct_golden()
         elif item == "asm":
