@@ -301,6 +301,54 @@ int wx_pre_create(int n_fields, const int32_t* n_levels, int frames, int H, int 
 int wx_pre_destroy(wx_pre_handle p);
 int wx_pre_channels(wx_pre_handle p, int* channels);
 int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, int batch, void* stream);
+
+/* ---- gen-2 variable transforms on the device (csrc/wx_pre.h pre_xform_kernel, csrc/wx_unxform.h) -------------------------------
+ * The per-step chains of the reference's gen-2 configs (config/gen_2/examples), fused around the two existing passes:
+ *   pre : fill_values* -> (log_transform | sqrt_transform)? -> bridgescaler_transform(transform) -> concat
+ *   post: reconstruct -> bridgescaler_transform(inverse_transform) -> (exp_transform | square_transform)?
+ *   wx_pre_set_transforms <-> FillValues.forward (credit/preblock/fill_values.py:120-171), LogTransform.forward
+ *                         (credit/preblock/log.py:84-105) and SqrtTransform.forward (credit/preblock/sqrt.py:52-71), applied by
+ *                         wx_pre_apply from then on, per OUTPUT channel c of the block (host arrays of wx_pre_channels entries):
+ *       n_rules[c]        0 .. 8 fill rules, rule k of channel c at [c * 8 + k] of rule_op (enum wx_fill_op) / rule_search /
+ *                         rule_fill.  Every mask is taken on the ORIGINAL value, a numeric rule never matches NaN, replacements
+ *                         happen in rule order (the last matching rule wins); rule_search is ignored for WX_FILL_NAN.  Rules of
+ *                         stacked FillValues blocks on one variable are NOT simply concatenated (a later block sees the earlier
+ *                         block's output): the host composes them, see wxengine/transforms.py.
+ *       kind[c]           enum wx_xform: then log_base(x + eps[c]) - log_eps[c] (base e / 2 / 10, the float32 sum's logarithm
+ *                         correctly rounded) or sqrtf(x); eps and log_eps are the reference's Python floats rounded to float32, as adding
+ *                         them to a float32 tensor rounds them.  x < -eps and the root of a negative give NaN as in the reference.
+ *       then the block's (v - mean) / max(std, 1e-12) and the store.  A block without a table runs the plain kernel, bit for bit.
+ *     WX_ERR_INVALID with the reason in wx_last_error(): a null pointer, an unknown kind or op, more than 8 rules, eps <= 0 (or a
+ *     non-finite eps / log_eps) on a log channel.
+ *   wx_unxform_create / wx_unxform_destroy <-> ExpTransform.__init__ (credit/postblock/exp.py:38-62), SquareTransform.__init__
+ *                         (credit/postblock/square.py:36-40) and the scaler's statistics, for a list of n_vars <= 64 variables with
+ *                         n_levels[v] levels on an H x W grid: kind[v] (enum wx_xform, inverse direction), eps[v] / log_eps[v]
+ *                         (float32 roundings as above), has_stats[v] and mean / std with one entry per (variable, level) in
+ *                         variable order (entries of variables without statistics are ignored; both NULL when none has any).
+ *   wx_unxform_apply      <-> the scaler's inverse_transform, ExpTransform.forward (exp.py:73-88) and SquareTransform.forward
+ *                         (square.py:42-57) of all the variables in ONE launch: p = y * std + mean (a rounded product, then a rounded
+ *                         sum; skipped where has_stats[v] == 0), then e^(p + log_eps) - eps | 2^(.) - eps | pow(10, .) - eps | p * p.
+ *       src_dev[v]        batch item b at src_dev[v] + b * batch_stride[v] floats: [n_levels[v]][n_time][H][W] contiguous -- the
+ *                         channel-slice views Reconstruct makes of y_pred are read where they lie; never modified
+ *       dst_dev[v]        [batch][n_levels[v]][n_time][H][W] contiguous, written
+ *     16-byte accesses where H * W % 4 == 0 and both pointers of a plane sit on 16 bytes, 4-byte accesses otherwise. */
+enum wx_xform {
+  WX_XFORM_NONE = 0,
+  WX_XFORM_LOG_E = 1,      /* pre: ln(x + eps) - ln(eps)         post: e^(p + ln eps) - eps */
+  WX_XFORM_LOG_2 = 2,      /* pre: log2(x + eps) - log2(eps)     post: 2^(p + log2 eps) - eps */
+  WX_XFORM_LOG_10 = 3,     /* pre: log10(x + eps) - log10(eps)   post: pow(10, p + log10 eps) - eps */
+  WX_XFORM_SQRT = 4        /* pre: sqrt(x)                       post: p * p */
+};
+enum wx_fill_op { WX_FILL_NAN = 0, WX_FILL_EQ = 1, WX_FILL_NE = 2, WX_FILL_LT = 3, WX_FILL_LE = 4, WX_FILL_GT = 5, WX_FILL_GE = 6 };
+#define WX_MAX_FILL_RULES 8
+int wx_pre_set_transforms(wx_pre_handle p, const int32_t* kind, const float* eps, const float* log_eps, const int32_t* n_rules,
+                          const int32_t* rule_op, const float* rule_search, const float* rule_fill);
+typedef struct wx_unxform* wx_unxform_handle;
+int wx_unxform_create(int n_vars, const int32_t* n_levels, int H, int W, const int32_t* kind, const float* eps, const float* log_eps,
+                      const int32_t* has_stats, const float* mean, const float* std, int device, wx_unxform_handle* out);
+int wx_unxform_destroy(wx_unxform_handle u);
+int wx_unxform_apply(wx_unxform_handle u, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch,
+                     int n_time, void* stream);
 int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx_post_handle* out);
 int wx_post_destroy(wx_post_handle p);
 int wx_post_set_grid(wx_post_handle p, const float* lat2d, const float* lon2d, const float* p_levels, int n_levels,

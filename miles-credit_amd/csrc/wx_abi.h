@@ -247,6 +247,47 @@ int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, 
     p->impl->apply(fields_dev, x_dev, batch, (hipStream_t)stream);
   });
 }
+int wx_pre_set_transforms(wx_pre_handle p, const int32_t* kind, const float* eps, const float* log_eps, const int32_t* n_rules,
+                          const int32_t* rule_op, const float* rule_search, const float* rule_fill) {
+  return guarded([&] {
+    if (!p || !p->impl) throw wx::ConfigError("wx_pre_set_transforms: null pre-block handle");
+    if (!kind || !eps || !log_eps || !n_rules || !rule_op || !rule_search || !rule_fill) throw wx::ConfigError("wx_pre_set_transforms: null argument");
+    remap<wx::ConfigError>([&] { p->impl->set_transforms(kind, eps, log_eps, n_rules, rule_op, rule_search, rule_fill); });
+  });
+}
+// ---- inverse scale + inverse transforms of named tensors (csrc/wx_unxform.h) ----------------------------------------------------
+struct wx_unxform {
+  std::unique_ptr<wx::Unxform> impl;
+};
+int wx_unxform_create(int n_vars, const int32_t* n_levels, int H, int W, const int32_t* kind, const float* eps, const float* log_eps,
+                      const int32_t* has_stats, const float* mean, const float* stdv, int device, wx_unxform_handle* out) {
+  return guarded([&] {
+    if (!out || !n_levels || !kind || !eps || !log_eps || !has_stats) throw wx::ConfigError("wx_unxform_create: null argument");
+    if (n_vars < 1 || n_vars > wx::kMaxFields) throw wx::ConfigError("wx_unxform_create: 1..64 variables");
+    if (H < 1 || W < 1) throw wx::ConfigError("wx_unxform_create: bad geometry");
+    bool any_stats = false;
+    for (int v = 0; v < n_vars; ++v) {
+      if (n_levels[v] < 1) throw wx::ConfigError("wx_unxform_create: a variable needs at least one level");
+      if (kind[v] < wx::kUnxNone || kind[v] > wx::kUnxSquare) throw wx::ConfigError("wx_unxform_create: unknown transform kind " + std::to_string(kind[v]));
+      if (kind[v] >= wx::kUnxExpE && kind[v] <= wx::kUnxExp10 && !(eps[v] > 0.f && std::isfinite(eps[v]) && std::isfinite(log_eps[v])))
+        throw wx::ConfigError("wx_unxform_create: an exp transform needs a finite eps > 0 and its finite log");
+      any_stats = any_stats || has_stats[v] != 0;
+    }
+    if (any_stats && (!mean || !stdv)) throw wx::ConfigError("wx_unxform_create: statistics flagged but mean / std are null");
+    need_device(device, "wx_unxform_create");
+    std::unique_ptr<wx_unxform> u(new wx_unxform);
+    u->impl.reset(new wx::Unxform(n_vars, n_levels, H, W, kind, eps, log_eps, has_stats, any_stats ? mean : nullptr, any_stats ? stdv : nullptr, device));
+    *out = u.release();
+  });
+}
+int wx_unxform_destroy(wx_unxform_handle u) { return guarded([&] { delete u; }); }
+int wx_unxform_apply(wx_unxform_handle u, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch,
+                     int n_time, void* stream) {
+  return guarded([&] {
+    if (!u || !u->impl || !src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_unxform_apply: null argument");
+    remap<wx::ConfigError>([&] { u->impl->apply(src_dev, batch_stride, dst_dev, batch, n_time, (hipStream_t)stream); });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

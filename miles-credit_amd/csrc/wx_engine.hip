@@ -37,6 +37,7 @@
 #include "wx_fuxi.h"
 #include "wx_post.h"
 #include "wx_pre.h"
+#include "wx_unxform.h"
 #include "wx_diag.h"
 #include "wx_noise.h"
 #include "wx_options.h"

@@ -4,6 +4,16 @@
 // fused into one pass: every named field [B, n_levels, T, H, W] (fp32, device) is written normalised into its channel
 // slot of x [B, C, T, H, W].  HBM-bound copy: one float4 per thread, coalesced along longitude on both sides.
 // The channel ORDER (field-type rank, 3d before 2d, stable) is host logic: wxengine/preblock.py.
+//
+// With a transform table set (wx_pre_set_transforms) a second kernel, pre_xform_kernel, serves the gen-2 chain
+//   fill_values* -> (log_transform | sqrt_transform)? -> scaler -> concat
+// in the same single pass; per output channel, in this order:
+//   credit/preblock/fill_values.py:120-171  FillValues   up to 8 rules; every mask on the ORIGINAL value, numeric rules never match
+//                                                         NaN, replacements in rule order (the last matching rule wins)
+//   credit/preblock/log.py:84-105           LogTransform log_base(x + eps) - log_base(eps), base e / 2 / 10 (correctly rounded: see xform_forward)
+//   credit/preblock/sqrt.py:52-71           SqrtTransform sqrtf(x)
+// x < -eps and sqrt of a negative give NaN as in the reference (no fast-math).  The plain kernel is untouched and is the one that runs
+// when no table is set, so that path keeps its bits.
 #pragma once
 #include <vector>
 
@@ -22,6 +32,93 @@ struct PreParams {
   float* x;                        // [B][C][T][HW]
   int C, T, hw, batch;
 };
+
+constexpr int kMaxFillRules = 8;
+// enum wx_xform / wx_fill_op of include/wxengine.h
+enum { kXfNone = 0, kXfLogE = 1, kXfLog2 = 2, kXfLog10 = 3, kXfSqrt = 4 };
+enum { kFillNan = 0, kFillEq = 1, kFillNe = 2, kFillLt = 3, kFillLe = 4, kFillGt = 5, kFillGe = 6 };
+
+struct PreXform {
+  const int* kind;            // [C]
+  const float *eps, *log_eps; // [C] rounded to fp32 on the host (the reference adds Python floats to fp32 tensors)
+  const int* n_rules;         // [C] 0 .. kMaxFillRules
+  const int* rule_op;         // [C][kMaxFillRules]
+  const float *rule_search, *rule_fill;
+};
+
+__device__ __forceinline__ bool fill_match(int op, float x, float s) {
+  switch (op) {   // comparisons with a NaN x are false, != excepted: fill_values.py:155 ANDs every numeric mask with ~isnan
+    case kFillNan: return x != x;
+    case kFillEq: return x == s;
+    case kFillNe: return x != s && x == x;
+    case kFillLt: return x < s;
+    case kFillLe: return x <= s;
+    case kFillGt: return x > s;
+    default: return x >= s;
+  }
+}
+
+__device__ __forceinline__ float xform_forward(float v, int kind, float eps, float log_eps) {
+  switch (kind) {
+    // The sum v + eps is the reference's float32 sum; its logarithm is evaluated in double and rounded once, i.e. correctly rounded.
+    // The device logf / log2f / log10f are good to 1 ulp, and inside a forecast that is not enough: a variable that went out through
+    // e^(p + log_eps) - eps comes back within a few hundredths of an ulp of the float32 value it started from, the host's logarithm
+    // returns that value, and a 1-ulp miss here becomes a whole ulp of p (measured: 5.4e-4 of the normalised surface pressure at
+    // std 0.003, against 8.7e-5 between the reference's own fp32 and fp64).  The pass stays HBM-bound.
+    case kXfLogE: return (float)log((double)(v + eps)) - log_eps;
+    case kXfLog2: return (float)log2((double)(v + eps)) - log_eps;
+    case kXfLog10: return (float)log10((double)(v + eps)) - log_eps;
+    case kXfSqrt: return sqrtf(v);
+    default: return v;
+  }
+}
+
+// One plane (b, c, t) per blockIdx.y, four longitudes per thread like pre_assemble_kernel.  Every per-channel quantity is uniform in the
+// workgroup (scalar loads); the 16-byte path needs hw % 4 == 0 AND both plane pointers on 16 bytes (a field may be a view).
+__global__ __launch_bounds__(256) void pre_xform_kernel(const PreParams p, const PreXform t) {
+  const int64_t plane = (int64_t)blockIdx.y;
+  const int tt = (int)(plane % p.T);
+  const int c = (int)((plane / p.T) % p.C);
+  const int b = (int)(plane / ((int64_t)p.T * p.C));
+  const int f = p.ch_field[c], l = p.ch_level[c];
+  const float* __restrict__ src = p.field[f] + (((int64_t)b * p.f_levels[f] + l) * p.T + tt) * p.hw;
+  float* __restrict__ dst = p.x + plane * p.hw;
+  const float m = p.mean ? p.mean[c] : 0.f;
+  const float s = p.mean ? fmaxf(p.stdv[c], 1e-12f) : 1.f;
+  const int kind = t.kind[c], nr = t.n_rules[c];
+  const float eps = t.eps[c], log_eps = t.log_eps[c];
+  const int* __restrict__ rop = t.rule_op + (int64_t)c * kMaxFillRules;
+  const float* __restrict__ rs = t.rule_search + (int64_t)c * kMaxFillRules;
+  const float* __restrict__ rf = t.rule_fill + (int64_t)c * kMaxFillRules;
+  const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= p.hw) return;
+  const bool vec = (p.hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  const int n = vec ? 4 : min(4, p.hw - i);
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (vec) {
+    const float4 q = *reinterpret_cast<const float4*>(src + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    for (int k = 0; k < n; ++k) v[k] = src[i + k];
+  }
+  float r[4] = {v[0], v[1], v[2], v[3]};
+  for (int k = 0; k < nr; ++k) {
+    const int op = rop[k];
+    const float sv = rs[k], fv = rf[k];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r[j] = fill_match(op, v[j], sv) ? fv : r[j];   // mask on the original value v, not on r
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    r[j] = xform_forward(r[j], kind, eps, log_eps);
+    if (p.mean) r[j] = (r[j] - m) / s;
+  }
+  if (vec) {
+    *reinterpret_cast<float4*>(dst + i) = make_float4(r[0], r[1], r[2], r[3]);
+  } else {
+    for (int k = 0; k < n; ++k) dst[i + k] = r[k];
+  }
+}
 
 __global__ __launch_bounds__(256) void pre_assemble_kernel(const PreParams p) {
   const int64_t plane = (int64_t)blockIdx.y;           // (b, c, t)
@@ -67,6 +164,36 @@ class PreBlock {
     for (void* p : allocs) (void)hipFree(p);
   }
   int channels() const { return C; }
+  // per-output-channel arrays ([C], rules [C][kMaxFillRules]); from now on apply() launches pre_xform_kernel
+  void set_transforms(const int32_t* kind, const float* eps, const float* log_eps, const int32_t* n_rules, const int32_t* rule_op,
+                      const float* rule_search, const float* rule_fill) {
+    for (int c = 0; c < C; ++c) {
+      if (kind[c] < kXfNone || kind[c] > kXfSqrt) throw std::runtime_error("wx_pre_set_transforms: unknown transform kind " + std::to_string(kind[c]));
+      if (kind[c] >= kXfLogE && kind[c] <= kXfLog10 && !(eps[c] > 0.f && std::isfinite(eps[c]) && std::isfinite(log_eps[c])))
+        throw std::runtime_error("wx_pre_set_transforms: a log transform needs a finite eps > 0 and its finite log");
+      if (n_rules[c] < 0 || n_rules[c] > kMaxFillRules) throw std::runtime_error("wx_pre_set_transforms: 0 .. 8 fill rules per channel");
+      for (int k = 0; k < n_rules[c]; ++k)
+        if (rule_op[c * kMaxFillRules + k] < kFillNan || rule_op[c * kMaxFillRules + k] > kFillGe)
+          throw std::runtime_error("wx_pre_set_transforms: unknown fill rule op " + std::to_string(rule_op[c * kMaxFillRules + k]));
+    }
+    WX_HIP(hipSetDevice(device));
+    if (!xf.kind) {
+      xf.kind = (int*)alloc(C * sizeof(int)); xf.n_rules = (int*)alloc(C * sizeof(int));
+      xf.eps = (float*)alloc(C * sizeof(float)); xf.log_eps = (float*)alloc(C * sizeof(float));
+      xf.rule_op = (int*)alloc((size_t)C * kMaxFillRules * sizeof(int));
+      xf.rule_search = (float*)alloc((size_t)C * kMaxFillRules * sizeof(float));
+      xf.rule_fill = (float*)alloc((size_t)C * kMaxFillRules * sizeof(float));
+    }
+    const size_t nr = (size_t)C * kMaxFillRules;
+    WX_HIP(hipMemcpy((void*)xf.kind, kind, C * sizeof(int), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.n_rules, n_rules, C * sizeof(int), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.eps, eps, C * sizeof(float), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.log_eps, log_eps, C * sizeof(float), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.rule_op, rule_op, nr * sizeof(int), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.rule_search, rule_search, nr * sizeof(float), hipMemcpyHostToDevice));
+    WX_HIP(hipMemcpy((void*)xf.rule_fill, rule_fill, nr * sizeof(float), hipMemcpyHostToDevice));
+    has_xf = true;
+  }
   void apply(const float* const* fields, float* x, int batch, hipStream_t stream) {
     if (batch < 1) throw std::runtime_error("wx_pre_apply: batch < 1");
     WX_HIP(hipSetDevice(device));
@@ -78,7 +205,12 @@ class PreBlock {
     }
     p.ch_field = ch_field; p.ch_level = ch_level; p.f_levels = f_levels; p.mean = d_mean; p.stdv = d_std;
     p.x = x; p.C = C; p.T = T; p.hw = hw; p.batch = batch;
-    hipLaunchKernelGGL(pre_assemble_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * T)), dim3(256), 0, stream, p);
+    if (has_xf) {
+      if ((int64_t)batch * C * T > 65535) throw std::runtime_error("wx_pre_apply: batch * channels * frames exceeds 65535 planes");
+      hipLaunchKernelGGL(pre_xform_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * T)), dim3(256), 0, stream, p, xf);
+    } else {
+      hipLaunchKernelGGL(pre_assemble_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * T)), dim3(256), 0, stream, p);
+    }
     WX_HIP(hipGetLastError());
   }
 
@@ -88,6 +220,14 @@ class PreBlock {
   std::vector<void*> allocs;
   int *ch_field = nullptr, *ch_level = nullptr, *f_levels = nullptr;
   float *d_mean = nullptr, *d_std = nullptr;
+  PreXform xf = {};
+  bool has_xf = false;
+  void* alloc(size_t bytes) {
+    void* d = nullptr;
+    WX_HIP(hipMalloc(&d, bytes));
+    allocs.push_back(d);
+    return d;
+  }
   void* up(const void* src, size_t bytes) {
     void* d = nullptr;
     WX_HIP(hipMalloc(&d, bytes));

@@ -102,6 +102,12 @@ _PROTOTYPES = {
     "wx_pre_destroy": ([C.c_void_p], C.c_int),
     "wx_pre_channels": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
     "wx_pre_apply": ([C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "wx_pre_set_transforms": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)], C.c_int),
+    "wx_unxform_create": ([C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                           C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_unxform_destroy": ([C.c_void_p], C.c_int),
+    "wx_unxform_apply": ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p], C.c_int),
     "wx_post_set_grid": ([C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int], C.c_int),
     "wx_post_set_grid_sigma": ([C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                 C.c_int, C.c_int, C.c_int], C.c_int),

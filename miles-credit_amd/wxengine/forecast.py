@@ -2,9 +2,10 @@
 credit/trainers/rollout_utils.py::run_forecast (:204-319) and the routing contract of ::assemble_rollout_batch (:322-430).
 
 Per step, with every tensor resident in HBM:
-    x --model--> y_pred --Reconstruct--> named y (views) --InverseScale--> physical --fixers--> y_processed --consume-->
+    x --model--> y_pred --Reconstruct--> named y (views) --InverseScale | InverseTransforms (inverse scale + exp / square, one
+    kernel)--> physical --fixers, diagnostics--> y_processed --consume-->
     assemble_rollout_batch(prognostic/diagnostic <- y_processed, dynamic_forcing <- this step's batch, static <- IC)
-    --DevicePreblock (normalise + concatenate, one kernel)--> x
+    --DevicePreblock ([fill -> log | sqrt ->] normalise + concatenate, one kernel)--> x
 The chain of post blocks is a list of callables on the batch dict, exactly like the reference's `apply_postblocks`.
 """
 from __future__ import annotations
@@ -103,15 +104,17 @@ class InverseScale:
 
 def run_forecast(model, ic_batch: dict, forcing_batches: Iterable[dict], n_steps: int, target_channel_map: Dict,
                  mean: Optional[Dict], std: Optional[Dict], step_postblocks: List[Callable[[dict], dict]],
-                 consume: Callable[[dict, int], None]) -> dict:
+                 consume: Callable[[dict, int], None], pre_transforms: Optional[List] = None) -> dict:
     """rollout_utils.py:204-319 with the engine's device blocks.  `ic_batch["input"]` / the forcing batches hold PHYSICAL named
     tensors [B, n_levels, T, H, W]; `step_postblocks` runs after `Reconstruct` (e.g. InverseScale, the conservation fixers);
-    `consume(y_processed, step)` stands in for `save_output_fn`.  Returns the final state dict."""
+    `consume(y_processed, step)` stands in for `save_output_fn`; `pre_transforms`: the FillValues / LogTransform / SqrtTransform
+    descriptors of wxengine/transforms.py that run in front of the normalisation at every step (their inverses, ExpTransform /
+    SquareTransform / InverseTransforms, go into `step_postblocks`).  Returns the final state dict."""
     import torch
     full: dict = {"ic_preprocessed": {"input": ic_batch["input"]}, "x_physical": ic_batch["input"],
                   "metadata": {"target": {"_channel_map": target_channel_map}}}
     full["ic_raw"] = ic_batch["input"]   # rollout_utils.py:261: where the diagnostics blocks find the static fields (PHIS)
-    pre = DevicePreblock(ic_batch["input"], mean, std)   # lives on the device of the IC tensors
+    pre = DevicePreblock(ic_batch["input"], mean, std, transforms=pre_transforms)   # lives on the device of the IC tensors
     router = RolloutRouter(ic_batch["input"])
     full["metadata"]["input"] = {"_channel_map": pre.channel_map}
     full["x"] = pre(ic_batch["input"])

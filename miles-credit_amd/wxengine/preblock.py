@@ -7,7 +7,10 @@ prognostic < static < dynamic_forcing < diagnostic from `credit/datasets/gen_2/c
 otherwise insertion order -- Python's sort is stable), normalises them like
 `credit/preblock/norm.py::ERA5Normalizer._normalize_tensor` (:78-98) and concatenates along the channel dim like
 `ConcatToTensor.forward` (:96-207) -- the last two in ONE kernel pass through the C ABI (`wx_pre_*`).  It also returns the
-reference's `_channel_map` (var_key -> {"slice", "orig_shape"}).  No CPU fallback.
+reference's `_channel_map` (var_key -> {"slice", "orig_shape"}).  With `transforms=[...]` (the FillValues / LogTransform /
+SqrtTransform descriptors of wxengine/transforms.py) the same single pass also fills and log- / sqrt-transforms the selected
+variables in front of the normalisation: the gen-2 chain fill_values -> log_transform | sqrt_transform -> scaler -> concat.
+No CPU fallback.
 """
 from __future__ import annotations
 
@@ -60,8 +63,10 @@ def channel_stats(keys, levels, mean: Optional[Dict], std: Optional[Dict]):
 
 class DevicePreblock:
     def __init__(self, example_input: Dict[str, Dict], mean: Optional[Dict] = None, std: Optional[Dict] = None,
-                 device: Optional[int] = None):
-        """`device`: GPU index the block lives on; default = the device of the example tensors when they are on a GPU, else the
+                 device: Optional[int] = None, transforms=None):
+        """`transforms`: descriptors in chain order, compiled against `example_input` (wxengine/transforms.py::compile_channel_table;
+        orders the fused kernel does not serve are a ValueError here).  None or [] = the plain normalise + concatenate kernel.
+        `device`: GPU index the block lives on; default = the device of the example tensors when they are on a GPU, else the
         current device (rank r of a replicas run works on cuda:r -- a block pinned to GPU 0 would launch on another device's
         stream there)."""
         import torch
@@ -87,12 +92,19 @@ class DevicePreblock:
             self.channel_map[k] = {"slice": slice(cur, cur + nl * self.T), "orig_shape": (nl, self.T)}
             cur += nl * self.T
         self.channels = sum(self.levels)
+        from .transforms import compile_channel_table
+        self.transform_table = compile_channel_table(transforms, example_input, self.keys, self.levels) if transforms else None
         lv = (C.c_int32 * len(self.levels))(*self.levels)
         fp = C.POINTER(C.c_float)
         self._p = C.c_void_p()
         _check(self.lib.wx_pre_create(len(self.levels), lv, self.T, self.H, self.W,
                                       self.mean.ctypes.data_as(fp) if self.mean is not None else None,
                                       self.std.ctypes.data_as(fp) if self.std is not None else None, self.device, C.byref(self._p)))
+        if self.transform_table is not None:
+            t, ip = self.transform_table, C.POINTER(C.c_int32)
+            _check(self.lib.wx_pre_set_transforms(self._p, t["kind"].ctypes.data_as(ip), t["eps"].ctypes.data_as(fp), t["log_eps"].ctypes.data_as(fp),
+                                                  t["n_rules"].ctypes.data_as(ip), t["rule_op"].ctypes.data_as(ip),
+                                                  t["rule_search"].ctypes.data_as(fp), t["rule_fill"].ctypes.data_as(fp)))
 
     def __del__(self):
         try:

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform]
 """
 import argparse
 import os
@@ -851,6 +851,79 @@ def diag_golden():
               + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()))
 
 
+def xform_golden():
+    """Variable transforms: the reference's own FillValues / LogTransform / SqrtTransform (credit/preblock/{fill_values,log,sqrt}.py)
+    and ExpTransform / SquareTransform (credit/postblock/{exp,square}.py) run unmodified, stacked as the cases of tests/xform_cases.py
+    say, in fp32 and in fp64.  The scaler legs between them are NOT the reference's class: bridgescaler is not installed, so
+    bridgescaler_transform cannot be run; they are the expressions already pinned for DevicePreblock and InverseScale,
+    (t - mean) / std.clamp(min=1e-12) (credit/preblock/norm.py:98) and t * std + mean, with float32 statistics.  Written per case:
+    xform_<case>.npz (SHA-256 of every regenerated input, the fp32 outputs "f32:pre:<var>" / "f32:post:<var>" and d_ref = the
+    reference's own fp32-against-fp64 distance per variable AND level, NaN positions excluded) and xform_<case>_f64.npz (the fp64
+    outputs as float32 differences from the fp32 ones).  Refused: a level with 1 % NaN or more, a designated NaN case without one,
+    NaN positions that differ between the two precisions."""
+    import types
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from credit.postblock.exp import ExpTransform
+    from credit.postblock.square import SquareTransform
+    from credit.preblock.fill_values import FillValues
+    from credit.preblock.log import LogTransform
+    from credit.preblock.sqrt import SqrtTransform
+    from xform_cases import (SRC, XFORM_CASES, batch_input, case_inputs, case_stats, input_digest, level_distance, out_variables, post_blocks,
+                             pre_blocks, target_channel_map)
+    ref = types.SimpleNamespace(FillValues=FillValues, LogTransform=LogTransform, SqrtTransform=SqrtTransform, ExpTransform=ExpTransform,
+                                SquareTransform=SquareTransform)
+    for name, c in XFORM_CASES.items():
+        fields, y_pred = case_inputs(name)
+        mean, std = case_stats(name)
+        res = {}
+        for dtype in (torch.float32, torch.float64):
+            st = lambda a: torch.as_tensor(np.asarray(a, np.float32)).to(dtype).reshape(1, -1, 1, 1, 1)   # noqa: E731
+            batch = {"input": batch_input(name, fields, lambda a: torch.from_numpy(a).to(dtype))}
+            with torch.no_grad():
+                for blk in pre_blocks(name, ref):
+                    batch = blk(batch)
+                out = {}
+                for v in c["variables"]:
+                    t = batch["input"][SRC][v["key"]]
+                    if v["name"] in mean:
+                        t = (t - st(mean[v["name"]])) / st(std[v["name"]]).clamp(min=1e-12)
+                    out[f"pre:{v['name']}"] = t
+                y = torch.from_numpy(y_pred).to(dtype).flatten(1, 2)
+                nested = {SRC: {}}
+                for key, info in target_channel_map(name).items():
+                    t = y[:, info["slice"]].unflatten(1, info["orig_shape"])
+                    n = key.split("/")[-1]
+                    nested[SRC][key] = t * st(std[n]) + st(mean[n]) if n in mean else t
+                full = {"y_processed": nested}
+                for blk in post_blocks(name, ref):
+                    full = blk(full)
+                for v in out_variables(name):
+                    out[f"post:{v['name']}"] = full["y_processed"][SRC][v["key"]]
+            assert all(t.dtype == dtype for t in out.values()), name
+            res[dtype] = {k: t.contiguous().numpy() for k, t in out.items()}
+        fix, f64, n_nan, worst = {}, {}, 0, 0.0
+        for v in c["variables"]:
+            fix[f"sha256:in:{v['name']}"] = np.array(input_digest(fields[v["key"]]))
+        fix["sha256:y_pred"] = np.array(input_digest(y_pred))
+        for k in res[torch.float32]:
+            a32, a64 = res[torch.float32][k], res[torch.float64][k]
+            share = np.isnan(a32).mean(axis=(0, 2, 3, 4))
+            assert share.max() < 0.01, (name, k, share)
+            n_nan += int(np.isnan(a32).sum())
+            d = level_distance(a32, a64)
+            assert np.isfinite(d).all(), f"{name} {k}: NaN positions differ between fp32 and fp64"
+            fix[f"f32:{k}"] = a32
+            f64[f"d64:{k}"] = np.nan_to_num(a64 - a32.astype(np.float64), nan=0.0).astype(np.float32)
+            fix[f"d_ref:{k}"] = d
+            worst = max(worst, d.max())
+        assert (n_nan > 0) == c["nan_case"], (name, n_nan)
+        np.savez_compressed(os.path.join(GOLD, f"xform_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"xform_{name}_f64.npz"), **f64)
+        sizes = [os.path.getsize(os.path.join(GOLD, f"xform_{name}{s}.npz")) for s in ("", "_f64")]
+        assert max(sizes) < 1000000, (name, sizes)
+        print(f"[golden] xform {name}: {len(res[torch.float32])} outputs, {n_nan} NaN, files {sizes[0] // 1024} + {sizes[1] // 1024} KB, worst d_ref {worst:.2e}")
+
+
 def reconstruct_golden():
     """Reconstruct -> FlattenToTensor of the reference (no scaler) on a synthetic y_pred + channel map."""
     from credit.postblock.reconstruct import FlattenToTensor, Reconstruct
@@ -1138,6 +1211,8 @@ def main():
             conservation_golden()
         elif item == "diag":        # pressure-level products: geopotential, p-level interpolation, MSLP
             diag_golden()
+        elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
+            xform_golden()
         elif item == "rec":
             reconstruct_golden()
         elif item == "asm":
