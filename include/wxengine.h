@@ -416,6 +416,38 @@ int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const
                   int phis_n_time, const float* t_near_surface, const float* const* fields, int n_fields, float* z_model_out,
                   float* const* plev_out, float* mslp_out, void* stream);
 
+/* ---- wind artifact filter on the device (csrc/wx_wind.h) ------------------------------------------------------------------------
+ * credit/postblock/wind_filter.py in at most four launches, whatever the number of variables and levels; float32 throughout.
+ *   wx_wind_create / wx_wind_destroy <-> WindArtifactFilter.__init__ (wind_filter.py:175-204) and the kernels _compute_blend_mask
+ *                         builds at every call (:51-82).  The normalised 1-D Gaussians are computed by the caller with the reference's
+ *                         float32 expressions and passed as HOST arrays: smooth_lat / smooth_lon (size int(6 sigma + 1) | 1 per axis),
+ *                         falloff_lat (sigma falloff_sigma, size int(4 sigma + 1) | 1) / falloff_lon (sigma 2 falloff_sigma, size
+ *                         int(8 sigma + 1) | 1); the 2-D outer products are never formed.  dilation_lat x dilation_lon: the rectangle of
+ *                         ones (dilation_meridional x dilation_zonal).  WX_ERR_INVALID with the reason: an even or non-positive size
+ *                         (the reference itself fails on an even dilation: its dilated mask comes out one row or column larger than the
+ *                         field), a size above 33 along latitude or 65 along longitude, a non-finite weight or threshold, H or W < 1.
+ *   wx_wind_apply         <-> WindArtifactFilter.forward (:206-252):
+ *       u_dev, v_dev      the mask-level PLANE of U and V: batch item b at u_dev + b * u_batch_stride floats, [H][W] contiguous
+ *       src_dev[v]        batch item b at src_dev[v] + b * batch_stride[v] floats: [n_levels[v]][H][W] contiguous (n_time == 1), read
+ *                         where it lies -- channel slices of y_pred included -- and never modified; n_vars <= 32, n_levels[v] <= 256
+ *       dst_dev[v]        [batch][n_levels[v]][H][W] contiguous, written completely: level l of target_levels (those beyond
+ *                         n_levels[v] are skipped, :229-236) becomes m fs + (1 - m) f with fs = the zero-padded Gaussian smoothing of f,
+ *                         times min(sqrt(sum m f^2 / (sum m fs^2 + 1e-12)), 4) per batch item and plane when preserve_amplitude; every
+ *                         other level is copied.  Must not overlap any input.
+ *       mask_out_dev      [batch][H][W]: the blend mask m, or NULL (it then stays in the handle's own buffer)
+ *     The mask is complete before any output is written (U and V may be targets); the amplitude sums are double partials added in a
+ *     fixed order, so repeated calls give identical bits; a point with m == 0 keeps the bits of its input.  16-byte accesses where
+ *     W % 4 == 0 and the plane pointer sits on 16 bytes, 4-byte accesses otherwise (the same results).  batch * sum(n_levels) *
+ *     ceil(H / 16) * ceil(W / 64) must stay below 2^31. */
+typedef struct wx_wind* wx_wind_handle;
+int wx_wind_create(int H, int W, const float* smooth_lat, int n_smooth_lat, const float* smooth_lon, int n_smooth_lon,
+                   const float* falloff_lat, int n_falloff_lat, const float* falloff_lon, int n_falloff_lon, int dilation_lat,
+                   int dilation_lon, float speed_threshold, int preserve_amplitude, int device, wx_wind_handle* out);
+int wx_wind_destroy(wx_wind_handle f);
+int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride, int n_vars,
+                  const float* const* src_dev, const int64_t* batch_stride, const int32_t* n_levels, float* const* dst_dev,
+                  const int32_t* target_levels, int n_target_levels, int batch, float* mask_out_dev, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

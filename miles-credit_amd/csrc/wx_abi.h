@@ -288,6 +288,38 @@ int wx_unxform_apply(wx_unxform_handle u, const float* const* src_dev, const int
     remap<wx::ConfigError>([&] { u->impl->apply(src_dev, batch_stride, dst_dev, batch, n_time, (hipStream_t)stream); });
   });
 }
+// ---- wind artifact filter (jet mask, masked Gaussian blend; csrc/wx_wind.h) -----------------------------------------------------
+struct wx_wind {
+  std::unique_ptr<wx::Wind> impl;
+};
+int wx_wind_create(int H, int W, const float* smooth_lat, int n_smooth_lat, const float* smooth_lon, int n_smooth_lon,
+                   const float* falloff_lat, int n_falloff_lat, const float* falloff_lon, int n_falloff_lon, int dilation_lat,
+                   int dilation_lon, float speed_threshold, int preserve_amplitude, int device, wx_wind_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_wind_create: null argument");
+    const float* const w[4] = {smooth_lat, smooth_lon, falloff_lat, falloff_lon};
+    const int n[4] = {n_smooth_lat, n_smooth_lon, n_falloff_lat, n_falloff_lon};
+    const std::string why = wx::wind_check_create(H, W, w, n, dilation_lat, dilation_lon, speed_threshold);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_wind_create: " + why);
+    need_device(device, "wx_wind_create");
+    std::unique_ptr<wx_wind> f(new wx_wind);
+    f->impl.reset(new wx::Wind(H, W, w, n, dilation_lat, dilation_lon, speed_threshold, preserve_amplitude != 0, device));
+    *out = f.release();
+  });
+}
+int wx_wind_destroy(wx_wind_handle f) { return guarded([&] { delete f; }); }
+int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride, int n_vars,
+                  const float* const* src_dev, const int64_t* batch_stride, const int32_t* n_levels, float* const* dst_dev,
+                  const int32_t* target_levels, int n_target_levels, int batch, float* mask_out_dev, void* stream) {
+  return guarded([&] {
+    if (!f || !f->impl) throw wx::ConfigError("wx_wind_apply: null wind-filter handle");
+    if (!u_dev || !v_dev || !src_dev || !batch_stride || !n_levels || !dst_dev) throw wx::ConfigError("wx_wind_apply: null argument");
+    remap<wx::ConfigError>([&] {
+      f->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, n_vars, src_dev, batch_stride, n_levels, dst_dev, target_levels,
+                     n_target_levels, batch, mask_out_dev, (hipStream_t)stream);
+    });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind]
 """
 import argparse
 import os
@@ -851,6 +851,62 @@ def diag_golden():
               + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()))
 
 
+def wind_golden():
+    """Wind artifact filter: the reference's WindArtifactFilter (credit/postblock/wind_filter.py) run unmodified in fp32, and its two
+    helpers `_compute_blend_mask` / `_blend_smoothed` on double tensors (the class itself casts to float) as the fp64 side, on every
+    case of tests/wind_cases.py.  Written per case: wind_<case>.npz (SHA-256 of every regenerated input, the fp32 blend mask and the
+    fp32 FILTERED planes per target variable, d_ref = the reference's own fp32-against-fp64 distance per output) and
+    wind_<case>_f64.npz (the fp64 outputs as float32 differences from the fp32 ones)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import credit.postblock.wind_filter as RW
+    from diag_cases import distance
+    from wind_cases import KEYS, SRC, WIND_CASES, case_inputs, filtered_levels, input_digest, output_names
+
+    for name, c in WIND_CASES.items():
+        inp = case_inputs(name)
+        a = c["args"]
+        targets = [KEYS[v] for v in c["targets"]]
+        lv = filtered_levels(name)
+        blk = RW.WindArtifactFilter(u_var=KEYS["U"], v_var=KEYS["V"], target_vars=targets, **a)
+        batch = {"y_processed": {SRC: {KEYS[v]: torch.from_numpy(inp[v]) for v in ("U", "V", "T")}}}
+        with torch.no_grad():
+            y = blk(batch)["y_processed"][SRC]
+            u, v = torch.from_numpy(inp["U"]), torch.from_numpy(inp["V"])
+            common = (a["speed_threshold"], a["dilation_zonal"], a["dilation_meridional"], a["falloff_sigma"], a["smooth_sigma"],
+                      a["smooth_sigma_zonal"], a["smooth_sigma_meridional"])
+            m32, _ = RW._compute_blend_mask(u[:, a["mask_level"], 0], v[:, a["mask_level"], 0], *common)
+            m64, g64 = RW._compute_blend_mask(u[:, a["mask_level"], 0].double(), v[:, a["mask_level"], 0].double(), *common)
+            res32, res64 = {"mask": m32.numpy()}, {"mask": m64.numpy()}
+            for var in c["targets"]:
+                t = torch.from_numpy(inp[var])
+                assert y[KEYS[var]].shape == t.shape and y[KEYS[var]].dtype == torch.float32
+                for l in range(c["L"]):      # the levels that are not filtered come back untouched
+                    assert l in lv or torch.equal(y[KEYS[var]][:, l], t[:, l]), (name, var, l)
+                res32[var] = y[KEYS[var]][:, lv, 0].contiguous().numpy()
+                res64[var] = torch.stack([RW._blend_smoothed(t[:, l].double(), g64, m64, a["preserve_amplitude"])[:, 0] for l in lv], dim=1).numpy()
+        fix, f64, d_ref = {}, {}, {}
+        for k in ("U", "V", "T"):
+            fix[f"sha256:{k}"] = np.array(input_digest(inp[k]))
+        fix["levels"] = np.array(lv, np.int32)
+        for o in output_names(name):
+            a32, a64 = res32[o], res64[o]
+            assert a32.dtype == np.float32 and a64.dtype == np.float64 and np.isfinite(a32).all() and np.isfinite(a64).all(), (name, o)
+            fix[f"f32:{o}"] = a32
+            f64[f"d64:{o}"] = (a64 - a32.astype(np.float64)).astype(np.float32)
+            d_ref[o] = distance(a32, a64) if np.abs(a64).max() > 0 else 0.0
+            fix[f"d_ref:{o}"] = np.float64(d_ref[o])
+        if name == "calm":
+            assert not res32["mask"].any() and all(np.array_equal(res32[v], inp[v][:, lv, 0]) for v in c["targets"])
+        else:       # the fp32 and the fp64 side flag the same points
+            assert np.array_equal(res32["mask"] > 0, res64["mask"] > 0), name
+        np.savez_compressed(os.path.join(GOLD, f"wind_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"wind_{name}_f64.npz"), **f64)
+        sizes = [os.path.getsize(os.path.join(GOLD, f"wind_{name}{s}.npz")) for s in ("", "_f64")]
+        assert max(sizes) < 1000000, (name, sizes)
+        print(f"[golden] wind {name}: {c['B']} x {c['L']} x {c['H']} x {c['W']}, mask > 0.5 on {100 * float((res32['mask'] > 0.5).mean()):.1f} %, "
+              f"files {sizes[0] // 1024} + {sizes[1] // 1024} KB, d_ref " + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()))
+
+
 def xform_golden():
     """Variable transforms: the reference's own FillValues / LogTransform / SqrtTransform (credit/preblock/{fill_values,log,sqrt}.py)
     and ExpTransform / SquareTransform (credit/postblock/{exp,square}.py) run unmodified, stacked as the cases of tests/xform_cases.py
@@ -1211,6 +1267,8 @@ def main():
             conservation_golden()
         elif item == "diag":        # pressure-level products: geopotential, p-level interpolation, MSLP
             diag_golden()
+        elif item == "wind":        # wind artifact filter: jet mask, masked Gaussian blend
+            wind_golden()
         elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
             xform_golden()
         elif item == "rec":
