@@ -23,7 +23,11 @@ static int guarded(F&& fn) {
   } catch (const wx::HipError& e) { wx::g_last_error = e.what(); return WX_ERR_HIP;
   } catch (const std::exception& e) { wx::g_last_error = e.what(); return WX_ERR_INVALID; }
 }
-#define WX_NEED(h) if (!(h) || !(h)->impl) throw wx::ConfigError("null engine handle")
+// the first test of a wrapper that takes a handle: a live one, or `what` as WX_ERR_INVALID
+template <typename H>
+static void need(const H* h, const char* what) {
+  if (!h || !h->impl) throw wx::ConfigError(what);
+}
 static void need_device(int device, const char* fn) {
   int ndev = 0;
   WX_HIP(hipGetDeviceCount(&ndev));
@@ -64,49 +68,49 @@ int wx_destroy(wx_handle h) {
   return guarded([&] { delete h; });
 }
 int wx_load_tensor(wx_handle h, const char* key, const float* data, int ndim, const int64_t* shape) {
-  return guarded([&] { WX_NEED(h); if (!key || !data || !shape) throw wx::ConfigError("wx_load_tensor: null argument"); h->impl->load_tensor(key, data, ndim, shape); });
+  return guarded([&] { need(h, "null engine handle"); if (!key || !data || !shape) throw wx::ConfigError("wx_load_tensor: null argument"); h->impl->load_tensor(key, data, ndim, shape); });
 }
-int wx_finalize_weights(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->finalize(); }); }
+int wx_finalize_weights(wx_handle h) { return guarded([&] { need(h, "null engine handle"); h->impl->finalize(); }); }
 int wx_num_tensors(wx_handle h) { return (h && h->impl) ? h->impl->num_tensors() : WX_ERR_INVALID; }
 int wx_tensor_info(wx_handle h, int index, const char** key, int* ndim, int64_t shape[8]) {
-  return guarded([&] { WX_NEED(h); h->impl->tensor_info(index, key, ndim, shape); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->tensor_info(index, key, ndim, shape); });
 }
 int wx_set_denorm(wx_handle h, const float* mean, const float* stdv, int n) {
-  return guarded([&] { WX_NEED(h); if (!mean || !stdv) throw wx::ConfigError("wx_set_denorm: null argument"); h->impl->set_denorm(mean, stdv, n); });
+  return guarded([&] { need(h, "null engine handle"); if (!mean || !stdv) throw wx::ConfigError("wx_set_denorm: null argument"); h->impl->set_denorm(mean, stdv, n); });
 }
 int wx_set_tracer_fixer(wx_handle h, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
-  return guarded([&] { WX_NEED(h); if (n > 0 && (!inds || !thres)) throw wx::ConfigError("wx_set_tracer_fixer: null argument"); h->impl->set_tracer(inds, thres, thres_max, n, denorm); });
+  return guarded([&] { need(h, "null engine handle"); if (n > 0 && (!inds || !thres)) throw wx::ConfigError("wx_set_tracer_fixer: null argument"); h->impl->set_tracer(inds, thres, thres_max, n, denorm); });
 }
 int wx_set_layout(wx_handle h, int n_prog, int n_static, int n_dyn) {
-  return guarded([&] { WX_NEED(h); h->impl->set_layout(n_prog, n_static, n_dyn); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->set_layout(n_prog, n_static, n_dyn); });
 }
 int wx_set_layout_groups(wx_handle h, int n_groups, const int32_t* kind, const int32_t* x_start, const int32_t* src_start, const int32_t* count) {
-  return guarded([&] { WX_NEED(h); h->impl->set_layout_groups(n_groups, kind, x_start, src_start, count); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->set_layout_groups(n_groups, kind, x_start, src_start, count); });
 }
 int wx_forward(wx_handle h, const float* x_dev, float* y_dev, int batch, void* stream) {
-  return guarded([&] { WX_NEED(h); if (!x_dev || !y_dev) throw wx::ConfigError("wx_forward: null pointer"); h->impl->forward(x_dev, y_dev, batch, (hipStream_t)stream); });
+  return guarded([&] { need(h, "null engine handle"); if (!x_dev || !y_dev) throw wx::ConfigError("wx_forward: null pointer"); h->impl->forward(x_dev, y_dev, batch, (hipStream_t)stream); });
 }
 int wx_step(wx_handle h, const float* x_dev, const float* frc_dev, float* y_dev, float* y_phys_dev, float* x_next_dev, void* stream) {
-  return guarded([&] { WX_NEED(h); if (!x_dev) throw wx::ConfigError("wx_step: null input"); h->impl->step(x_dev, frc_dev, y_dev, y_phys_dev, x_next_dev, (hipStream_t)stream); });
+  return guarded([&] { need(h, "null engine handle"); if (!x_dev) throw wx::ConfigError("wx_step: null input"); h->impl->step(x_dev, frc_dev, y_dev, y_phys_dev, x_next_dev, (hipStream_t)stream); });
 }
 int wx_rollout(wx_handle h, const float* x0_dev, const float* const* frc_dev, int n_steps, float* const* y_phys_dev, float* x_final_dev,
                void* stream) {
-  return guarded([&] { WX_NEED(h); h->impl->rollout(x0_dev, frc_dev, n_steps, y_phys_dev, x_final_dev, (hipStream_t)stream); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->rollout(x0_dev, frc_dev, n_steps, y_phys_dev, x_final_dev, (hipStream_t)stream); });
 }
-int wx_band_enable(wx_handle h, int rank, int nranks) { return guarded([&] { WX_NEED(h); h->impl->band_enable(rank, nranks); }); }
+int wx_band_enable(wx_handle h, int rank, int nranks) { return guarded([&] { need(h, "null engine handle"); h->impl->band_enable(rank, nranks); }); }
 int wx_band_info(wx_handle h, int* own_row0, int* own_rows, int64_t* send_bytes, int64_t* recv_bytes, int* n_exchanges) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!own_row0 || !own_rows || !send_bytes || !recv_bytes || !n_exchanges) throw wx::ConfigError("wx_band_info: null argument");
     h->impl->band_info(own_row0, own_rows, send_bytes, recv_bytes, n_exchanges);
   });
 }
 int wx_band_set_staging(wx_handle h, void* send_dev, int64_t send_bytes, void* recv_dev, int64_t recv_bytes) {
-  return guarded([&] { WX_NEED(h); h->impl->band_set_staging(send_dev, send_bytes, recv_dev, recv_bytes); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->band_set_staging(send_dev, send_bytes, recv_dev, recv_bytes); });
 }
 int wx_band_exchange(wx_handle h, int xid, wx_band_msg* sends, int cap_sends, int* n_sends, wx_band_msg* recvs, int cap_recvs, int* n_recvs) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!sends || !recvs || !n_sends || !n_recvs) throw wx::ConfigError("wx_band_exchange: null argument");
     h->impl->band_messages_of(xid, sends, cap_sends, n_sends, recvs, cap_recvs, n_recvs);
   });
@@ -114,21 +118,21 @@ int wx_band_exchange(wx_handle h, int xid, wx_band_msg* sends, int cap_sends, in
 int wx_band_begin(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band, void* stream,
                   int* next_xid) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!next_xid) throw wx::ConfigError("wx_band_begin: null next_xid");
     *next_xid = h->impl->band_begin(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream);
   });
 }
 int wx_band_resume(wx_handle h, int* next_xid) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!next_xid) throw wx::ConfigError("wx_band_resume: null next_xid");
     *next_xid = h->impl->band_resume();
   });
 }
 int wx_band_comm_stream(wx_handle h, void* adopt_stream, void** stream_out) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     void* st = h->impl->band_comm_stream(adopt_stream);
     if (stream_out) *stream_out = st;
   });
@@ -145,7 +149,7 @@ int wx_band_rccl_unique_id(uint8_t id[128]) {
 }
 int wx_band_rccl_init(wx_handle h, const uint8_t id[128]) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!id) throw wx::ConfigError("wx_band_rccl_init: null argument");
     ncclUniqueId u;
     std::memcpy(&u, id, 128);
@@ -154,7 +158,7 @@ int wx_band_rccl_init(wx_handle h, const uint8_t id[128]) {
 }
 int wx_band_step_rccl(wx_handle h, const float* x_band, const float* frc_band, float* y_band, float* y_phys_band, float* x_next_band,
                       void* stream) {
-  return guarded([&] { WX_NEED(h); h->impl->band_step_rccl(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->band_step_rccl(x_band, frc_band, y_band, y_phys_band, x_next_band, (hipStream_t)stream); });
 }
 // host-only plan: the model spec supplies the derived geometry (no HIP call is made)
 struct wx_band_plan_s { wx::BandPlan plan; };
@@ -202,26 +206,26 @@ int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts) {
   });
 }
 int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step) {
-  return guarded([&] { WX_NEED(h); h->impl->set_noise(seed, member0, step); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->set_noise(seed, member0, step); });
 }
 int wx_set_noise_tape(wx_handle h, const float* const* draws, int n) {
-  return guarded([&] { WX_NEED(h); h->impl->set_noise_tape(draws, n); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->set_noise_tape(draws, n); });
 }
-int wx_set_debug(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->set_debug(enable); }); }
+int wx_set_debug(wx_handle h, int enable) { return guarded([&] { need(h, "null engine handle"); h->impl->set_debug(enable); }); }
 int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]) {
-  return guarded([&] { WX_NEED(h); if (!name || !shape) throw wx::ConfigError("wx_debug_read: null argument"); h->impl->debug_read(name, host_out, capacity, shape); });
+  return guarded([&] { need(h, "null engine handle"); if (!name || !shape) throw wx::ConfigError("wx_debug_read: null argument"); h->impl->debug_read(name, host_out, capacity, shape); });
 }
 int wx_query(wx_handle h, const char* key, int64_t* value) {
   return guarded([&] {
-    WX_NEED(h);
+    need(h, "null engine handle");
     if (!key || !value) throw wx::ConfigError("wx_query: null argument");
     if (!h->impl->query(key, value)) throw wx::ConfigError(std::string("wx_query: unknown key '") + key + "'");
   });
 }
-int wx_profile(wx_handle h, int enable) { return guarded([&] { WX_NEED(h); h->impl->profile(enable); }); }
-int wx_profile_reset(wx_handle h) { return guarded([&] { WX_NEED(h); h->impl->profile_reset(); }); }
+int wx_profile(wx_handle h, int enable) { return guarded([&] { need(h, "null engine handle"); h->impl->profile(enable); }); }
+int wx_profile_reset(wx_handle h) { return guarded([&] { need(h, "null engine handle"); h->impl->profile_reset(); }); }
 int wx_profile_read(wx_handle h, wx_kernel_stat* out, int capacity, int* count) {
-  return guarded([&] { WX_NEED(h); if (!out || !count) throw wx::ConfigError("wx_profile_read: null argument"); *count = h->impl->profile_read(out, capacity); });
+  return guarded([&] { need(h, "null engine handle"); if (!out || !count) throw wx::ConfigError("wx_profile_read: null argument"); *count = h->impl->profile_read(out, capacity); });
 }
 // ---- pre block (input normalisation + channel concatenation) ---------------------------------------------------------
 struct wx_pre {
@@ -239,18 +243,19 @@ int wx_pre_create(int n_fields, const int32_t* n_levels, int frames, int H, int 
 }
 int wx_pre_destroy(wx_pre_handle p) { return guarded([&] { delete p; }); }
 int wx_pre_channels(wx_pre_handle p, int* channels) {
-  return guarded([&] { if (!p || !p->impl || !channels) throw wx::ConfigError("wx_pre_channels: null argument"); *channels = p->impl->channels(); });
+  return guarded([&] { need(p, "wx_pre_channels: null argument"); if (!channels) throw wx::ConfigError("wx_pre_channels: null argument"); *channels = p->impl->channels(); });
 }
 int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, int batch, void* stream) {
   return guarded([&] {
-    if (!p || !p->impl || !fields_dev || !x_dev) throw wx::ConfigError("wx_pre_apply: null argument");
+    need(p, "wx_pre_apply: null argument");
+    if (!fields_dev || !x_dev) throw wx::ConfigError("wx_pre_apply: null argument");
     p->impl->apply(fields_dev, x_dev, batch, (hipStream_t)stream);
   });
 }
 int wx_pre_set_transforms(wx_pre_handle p, const int32_t* kind, const float* eps, const float* log_eps, const int32_t* n_rules,
                           const int32_t* rule_op, const float* rule_search, const float* rule_fill) {
   return guarded([&] {
-    if (!p || !p->impl) throw wx::ConfigError("wx_pre_set_transforms: null pre-block handle");
+    need(p, "wx_pre_set_transforms: null pre-block handle");
     if (!kind || !eps || !log_eps || !n_rules || !rule_op || !rule_search || !rule_fill) throw wx::ConfigError("wx_pre_set_transforms: null argument");
     remap<wx::ConfigError>([&] { p->impl->set_transforms(kind, eps, log_eps, n_rules, rule_op, rule_search, rule_fill); });
   });
@@ -284,7 +289,8 @@ int wx_unxform_destroy(wx_unxform_handle u) { return guarded([&] { delete u; });
 int wx_unxform_apply(wx_unxform_handle u, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch,
                      int n_time, void* stream) {
   return guarded([&] {
-    if (!u || !u->impl || !src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_unxform_apply: null argument");
+    need(u, "wx_unxform_apply: null argument");
+    if (!src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_unxform_apply: null argument");
     remap<wx::ConfigError>([&] { u->impl->apply(src_dev, batch_stride, dst_dev, batch, n_time, (hipStream_t)stream); });
   });
 }
@@ -312,7 +318,7 @@ int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, 
                   const float* const* src_dev, const int64_t* batch_stride, const int32_t* n_levels, float* const* dst_dev,
                   const int32_t* target_levels, int n_target_levels, int batch, float* mask_out_dev, void* stream) {
   return guarded([&] {
-    if (!f || !f->impl) throw wx::ConfigError("wx_wind_apply: null wind-filter handle");
+    need(f, "wx_wind_apply: null wind-filter handle");
     if (!u_dev || !v_dev || !src_dev || !batch_stride || !n_levels || !dst_dev) throw wx::ConfigError("wx_wind_apply: null argument");
     remap<wx::ConfigError>([&] {
       f->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, n_vars, src_dev, batch_stride, n_levels, dst_dev, target_levels,
@@ -324,7 +330,6 @@ int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, 
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;
 };
-#define WX_NEEDP(p) if (!(p) || !(p)->impl) throw wx::ConfigError("null post-block handle")
 int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx_post_handle* out) {
   return guarded([&] {
     if (!out) throw wx::ConfigError("wx_post_create: null argument");
@@ -336,36 +341,36 @@ int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx
 }
 int wx_post_destroy(wx_post_handle p) { return guarded([&] { delete p; }); }
 int wx_post_set_band(wx_post_handle p, int row0, int rows) {
-  return guarded([&] { if (!p || !p->impl) throw wx::ConfigError("null post handle"); p->impl->set_band(row0, rows); });
+  return guarded([&] { need(p, "null post handle"); p->impl->set_band(row0, rows); });
 }
 int wx_post_set_grid_sigma(wx_post_handle p, const float* lat2d, const float* lon2d, const float* coef_a, const float* coef_b,
                            int n_levels, int midpoint, int sp_ind) {
   return guarded([&] {
-    WX_NEEDP(p);
+    need(p, "null post-block handle");
     if (!lat2d || !lon2d || !coef_a || !coef_b) throw wx::ConfigError("wx_post_set_grid_sigma: null argument");
     p->impl->set_grid_sigma(lat2d, lon2d, coef_a, coef_b, n_levels, midpoint, sp_ind);
   });
 }
 int wx_post_set_grid(wx_post_handle p, const float* lat2d, const float* lon2d, const float* p_levels, int n_levels, int midpoint) {
-  return guarded([&] { WX_NEEDP(p); if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument"); p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint); });
+  return guarded([&] { need(p, "null post-block handle"); if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument"); p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint); });
 }
 int wx_post_set_stats(wx_post_handle p, const float* mi, const float* si, const float* mo, const float* so) {
-  return guarded([&] { WX_NEEDP(p); if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument"); p->impl->set_stats(mi, si, mo, so); });
+  return guarded([&] { need(p, "null post-block handle"); if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument"); p->impl->set_stats(mi, si, mo, so); });
 }
 int wx_post_add_tracer_fixer(wx_post_handle p, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
-  return guarded([&] { WX_NEEDP(p); if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument"); p->impl->add_tracer(inds, thres, thres_max, n, denorm); });
+  return guarded([&] { need(p, "null post-block handle"); if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument"); p->impl->add_tracer(inds, thres, thres_max, n, denorm); });
 }
 int wx_post_add_mass_fixer(wx_post_handle p, int q_start, int fix_level_num, int denorm) {
-  return guarded([&] { WX_NEEDP(p); p->impl->add_mass(q_start, fix_level_num, denorm); });
+  return guarded([&] { need(p, "null post-block handle"); p->impl->add_mass(q_start, fix_level_num, denorm); });
 }
 int wx_post_add_water_fixer(wx_post_handle p, int q_start, int precip_ind, int evapor_ind, float n_seconds, int denorm) {
-  return guarded([&] { WX_NEEDP(p); p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
+  return guarded([&] { need(p, "null post-block handle"); p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
 }
 int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, int n_toa,
                                     const int32_t* toa_inds, const float* toa_signs, int n_srf, const int32_t* srf_inds,
                                     const float* srf_signs, const float* gph_surf, float n_seconds, int denorm) {
   return guarded([&] {
-    WX_NEEDP(p);
+    need(p, "null post-block handle");
     if (!toa_inds || !toa_signs || !srf_inds || !srf_signs || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_signed: null argument");
     p->impl->add_energy_signed(T_start, q_start, U_start, V_start, n_toa, toa_inds, toa_signs, n_srf, srf_inds, srf_signs, gph_surf,
                                n_seconds, denorm);
@@ -374,27 +379,26 @@ int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, 
 int wx_post_add_energy_fixer_updown(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t flux_inds[9],
                                     const float* gph_surf, float n_seconds, int denorm) {
   return guarded([&] {
-    WX_NEEDP(p);
+    need(p, "null post-block handle");
     if (!flux_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_updown: null argument");
     p->impl->add_energy_updown(T_start, q_start, U_start, V_start, flux_inds, gph_surf, n_seconds, denorm);
   });
 }
 int wx_post_add_energy_fixer(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t rad_inds[6],
                              const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] { WX_NEEDP(p); if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument"); p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm); });
+  return guarded([&] { need(p, "null post-block handle"); if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument"); p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm); });
 }
 int wx_post_apply(wx_post_handle p, const float* x_dev, float* y_dev, void* stream) {
-  return guarded([&] { WX_NEEDP(p); if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer"); p->impl->apply(x_dev, y_dev, (hipStream_t)stream); });
+  return guarded([&] { need(p, "null post-block handle"); if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer"); p->impl->apply(x_dev, y_dev, (hipStream_t)stream); });
 }
 int wx_attach_postblock(wx_handle h, wx_post_handle p) {
-  return guarded([&] { WX_NEED(h); h->impl->attach_post(p ? p->impl.get() : nullptr); });
+  return guarded([&] { need(h, "null engine handle"); h->impl->attach_post(p ? p->impl.get() : nullptr); });
 }
 
 // ---- pressure-level products (geopotential, model -> pressure levels, MSLP; csrc/wx_diag.h) ------------------------------------
 struct wx_diag {
   std::unique_ptr<wx::Diag> impl;
 };
-#define WX_NEEDD(d) if (!(d) || !(d)->impl) throw wx::ConfigError("null diagnostics handle")
 int wx_diag_create(int H, int W, int n_levels, int device, wx_diag_handle* out) {
   return guarded([&] {
     if (!out) throw wx::ConfigError("wx_diag_create: null argument");
@@ -407,16 +411,16 @@ int wx_diag_create(int H, int W, int n_levels, int device, wx_diag_handle* out) 
 }
 int wx_diag_destroy(wx_diag_handle d) { return guarded([&] { delete d; }); }
 int wx_diag_set_levels(wx_diag_handle d, const float* a_half, const float* b_half, const float* a_mid, const float* b_mid, int flip_vertical) {
-  return guarded([&] { WX_NEEDD(d); remap<wx::ConfigError>([&] { d->impl->set_levels(a_half, b_half, a_mid, b_mid, flip_vertical); }); });
+  return guarded([&] { need(d, "null diagnostics handle"); remap<wx::ConfigError>([&] { d->impl->set_levels(a_half, b_half, a_mid, b_mid, flip_vertical); }); });
 }
 int wx_diag_set_pressure_levels(wx_diag_handle d, const float* p_pa, int n_plev, float temp_height) {
-  return guarded([&] { WX_NEEDD(d); remap<wx::ConfigError>([&] { d->impl->set_pressure_levels(p_pa, n_plev, temp_height); }); });
+  return guarded([&] { need(d, "null diagnostics handle"); remap<wx::ConfigError>([&] { d->impl->set_pressure_levels(p_pa, n_plev, temp_height); }); });
 }
 int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const float* q, const float* sp, const float* phis,
                   int phis_n_time, const float* t_near_surface, const float* const* fields, int n_fields, float* z_model_out,
                   float* const* plev_out, float* mslp_out, void* stream) {
   return guarded([&] {
-    WX_NEEDD(d);
+    need(d, "null diagnostics handle");
     remap<wx::ConfigError>([&] {
       d->impl->apply(batch, n_time, T, q, sp, phis, phis_n_time, t_near_surface, fields, n_fields, z_model_out, plev_out, mslp_out,
                      (hipStream_t)stream);
@@ -427,15 +431,13 @@ int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const
 // ---- standalone window attention (the Swin / FuXi mode of the attention kernel) -----------------------
 struct wx_winattn {
   wx_winattn_desc d;
-  int device = 0;
+  int device;
+  wx::DeviceArena mem;
   int NP = 0;
   float* bias_dev = nullptr;     // [n_bias_heads][NP][NP], padded keys -1e30, x log2(e) for bf16
   float* logit_dev = nullptr;    // [heads] or nullptr
   int64_t n_bias_stride = 0;     // floats between two heads' tables (0: one table shared by every head)
-  ~wx_winattn() {
-    if (bias_dev) (void)hipFree(bias_dev);
-    if (logit_dev) (void)hipFree(logit_dev);
-  }
+  wx_winattn(const wx_winattn_desc& desc, int dev) : d(desc), device(dev), mem(dev) {}
 };
 int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bias_heads, const float* logit_scale_host, int device,
                       wx_winattn_handle* out) {
@@ -458,8 +460,8 @@ int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bi
     if (nkf < 0 || nkf > 8) throw wx::ConfigError("winattn: at most 128 tokens per window");
     if (n_bias_heads != 0 && n_bias_heads != 1 && n_bias_heads != d->heads) throw wx::ConfigError("winattn: bias for 0, 1 or `heads` heads");
     WX_HIP(hipSetDevice(device));
-    auto w = std::make_unique<wx_winattn>();
-    w->d = *d; w->device = device; w->NP = nkf * 16;
+    auto w = std::make_unique<wx_winattn>(*d, device);
+    w->NP = nkf * 16;
     const int NP = w->NP, nb = n_bias_heads > 0 ? n_bias_heads : 1;
     const float l2e = d->precision == WX_PREC_BF16 ? 1.4426950408889634f : 1.0f;   // bf16 softmax runs on exp2
     std::vector<float> tab((size_t)nb * NP * NP, -1.0e30f);
@@ -467,14 +469,12 @@ int wx_winattn_create(const wx_winattn_desc* d, const float* bias_host, int n_bi
       for (int q = 0; q < NP; ++q)
         for (int k = 0; k < N; ++k)
           tab[((size_t)h * NP + q) * NP + k] = (q < N && bias_host && n_bias_heads > 0) ? bias_host[((size_t)h * N + q) * N + k] * l2e : 0.f;
-    WX_HIP(hipMalloc(&w->bias_dev, tab.size() * sizeof(float)));
-    WX_HIP(hipMemcpy(w->bias_dev, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+    w->bias_dev = w->mem.upload(tab.data(), tab.size());
     w->n_bias_stride = nb > 1 ? (int64_t)NP * NP : 0;
     if (logit_scale_host) {
       std::vector<float> ls(d->heads);
       for (int h = 0; h < d->heads; ++h) ls[h] = logit_scale_host[h] * l2e;
-      WX_HIP(hipMalloc(&w->logit_dev, ls.size() * sizeof(float)));
-      WX_HIP(hipMemcpy(w->logit_dev, ls.data(), ls.size() * sizeof(float), hipMemcpyHostToDevice));
+      w->logit_dev = w->mem.upload(ls.data(), ls.size());
     }
     *out = w.release();
   });

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace wx {
 
@@ -257,6 +259,47 @@ __device__ __forceinline__ float max_over_rows(float x) {
 __device__ __forceinline__ int pair_rows16_channel(int g) { return 16 * (g & 1) + 4 * (g & ~1); }
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Owner of the device allocations of one object on one device.  Held as a MEMBER: a constructor that throws halfway still frees what it
+// had allocated, and a destructor body (streams, graphs, communicators) runs before the memory goes.  The caller has made `device`
+// current before alloc / upload / release, as every entry point does; the destructor selects it itself.
+class DeviceArena {
+ public:
+  explicit DeviceArena(int device) : device_(device) {}
+  DeviceArena(const DeviceArena&) = delete;
+  DeviceArena& operator=(const DeviceArena&) = delete;
+  ~DeviceArena() {
+    (void)hipSetDevice(device_);
+    for (void* p : ptrs_) (void)hipFree(p);
+  }
+  void* alloc(size_t bytes) {
+    ptrs_.reserve(ptrs_.size() + 1);   // so that nothing can throw between hipMalloc and the bookkeeping
+    void* p = nullptr;
+    WX_HIP(hipMalloc(&p, bytes));
+    ptrs_.push_back(p);
+    return p;
+  }
+  template <typename T>
+  T* upload(const T* src, size_t n) {
+    T* d = (T*)alloc(n * sizeof(T));
+    WX_HIP(hipMemcpy(d, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  // frees one allocation, nulls the caller's pointer and forgets it; a null pointer is left alone.  hipFree waits for the kernels
+  // that still read the buffer.
+  template <typename P>
+  void release(P*& p) {
+    if (!p) return;
+    ptrs_.erase(std::find(ptrs_.begin(), ptrs_.end(), (void*)p));
+    void* old = (void*)p;
+    p = nullptr;
+    WX_HIP(hipFree(old));
+  }
+
+ private:
+  int device_;
+  std::vector<void*> ptrs_;
+};
 
 // "this kernel's launch attributes are set" flags: hipFuncSetAttribute applies to the CURRENT device only, so a process that
 // drives several GPUs (one engine per device) must set them once per device

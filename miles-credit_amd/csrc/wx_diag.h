@@ -174,16 +174,12 @@ inline int diag_threads(int L) { return L <= 32 ? 256 : L <= 64 ? 128 : L <= 128
 
 class Diag {
  public:
-  Diag(int H, int W, int n_levels, int dev) : hw((int64_t)H * W), L(n_levels), device(dev) {
+  Diag(int H, int W, int n_levels, int dev) : hw((int64_t)H * W), L(n_levels), device(dev), mem(dev) {
     if (H < 1 || W < 1) throw std::runtime_error("wx_diag_create: bad geometry");
     if (n_levels < 2 || n_levels > kDiagMaxLevels) throw std::runtime_error("wx_diag_create: n_levels must be 2 .. 137");
     WX_HIP(hipSetDevice(device));
     // a_half | b_half | a_mid | b_mid | plev
-    WX_HIP(hipMalloc(&coef, sizeof(float) * (2 * (L + 1) + 2 * L + kDiagMaxPlev)));
-  }
-  ~Diag() {
-    (void)hipSetDevice(device);
-    if (coef) (void)hipFree(coef);
+    coef = (float*)mem.alloc(sizeof(float) * (2 * (L + 1) + 2 * L + kDiagMaxPlev));
   }
   void set_levels(const float* a_half, const float* b_half, const float* a_mid, const float* b_mid, int flip_vertical_) {
     if ((a_half == nullptr) != (b_half == nullptr)) throw std::runtime_error("wx_diag_set_levels: a_half and b_half come together");
@@ -269,6 +265,7 @@ class Diag {
  private:
   int64_t hw;
   int L, device, n_plev = 0;
+  DeviceArena mem;
   float* coef = nullptr;
   bool have_half = false, have_mid = false, flip_vertical = true, flip_mid = false;
   float temp_height = 150.0f;

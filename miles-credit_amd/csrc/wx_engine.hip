@@ -95,7 +95,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // the reference's fp32 forward: ~1e-5 of max|y| (base weights), 5-7e-5 on the stress families -- inside the stated 1e-4 tolerance.
   bool split_mma = false;
   const Options opt;   // the run-time switches, read once by wx_create (wx_options.h)
-  Engine(const wx_config& c, int dev, const Options& o, bool split = false) : ModelSpec(c), split_mma(split && sizeof(T) == 4), opt(o) {
+  Engine(const wx_config& c, int dev, const Options& o, bool split = false) : ModelSpec(c), split_mma(split && sizeof(T) == 4), opt(o), mem(dev) {
     device = dev;
   }
   ~Engine() override {
@@ -105,7 +105,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (b_ev_pack) { (void)hipEventDestroy(b_ev_pack); (void)hipEventDestroy(b_ev_done); }
     roll_invalidate();
     if (roll_stream) { (void)hipStreamDestroy(roll_stream); (void)hipEventDestroy(roll_ev_in); (void)hipEventDestroy(roll_ev_out); }
-    for (void* p : allocs) (void)hipFree(p);
     for (auto& e : ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   }
 
@@ -132,10 +131,10 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     WeightPacker<T> pk(*this, *this, opt, split_mma);
     pk.run();
     // upload
-    dfree(wt_dev);
-    dfree(f_dev);
-    wt_dev = (T*)dalloc(pk.wt_host.size() * sizeof(T) + 256);
-    f_dev = (float*)dalloc(pk.f_host.size() * sizeof(float) + 256);
+    mem.release(wt_dev);
+    mem.release(f_dev);
+    wt_dev = (T*)mem.alloc(pk.wt_host.size() * sizeof(T) + 256);
+    f_dev = (float*)mem.alloc(pk.f_host.size() * sizeof(float) + 256);
     WX_HIP(hipMemcpy(wt_dev, pk.wt_host.data(), pk.wt_host.size() * sizeof(T), hipMemcpyHostToDevice));
     WX_HIP(hipMemcpy(f_dev, pk.f_host.data(), pk.f_host.size() * sizeof(float), hipMemcpyHostToDevice));
     if constexpr (sizeof(T) == 4) {
@@ -147,12 +146,12 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         while (pk.wt_host.size() % 32) pk.wt_host.push_back(0.f);
         std::vector<uint16_t> sp(pk.wt_host.size() * 2);
         split_encode_chunks(pk.wt_host.data(), pk.wt_host.size(), sp.data());
-        dfree(ws_dev);
-        ws_dev = (T*)dalloc(sp.size() * sizeof(uint16_t) + 256);
+        mem.release(ws_dev);
+        ws_dev = (T*)mem.alloc(sp.size() * sizeof(uint16_t) + 256);
         WX_HIP(hipMemcpy(ws_dev, sp.data(), sp.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         if (!pk.sp16_host.empty()) {
-          dfree(sp16_dev);   // a second wx_finalize_weights: no leak
-          sp16_dev = (uint16_t*)dalloc(pk.sp16_host.size() * sizeof(uint16_t) + 256);
+          mem.release(sp16_dev);   // a second wx_finalize_weights: no leak
+          sp16_dev = (uint16_t*)mem.alloc(pk.sp16_host.size() * sizeof(uint16_t) + 256);
           WX_HIP(hipMemcpy(sp16_dev, pk.sp16_host.data(), pk.sp16_host.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
         }
       }
@@ -162,20 +161,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   }
 
   // ------------------------------------------------------------------ buffers
-  std::vector<void*> allocs;
-  void* dalloc(size_t bytes) {
-    void* p = nullptr;
-    WX_HIP(hipMalloc(&p, bytes));
-    allocs.push_back(p);
-    return p;
-  }
-  template <typename P>
-  void dfree(P*& p) {
-    if (!p) return;
-    (void)hipFree(p);
-    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)p));
-    p = nullptr;
-  }
+  DeviceArena mem;   // every device buffer below; freed after ~Engine's body has destroyed the communicator, streams, graphs and events
   T* ws_dev = nullptr;       // split_mma: the weight arena re-encoded as bf16 (hi, lo) fragments, same offsets as wt_dev
   char* xs_planes = nullptr; // split_mma: the packed input as bf16 planes [x_hi | x_lo] (PackParams::split_planar); the patch kernel's third
                              // chunk group wraps around to x_hi (EmbedPatchParams::plane_wrap)
@@ -231,60 +217,60 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   void alloc_activations() {
     if (acts_ready) return;
     const int64_t xin_elems = (int64_t)(Hp + 2 * halo + 2) * (Wp + 2 * halo + 2) * cpad0;
-    xin = (T*)dalloc(xin_elems * sizeof(T));
+    xin = (T*)mem.alloc(xin_elems * sizeof(T));
     WX_HIP(hipMemset(xin, 0, xin_elems * sizeof(T)));
     if (split_mma && opt.use_patch && sp16_dev) {   // the patch kernel reads the bf16 (hi, lo) planes: no fp32 planar copy in this mode
-      xs_planes = (char*)dalloc((size_t)xin_elems * 2 * 2);
+      xs_planes = (char*)mem.alloc((size_t)xin_elems * 2 * 2);
       WX_HIP(hipMemset(xs_planes, 0, (size_t)xin_elems * 2 * 2));
     } else if (opt.use_patch && opt.planar_xin) {
-      xin_planar = (T*)dalloc(xin_elems * sizeof(T));
+      xin_planar = (T*)mem.alloc(xin_elems * sizeof(T));
       WX_HIP(hipMemset(xin_planar, 0, xin_elems * sizeof(T)));
     }
     int64_t max_sc = 0, max_ao = 0, max_hw = 0;
     for (int s = 0; s < 4; ++s) {
       const int64_t hw = (int64_t)sh[s] * sw[s];
-      if (s < 3) cat[s] = (T*)dalloc(hw * 2 * cfg.dim[s] * sizeof(T));
-      else x3 = (T*)dalloc(hw * cfg.dim[s] * sizeof(T));
+      if (s < 3) cat[s] = (T*)mem.alloc(hw * 2 * cfg.dim[s] * sizeof(T));
+      else x3 = (T*)mem.alloc(hw * cfg.dim[s] * sizeof(T));
       max_sc = std::max(max_sc, hw * 4 * cfg.dim[s]);
       max_ao = std::max(max_ao, hw * cfg.dim[s]);
       max_hw = std::max(max_hw, hw);
     }
-    scratch = (T*)dalloc(max_sc * sizeof(T));
-    attn_o = (T*)dalloc(max_ao * sizeof(T));
+    scratch = (T*)mem.alloc(max_sc * sizeof(T));
+    attn_o = (T*)mem.alloc(max_ao * sizeof(T));
     int64_t max_dt = 0;
     for (int i = 0; i < 3; ++i) max_dt = std::max(max_dt, (int64_t)sh[2 - i] * sw[2 - i] * ups[i].cout);
-    for (int i = 0; i < 4; ++i) dtmp[i] = (T*)dalloc(max_dt * sizeof(T));
-    if (cfg.arch == WX_ARCH_WXFORMER) ps4_buf = (T*)dalloc((int64_t)Hd * Wd * cpad4 * sizeof(T));
+    for (int i = 0; i < 4; ++i) dtmp[i] = (T*)mem.alloc(max_dt * sizeof(T));
+    if (cfg.arch == WX_ARCH_WXFORMER) ps4_buf = (T*)mem.alloc((int64_t)Hd * Wd * cpad4 * sizeof(T));
     if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // bilinearly up-sampled conv input: largest is up_block4's (Hd x Wd x 2 dim0)
       int64_t m = (int64_t)Hd * Wd * 2 * cfg.dim[0];
       for (int i = 0; i < 3; ++i) m = std::max(m, (int64_t)sh[2 - i] * sw[2 - i] * ups[i].cin);
-      upbuf = (T*)dalloc(m * sizeof(T));
+      upbuf = (T*)mem.alloc(m * sizeof(T));
     }
-    dec = (T*)dalloc((int64_t)Hd * Wd * ld_dec * sizeof(T));
+    dec = (T*)mem.alloc((int64_t)Hd * Wd * ld_dec * sizeof(T));
     WX_HIP(hipMemset(dec, 0, (int64_t)Hd * Wd * ld_dec * sizeof(T)));
-    rowstat = (float2*)dalloc(max_hw * sizeof(float2));
+    rowstat = (float2*)mem.alloc(max_hw * sizeof(float2));
     // LayerNorm partials: most producers leave <= 8 per row; the weight-stationary GEMM and the attention block kernel leave C / 32
     // (16 at C = 512) -- sized from the largest rows x slots product any stage can ask for, and checked at every producer (stat_dst)
     statpart_elems = max_hw * 8;
     for (int s = 0; s < 4; ++s) statpart_elems = std::max(statpart_elems, (int64_t)sh[s] * sw[s] * std::max(8, cfg.dim[s] / 32));
-    statpart = (float2*)dalloc(statpart_elems * sizeof(float2));
+    statpart = (float2*)mem.alloc(statpart_elems * sizeof(float2));
     gnpart_elems = (int64_t)cdiv(max_hw, 128) * cfg.dim[3];
-    gnpart = (float2*)dalloc(gnpart_elems * sizeof(float2));
-    zero_page = (char*)dalloc(256);
+    gnpart = (float2*)mem.alloc(gnpart_elems * sizeof(float2));
+    zero_page = (char*)mem.alloc(256);
     WX_HIP(hipMemset(zero_page, 0, 256));
-    stream_sink = (char*)dalloc(8192);   // 16 bytes per thread of the widest workgroup (512: wx_gemm8p.h)
+    stream_sink = (char*)mem.alloc(8192);   // 16 bytes per thread of the widest workgroup (512: wx_gemm8p.h)
     splitk_bytes = splitk_bound();
-    splitk_buf = (float*)dalloc(splitk_bytes);
+    splitk_buf = (float*)mem.alloc(splitk_bytes);
     const int cmax = cfg.dim[3];
-    gn_acc = (double*)dalloc(2 * cmax * sizeof(double));
-    d_mean = (float*)dalloc(C_out * sizeof(float));
-    d_std = (float*)dalloc(C_out * sizeof(float));
-    d_lo = (float*)dalloc(C_out * sizeof(float));
-    d_hi = (float*)dalloc(C_out * sizeof(float));
+    gn_acc = (double*)mem.alloc(2 * cmax * sizeof(double));
+    d_mean = (float*)mem.alloc(C_out * sizeof(float));
+    d_std = (float*)mem.alloc(C_out * sizeof(float));
+    d_lo = (float*)mem.alloc(C_out * sizeof(float));
+    d_hi = (float*)mem.alloc(C_out * sizeof(float));
     if (cfg.noise_latent_dim > 0) {
-      d_noise = (NoiseState*)dalloc(sizeof(NoiseState));
+      d_noise = (NoiseState*)mem.alloc(sizeof(NoiseState));
       WX_HIP(hipMemset(d_noise, 0, sizeof(NoiseState)));
-      d_style = (float*)dalloc((size_t)6 * cfg.dim[3] * sizeof(float));
+      d_style = (float*)mem.alloc((size_t)6 * cfg.dim[3] * sizeof(float));
     }
     acts_ready = true;
   }
@@ -371,7 +357,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     }
     for (int c = 0; c < cx; ++c)
       if (owner[c] < 0) throw ConfigError("wx_set_layout_groups: the groups must cover every input channel");
-    if (!d_xmap) d_xmap = (int*)dalloc((size_t)C_out * sizeof(int));
+    if (!d_xmap) d_xmap = (int*)mem.alloc((size_t)C_out * sizeof(int));
     WX_HIP(hipMemcpy(d_xmap, xmap.data(), (size_t)C_out * sizeof(int), hipMemcpyHostToDevice));
     lgroups = gs;
     n_prog = np; n_static = ns; n_dyn = nd;   // n_dyn = channels of the forcing tensor
@@ -481,7 +467,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   void finish_item(const float* x_item, float* y, float* y_phys, float* x_next) {
     if (!post) { tail(y, y_phys, x_next); return; }
     if (!y) {
-      if (!y_internal) y_internal = (float*)dalloc((size_t)C_out * Ho * Wo * sizeof(float));
+      if (!y_internal) y_internal = (float*)mem.alloc((size_t)C_out * Ho * Wo * sizeof(float));
       y = y_internal;
     }
     tail(y, nullptr, nullptr);
@@ -1144,7 +1130,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           const int n_split = opt.embed_split_ways;
           const size_t need = (size_t)n_split * sh[0] * sw[0] * 64 * sizeof(float);
           if (need > embed_partial_bytes) {
-            embed_partial = (float*)dalloc(need);   // grows at most a few times (batch / band geometry); dalloc's list frees the older ones at destroy
+            embed_partial = (float*)mem.alloc(need);   // grows at most a few times (batch / band geometry); the arena frees the older ones at destroy
             embed_partial_bytes = need;
           }
           ep.partial = embed_partial;
@@ -1154,7 +1140,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           const int tail = embed_patch_tail_rows(sh[0], sw[0], chunks0);
           if (tail > 0) {
             const size_t need = (size_t)2 * tail * sw[0] * 64 * sizeof(float);
-            if (need > embed_tail_bytes) { embed_tail = (float*)dalloc(need); embed_tail_bytes = need; }
+            if (need > embed_tail_bytes) { embed_tail = (float*)mem.alloc(need); embed_tail_bytes = need; }
             ep.tail_partial = embed_tail;
           }
         }
@@ -1468,8 +1454,8 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     WX_HIP(hipSetDevice(device));
     if (splitk_bound(true) > splitk_bytes) {   // the band ranks' split-K rule reaches more tiles than the whole-map engine's
       splitk_bytes = splitk_bound(true);
-      dfree(splitk_buf);
-      splitk_buf = (float*)dalloc(splitk_bytes);
+      mem.release(splitk_buf);
+      splitk_buf = (float*)mem.alloc(splitk_bytes);
     }
     for (int s = 0; s < 4; ++s) gsh[s] = sh[s];
     bplan.build(band_model(*this, n, (int)sizeof(T), post ? post->n_fixers() : 0));
@@ -1483,25 +1469,25 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     // ---- buffers of this band
     const int st0 = cfg.embed_strides[0];
     const int64_t xin_elems = (int64_t)(st0 * g.rows_short(0, rank) + 2 * halo + 2) * (Wp + 2 * halo + 2) * cpad0;
-    bxin = (T*)dalloc(xin_elems * sizeof(T));
+    bxin = (T*)mem.alloc(xin_elems * sizeof(T));
     WX_HIP(hipMemset(bxin, 0, xin_elems * sizeof(T)));
     if (opt.use_patch && opt.planar_xin) {
-      bxin_planar = (T*)dalloc(xin_elems * sizeof(T));
+      bxin_planar = (T*)mem.alloc(xin_elems * sizeof(T));
       WX_HIP(hipMemset(bxin_planar, 0, xin_elems * sizeof(T)));
     }
     const int xneed = bplan.x_need_hi[rank] - bplan.x_need_lo[rank];
-    bxneed = (float*)dalloc((size_t)std::max(1, xneed) * C_in * cfg.image_width * sizeof(float));
+    bxneed = (float*)mem.alloc((size_t)std::max(1, xneed) * C_in * cfg.image_width * sizeof(float));
     int64_t emb_max = 1, dec_in_max = 1, dt_max = 1;
     for (int s = 0; s < 4; ++s) {
       const int64_t rs = g.rows_short(s, rank), rl = g.rows_long(s, rank);
       if (s < 3) {
         const int64_t el = (rs + 2) * sw[s] * 2 * cfg.dim[s];
-        bcat[s] = (T*)dalloc(el * sizeof(T));
+        bcat[s] = (T*)mem.alloc(el * sizeof(T));
         WX_HIP(hipMemset(bcat[s], 0, el * sizeof(T)));
       } else {
-        bx3 = (T*)dalloc(std::max<int64_t>(1, rs * sw[s] * cfg.dim[s]) * sizeof(T));
+        bx3 = (T*)mem.alloc(std::max<int64_t>(1, rs * sw[s] * cfg.dim[s]) * sizeof(T));
       }
-      if (cfg.global_window_size[s] > 1) blong[s] = (T*)dalloc(std::max<int64_t>(1, rl * sw[s] * cfg.dim[s]) * sizeof(T));
+      if (cfg.global_window_size[s] > 1) blong[s] = (T*)mem.alloc(std::max<int64_t>(1, rl * sw[s] * cfg.dim[s]) * sizeof(T));
       if (s > 0) emb_max = std::max(emb_max, (int64_t)(cfg.embed_strides[s] * rs + bplan.m.emb_lo[s] + bplan.m.emb_hi[s]) * sw[s - 1] * cfg.dim[s - 1]);
       // scratch / attn_o / rowstat / statpart of the whole-map engine are large enough for any band
     }
@@ -1510,30 +1496,30 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       const int64_t rows_in = (g.rows_short(so, rank) + 1) / 2 + 1 + (cfg.arch == WX_ARCH_WXFORMER ? 4 : 0);
       if (cfg.arch == WX_ARCH_WXFORMER) {
         const int64_t el = (int64_t)(g.rows_short(so, rank) + 4) * sw[so] * ups[i].cout;
-        bps[i] = (T*)dalloc(el * sizeof(T));
+        bps[i] = (T*)mem.alloc(el * sizeof(T));
         WX_HIP(hipMemset(bps[i], 0, el * sizeof(T)));
       }
       dec_in_max = std::max(dec_in_max, rows_in * sw[si] * (i == 0 ? cfg.dim[3] : 2 * cfg.dim[si]));
       dt_max = std::max(dt_max, (int64_t)(g.rows_short(so, rank) + 2) * sw[so] * ups[i].cout);
     }
-    bemb_in = (T*)dalloc(emb_max * sizeof(T));
-    bdec_in = (T*)dalloc(dec_in_max * sizeof(T));
-    bscut = (T*)dalloc(dt_max * sizeof(T));
-    bta = (T*)dalloc(dt_max * sizeof(T));
-    btb = (T*)dalloc(dt_max * sizeof(T));
+    bemb_in = (T*)mem.alloc(emb_max * sizeof(T));
+    bdec_in = (T*)mem.alloc(dec_in_max * sizeof(T));
+    bscut = (T*)mem.alloc(dt_max * sizeof(T));
+    bta = (T*)mem.alloc(dt_max * sizeof(T));
+    btb = (T*)mem.alloc(dt_max * sizeof(T));
     WX_HIP(hipMemset(bscut, 0, dt_max * sizeof(T)));
     WX_HIP(hipMemset(btb, 0, dt_max * sizeof(T)));
     if (cfg.arch == WX_ARCH_WXFORMER) {
       const int64_t el = (int64_t)(2 * g.rows_short(0, rank) + 2) * Wd * cpad4;
-      bps4 = (T*)dalloc(el * sizeof(T));
+      bps4 = (T*)mem.alloc(el * sizeof(T));
       WX_HIP(hipMemset(bps4, 0, el * sizeof(T)));
     }
     const int64_t dec_el = (int64_t)(2 * g.rows_short(0, rank) + 2) * Wd * ld_dec;
-    bdec = (T*)dalloc(dec_el * sizeof(T));
+    bdec = (T*)mem.alloc(dec_el * sizeof(T));
     WX_HIP(hipMemset(bdec, 0, dec_el * sizeof(T)));
-    gn_all = (double*)dalloc((size_t)n * 2 * cfg.dim[3] * sizeof(double));
-    fix_all = (double*)dalloc((size_t)n * 4 * sizeof(double));
-    if (post) by_internal = (float*)dalloc(std::max<size_t>(1, (size_t)C_out * (g.po[rank + 1] - g.po[rank]) * Wo) * sizeof(float));
+    gn_all = (double*)mem.alloc((size_t)n * 2 * cfg.dim[3] * sizeof(double));
+    fix_all = (double*)mem.alloc((size_t)n * 4 * sizeof(double));
+    if (post) by_internal = (float*)mem.alloc(std::max<size_t>(1, (size_t)C_out * (g.po[rank + 1] - g.po[rank]) * Wo) * sizeof(float));
     for (const BandExchange& x : bplan.xs) {
       b_send_need = std::max(b_send_need, band_send_bytes(x, rank));
       b_recv_need = std::max(b_recv_need, band_recv_bytes(x, rank));
@@ -1634,7 +1620,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       auto up2 = [&](const std::vector<int2>& v, int2** dst, int* n) {
         *n = (int)v.size();
         if (v.empty()) return;
-        *dst = (int2*)dalloc(v.size() * sizeof(int2));
+        *dst = (int2*)mem.alloc(v.size() * sizeof(int2));
         WX_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(int2), hipMemcpyHostToDevice));
       };
       up2(pk, &d.pack, &d.n_pack);
@@ -1987,8 +1973,8 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     WX_HIP(hipSetDevice(device));
     RcclApi& api = RcclApi::get();
     api.check(api.CommInitRank(&b_comm, b_n, id, b_rank), "ncclCommInitRank");
-    if (!b_send && b_send_need) b_send = (char*)dalloc((size_t)b_send_need);
-    if (!b_recv && b_recv_need) b_recv = (char*)dalloc((size_t)b_recv_need);
+    if (!b_send && b_send_need) b_send = (char*)mem.alloc((size_t)b_send_need);
+    if (!b_recv && b_recv_need) b_recv = (char*)mem.alloc((size_t)b_recv_need);
     b_msgs.resize(bplan.xs.size());
     for (size_t x = 0; x < bplan.xs.size(); ++x) band_messages(bplan.xs[x], b_rank, &b_msgs[x].first, &b_msgs[x].second);
     if (opt.band_overlap) band_comm_stream(nullptr);
@@ -2111,12 +2097,12 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       for (int t = 0; t < n; ++t)
         if ((t < n - 1 || x_final) && (!frc || !frc[t])) throw ConfigError("wx_rollout: forcing pointer is NULL but the layout has dynamic forcing channels");
     if (!roll_x[0]) {
-      roll_x[0] = (float*)dalloc(x_bytes);
-      roll_x[1] = (float*)dalloc(x_bytes);
+      roll_x[0] = (float*)mem.alloc(x_bytes);
+      roll_x[1] = (float*)mem.alloc(x_bytes);
     }
     if (n_dyn > roll_frc_ndyn) {   // a later layout may carry more forcing planes than the first call's
       roll_invalidate();           // (the captured copies point at the old buffer)
-      roll_frc = (float*)dalloc((size_t)n_dyn * plane * sizeof(float));
+      roll_frc = (float*)mem.alloc((size_t)n_dyn * plane * sizeof(float));
       roll_frc_ndyn = n_dyn;
     }
     const bool graph = want_graph() && roll_warm;

@@ -143,8 +143,8 @@ struct FuxiModel : FuxiBase {
   FuxiDesc d;
   int device;
   int Hp, Wp, Hd, Wd, Hs, Ws, pt, pl, K0, K0p, Nfc, Nfcp;
+  DeviceArena mem;   // declared before `stage`: the stage (its own arena) goes first, then the model's buffers
   std::unique_ptr<SwinStage<T>> stage;
-  std::vector<void*> allocs;
   std::map<std::string, bool> seen;
   // weights (T): GEMM rows K-contiguous; convs [n][ky][kx][c]; ConvTranspose k2 s2 as [(q cout + co)][ci], q = dy 2 + dx
   T *w_emb = nullptr, *w_dconv = nullptr, *w_d0 = nullptr, *w_d3 = nullptr, *w_uconv = nullptr, *w_u0 = nullptr, *w_u3 = nullptr, *w_fc = nullptr;
@@ -156,18 +156,13 @@ struct FuxiModel : FuxiBase {
   char* zero_page;
   bool ready = false;
 
-  void* dalloc(size_t n) {
-    void* p = nullptr;
-    WX_HIP(hipMalloc(&p, n ? n : 16));
-    allocs.push_back(p);
-    return p;
-  }
+  void* dalloc(size_t n) { return mem.alloc(n ? n : 16); }   // a zero-size request still gets a distinct, non-null buffer
   // split (T = float; WX_PREC_FP32_SPLIT): every convolution / Linear of the forward and of the stage runs split-bf16 arithmetic from a
   // re-encoded shadow copy of its weight (wx_swin.h SwinStage::split); GroupNorm, LayerNorm, the patch reshapes and the attention stay fp32
   bool split = false;
   std::map<const void*, T*> split_of;
   const Options opt;   // the run-time switches, read once by wx_fuxi_create (wx_options.h)
-  FuxiModel(const FuxiDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4), opt(o) {
+  FuxiModel(const FuxiDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), mem(dev), split(split_mma && sizeof(T) == 4), opt(o) {
     if (d.H % d.ph || d.W % d.pw) throw std::runtime_error("fuxi: the image must be a multiple of the patch");
     Hp = d.H / d.ph; Wp = d.W / d.pw;
     if (Hp % 2 || Wp % 2) throw std::runtime_error("fuxi: the patch grid must be even (DownBlock halves it, UpBlock doubles it back)");
@@ -203,11 +198,6 @@ struct FuxiModel : FuxiBase {
     gn_part = (float2*)dalloc((size_t)cdiv((int64_t)Mp, 128) * dim * sizeof(float2));
     zero_page = (char*)dalloc(256);
     WX_HIP(hipMemset(zero_page, 0, 256));
-  }
-  ~FuxiModel() override {
-    (void)hipSetDevice(device);
-    stage.reset();
-    for (void* p : allocs) (void)hipFree(p);
   }
   void put(T* dst, const std::vector<float>& h) {
     std::vector<T> t(h.size());

@@ -227,21 +227,17 @@ struct PostOp {
 class PostBlock {
  public:
   PostBlock(int H, int W, int c_in, int frames, int c_out, int dev)
-      : h(H), w(W), cin(c_in), fr(frames), cout(c_out), device(dev), h_full(H) {
+      : h(H), w(W), cin(c_in), fr(frames), cout(c_out), device(dev), h_full(H), mem(dev) {
     if (H < 3 || W < 3 || c_in < 1 || c_out < 1 || frames < 1) throw std::runtime_error("wx_post_create: bad geometry");
     WX_HIP(hipSetDevice(device));
     n_blocks = cdiv((int64_t)H * W, 256);
-    partial = (double*)alloc((size_t)n_blocks * 4 * sizeof(double));
-    sums = (double*)alloc(4 * sizeof(double));
-    ratio = (float*)alloc(sizeof(float));
-  }
-  ~PostBlock() {
-    (void)hipSetDevice(device);
-    for (void* p : allocs) (void)hipFree(p);
+    partial = (double*)mem.alloc((size_t)n_blocks * 4 * sizeof(double));
+    sums = (double*)mem.alloc(4 * sizeof(double));
+    ratio = (float*)mem.alloc(sizeof(float));
   }
   int h, w, cin, fr, cout, device, n_blocks = 0;
   int h_full, row0 = 0;   // lat-band mode: the block covers rows [row0, row0 + h) of a grid of h_full rows
-  std::vector<void*> allocs;
+  DeviceArena mem;
   float *area = nullptr, *plev = nullptr, *coef_a = nullptr, *coef_b = nullptr;
   int n_p = 0, midpoint = 0, sigma = 0, sp_ind = -1;
   float *mean_in = nullptr, *std_in = nullptr, *mean_out = nullptr, *std_out = nullptr;
@@ -250,16 +246,10 @@ class PostBlock {
   std::vector<PostOp> ops;
   std::vector<double> last_sums;
 
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    WX_HIP(hipMalloc(&p, bytes));
-    allocs.push_back(p);
-    return p;
-  }
-  float* upload(const float* src, size_t n) {
-    float* d = (float*)alloc(n * sizeof(float));
-    WX_HIP(hipMemcpy(d, src, n * sizeof(float), hipMemcpyHostToDevice));
-    return d;
+  // a setter called again replaces its buffer: the old one is released, not left to the destructor
+  void reupload(float*& dst, const float* src, size_t n) {
+    mem.release(dst);
+    dst = mem.upload(src, n);
   }
   // Lat-band mode (wx_band.h): this block then sees only rows [r0, r0 + rows) of x and y; the grid arrays passed later are
   // still those of the WHOLE grid (cell areas need the neighbouring latitudes), and the fixers' global sums are completed
@@ -276,7 +266,7 @@ class PostBlock {
     if (n_levels < 2 || n_levels > kMaxLevels) throw std::runtime_error("wx_post_set_grid: 2..64 pressure levels");
     WX_HIP(hipSetDevice(device));
     set_area(lat2d, lon2d);
-    plev = upload(p_levels, n_levels);
+    reupload(plev, p_levels, n_levels);
     n_p = n_levels;
     midpoint = mid;
     sigma = 0;
@@ -287,8 +277,8 @@ class PostBlock {
     if (sp < 0 || sp >= cout || sp >= cin) throw std::runtime_error("wx_post_set_grid_sigma: surface-pressure channel out of range");
     WX_HIP(hipSetDevice(device));
     set_area(lat2d, lon2d);
-    coef_a = upload(ca, n_levels);
-    coef_b = upload(cb, n_levels);
+    reupload(coef_a, ca, n_levels);
+    reupload(coef_b, cb, n_levels);
     n_p = n_levels;
     midpoint = mid;
     sigma = 1;
@@ -315,12 +305,12 @@ class PostBlock {
         dlam = t - pi;
         a[(size_t)i * w + j] = std::fabs((float)(kRadEarth * kRadEarth) * dphi * dlam);
       }
-    area = upload(a.data() + (size_t)row0 * w, std::max<size_t>((size_t)h * w, 1));
+    reupload(area, a.data() + (size_t)row0 * w, std::max<size_t>((size_t)h * w, 1));
   }
   void set_stats(const float* mi, const float* si, const float* mo, const float* so) {
     WX_HIP(hipSetDevice(device));
-    mean_in = upload(mi, cin); std_in = upload(si, cin);
-    mean_out = upload(mo, cout); std_out = upload(so, cout);
+    reupload(mean_in, mi, cin); reupload(std_in, si, cin);
+    reupload(mean_out, mo, cout); reupload(std_out, so, cout);
   }
   void need_grid() const { if (!area) throw std::runtime_error("wx_post: call wx_post_set_grid first"); }
   void need_stats(int denorm) const { if (denorm && !mean_out) throw std::runtime_error("wx_post: denorm needs wx_post_set_stats first"); }
@@ -339,10 +329,9 @@ class PostBlock {
       if (inds[i] < 0 || inds[i] >= cout) throw std::runtime_error("wx_post: tracer index out of range");
       if (thres_max) hi[i] = thres_max[i];
     }
-    op.tr_inds = (int*)alloc(n * sizeof(int));
-    WX_HIP(hipMemcpy(op.tr_inds, inds, n * sizeof(int), hipMemcpyHostToDevice));
-    op.tr_lo = upload(thres, n);
-    op.tr_hi = upload(hi.data(), n);
+    op.tr_inds = mem.upload(inds, n);
+    op.tr_lo = mem.upload(thres, n);
+    op.tr_hi = mem.upload(hi.data(), n);
     ops.push_back(op);
   }
   void add_mass(int q0, int fix_level_num, int denorm) {
@@ -404,7 +393,7 @@ class PostBlock {
     for (int s : {T0, q0, U0, V0}) { check_block(s, op.nlev, cout, "3-D block (output)"); check_block(s, op.nlev, cin, "3-D block (input)"); }
     for (int k = 0; k < op.toa_n; ++k) check_block(op.toa_i[k], 1, cout, "flux channel");
     for (int k = 0; k < op.srf_n; ++k) check_block(op.srf_i[k], 1, cout, "flux channel");
-    op.gph = upload(gph_surf + (size_t)row0 * w, std::max<size_t>((size_t)h * w, 1));
+    op.gph = mem.upload(gph_surf + (size_t)row0 * w, std::max<size_t>((size_t)h * w, 1));
     ops.push_back(op);
   }
 

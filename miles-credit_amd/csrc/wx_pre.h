@@ -12,8 +12,8 @@
 //                                                         NaN, replacements in rule order (the last matching rule wins)
 //   credit/preblock/log.py:84-105           LogTransform log_base(x + eps) - log_base(eps), base e / 2 / 10 (correctly rounded: see xform_forward)
 //   credit/preblock/sqrt.py:52-71           SqrtTransform sqrtf(x)
-// x < -eps and sqrt of a negative give NaN as in the reference (no fast-math).  The plain kernel is untouched and is the one that runs
-// when no table is set, so that path keeps its bits.
+// x < -eps and sqrt of a negative give NaN as in the reference (no fast-math).  The plain kernel shares only the load / store body
+// (plane_pass4) with it and is the one that runs when no table is set, so that path keeps its bits.
 #pragma once
 #include <vector>
 
@@ -73,27 +73,17 @@ __device__ __forceinline__ float xform_forward(float v, int kind, float eps, flo
   }
 }
 
-// One plane (b, c, t) per blockIdx.y, four longitudes per thread like pre_assemble_kernel.  Every per-channel quantity is uniform in the
-// workgroup (scalar loads); the 16-byte path needs hw % 4 == 0 AND both plane pointers on 16 bytes (a field may be a view).
-__global__ __launch_bounds__(256) void pre_xform_kernel(const PreParams p, const PreXform t) {
-  const int64_t plane = (int64_t)blockIdx.y;
-  const int tt = (int)(plane % p.T);
-  const int c = (int)((plane / p.T) % p.C);
-  const int b = (int)(plane / ((int64_t)p.T * p.C));
-  const int f = p.ch_field[c], l = p.ch_level[c];
-  const float* __restrict__ src = p.field[f] + (((int64_t)b * p.f_levels[f] + l) * p.T + tt) * p.hw;
-  float* __restrict__ dst = p.x + plane * p.hw;
-  const float m = p.mean ? p.mean[c] : 0.f;
-  const float s = p.mean ? fmaxf(p.stdv[c], 1e-12f) : 1.f;
-  const int kind = t.kind[c], nr = t.n_rules[c];
-  const float eps = t.eps[c], log_eps = t.log_eps[c];
-  const int* __restrict__ rop = t.rule_op + (int64_t)c * kMaxFillRules;
-  const float* __restrict__ rs = t.rule_search + (int64_t)c * kMaxFillRules;
-  const float* __restrict__ rf = t.rule_fill + (int64_t)c * kMaxFillRules;
+// The body of a named-tensor pass (pre_assemble_kernel, pre_xform_kernel, unxform_kernel of wx_unxform.h): one plane (b, c, t) per
+// blockIdx.y, four longitudes per thread.  Loads 4 floats of the source plane, hands them to op(float (&v)[4]) to transform in place and
+// stores 4.  The 16-byte path needs hw % 4 == 0 AND both plane pointers on 16 bytes (a field may be a view that starts on a 4-byte
+// boundary); otherwise the scalar path, which pads v with zeros past the end of the plane and stores only what lies inside.
+template <typename Op>
+__device__ __forceinline__ void plane_pass4(const float* __restrict__ src, float* __restrict__ dst, int hw, Op op) {
   const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i >= p.hw) return;
-  const bool vec = (p.hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  const int n = vec ? 4 : min(4, p.hw - i);
+  // No early return for a thread past the plane's end (n <= 0: it loads and stores nothing): behind one, the compiler sinks the
+  // kernel's scalar loads of the plane pointers below the branch, onto every workgroup's critical path (measured: 2.5 % of the plain pass).
+  const int n = min(4, hw - i);
+  const bool vec = n == 4 && (hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
   float v[4] = {0.f, 0.f, 0.f, 0.f};
   if (vec) {
     const float4 q = *reinterpret_cast<const float4*>(src + i);
@@ -101,48 +91,80 @@ __global__ __launch_bounds__(256) void pre_xform_kernel(const PreParams p, const
   } else {
     for (int k = 0; k < n; ++k) v[k] = src[i + k];
   }
-  float r[4] = {v[0], v[1], v[2], v[3]};
-  for (int k = 0; k < nr; ++k) {
-    const int op = rop[k];
-    const float sv = rs[k], fv = rf[k];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = fill_match(op, v[j], sv) ? fv : r[j];   // mask on the original value v, not on r
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    r[j] = xform_forward(r[j], kind, eps, log_eps);
-    if (p.mean) r[j] = (r[j] - m) / s;
-  }
+  op(v);
   if (vec) {
-    *reinterpret_cast<float4*>(dst + i) = make_float4(r[0], r[1], r[2], r[3]);
+    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
   } else {
-    for (int k = 0; k < n; ++k) dst[i + k] = r[k];
+    for (int k = 0; k < n; ++k) dst[i + k] = v[k];
   }
+}
+// (b, c, t) of this workgroup's plane, for planes laid out [B][C][T]
+__device__ __forceinline__ void plane_decode(int C, int T, int& b, int& c, int& t) {
+  const int64_t plane = (int64_t)blockIdx.y;
+  t = (int)(plane % T);
+  c = (int)((plane / T) % C);
+  b = (int)(plane / ((int64_t)T * C));
+}
+// Launches such a kernel over `planes` planes of hw floats.  The plane index is the grid's y dimension, which ends at 65535: more is
+// refused with `too_many` here instead of being left to a failing launch.
+template <auto Kernel, typename... Args>
+inline void launch_plane_pass(int64_t planes, int hw, hipStream_t stream, const char* too_many, const Args&... args) {
+  if (planes > 65535) throw std::runtime_error(too_many);
+  hipLaunchKernelGGL(Kernel, dim3(cdiv(hw, 1024), (unsigned)planes), dim3(256), 0, stream, args...);
+  WX_HIP(hipGetLastError());
+}
+
+// Every per-channel quantity is uniform in the workgroup (scalar loads).
+__global__ __launch_bounds__(256) void pre_xform_kernel(const PreParams p, const PreXform t) {
+  int b, c, tt;
+  plane_decode(p.C, p.T, b, c, tt);
+  const int f = p.ch_field[c], l = p.ch_level[c];
+  const float* __restrict__ src = p.field[f] + (((int64_t)b * p.f_levels[f] + l) * p.T + tt) * p.hw;
+  float* __restrict__ dst = p.x + (int64_t)blockIdx.y * p.hw;
+  const bool norm = p.mean != nullptr;
+  const float m = norm ? p.mean[c] : 0.f;
+  const float s = norm ? fmaxf(p.stdv[c], 1e-12f) : 1.f;
+  const int kind = t.kind[c], nr = t.n_rules[c];
+  const float eps = t.eps[c], log_eps = t.log_eps[c];
+  const int* __restrict__ rop = t.rule_op + (int64_t)c * kMaxFillRules;
+  const float* __restrict__ rs = t.rule_search + (int64_t)c * kMaxFillRules;
+  const float* __restrict__ rf = t.rule_fill + (int64_t)c * kMaxFillRules;
+  plane_pass4(src, dst, p.hw, [=](float (&v)[4]) {
+    float r[4] = {v[0], v[1], v[2], v[3]};
+    for (int k = 0; k < nr; ++k) {
+      const int op = rop[k];
+      const float sv = rs[k], fv = rf[k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = fill_match(op, v[j], sv) ? fv : r[j];   // mask on the original value v, not on r
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r[j] = xform_forward(r[j], kind, eps, log_eps);
+      v[j] = norm ? (r[j] - m) / s : r[j];
+    }
+  });
 }
 
 __global__ __launch_bounds__(256) void pre_assemble_kernel(const PreParams p) {
-  const int64_t plane = (int64_t)blockIdx.y;           // (b, c, t)
-  const int t = (int)(plane % p.T);
-  const int c = (int)((plane / p.T) % p.C);
-  const int b = (int)(plane / ((int64_t)p.T * p.C));
+  int b, c, t;
+  plane_decode(p.C, p.T, b, c, t);
   const int f = p.ch_field[c], l = p.ch_level[c];
   const float* __restrict__ src = p.field[f] + (((int64_t)b * p.f_levels[f] + l) * p.T + t) * p.hw;
-  float* __restrict__ dst = p.x + plane * p.hw;
-  const float m = p.mean ? p.mean[c] : 0.f;
-  const float s = p.mean ? fmaxf(p.stdv[c], 1e-12f) : 1.f;   // std.clamp(min=1e-12), norm.py:98
-  const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i + 3 < p.hw && ((p.hw & 3) == 0)) {
-    const float4 v = *reinterpret_cast<const float4*>(src + i);
-    *reinterpret_cast<float4*>(dst + i) = p.mean ? make_float4((v.x - m) / s, (v.y - m) / s, (v.z - m) / s, (v.w - m) / s) : v;
-  } else {
-    for (int k = i; k < i + 4 && k < p.hw; ++k) dst[k] = p.mean ? (src[k] - m) / s : src[k];
-  }
+  float* __restrict__ dst = p.x + (int64_t)blockIdx.y * p.hw;
+  const bool norm = p.mean != nullptr;   // without statistics: a plain copy
+  const float m = norm ? p.mean[c] : 0.f;
+  const float s = norm ? fmaxf(p.stdv[c], 1e-12f) : 1.f;   // std.clamp(min=1e-12), norm.py:98
+  plane_pass4(src, dst, p.hw, [=](float (&v)[4]) {
+    if (!norm) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = (v[j] - m) / s;
+  });
 }
 
 class PreBlock {
  public:
   PreBlock(int n_fields, const int32_t* n_levels, int T_, int H, int W, const float* mean, const float* stdv, int dev)
-      : nf(n_fields), T(T_), hw(H * W), device(dev) {
+      : nf(n_fields), T(T_), hw(H * W), device(dev), mem(dev) {
     if (n_fields < 1 || n_fields > kMaxFields) throw std::runtime_error("wx_pre_create: 1..64 fields");
     if (T_ < 1 || H < 1 || W < 1) throw std::runtime_error("wx_pre_create: bad geometry");
     WX_HIP(hipSetDevice(device));
@@ -153,15 +175,11 @@ class PreBlock {
     }
     C = (int)cf.size();
     levels = fl;
-    ch_field = (int*)up(cf.data(), C * sizeof(int));
-    ch_level = (int*)up(cl.data(), C * sizeof(int));
-    f_levels = (int*)up(fl.data(), n_fields * sizeof(int));
+    ch_field = mem.upload(cf.data(), C);
+    ch_level = mem.upload(cl.data(), C);
+    f_levels = mem.upload(fl.data(), n_fields);
     if ((mean == nullptr) != (stdv == nullptr)) throw std::runtime_error("wx_pre_create: mean and std come together");
-    if (mean) { d_mean = (float*)up(mean, C * sizeof(float)); d_std = (float*)up(stdv, C * sizeof(float)); }
-  }
-  ~PreBlock() {
-    (void)hipSetDevice(device);
-    for (void* p : allocs) (void)hipFree(p);
+    if (mean) { d_mean = mem.upload(mean, C); d_std = mem.upload(stdv, C); }
   }
   int channels() const { return C; }
   // per-output-channel arrays ([C], rules [C][kMaxFillRules]); from now on apply() launches pre_xform_kernel
@@ -177,21 +195,14 @@ class PreBlock {
           throw std::runtime_error("wx_pre_set_transforms: unknown fill rule op " + std::to_string(rule_op[c * kMaxFillRules + k]));
     }
     WX_HIP(hipSetDevice(device));
-    if (!xf.kind) {
-      xf.kind = (int*)alloc(C * sizeof(int)); xf.n_rules = (int*)alloc(C * sizeof(int));
-      xf.eps = (float*)alloc(C * sizeof(float)); xf.log_eps = (float*)alloc(C * sizeof(float));
-      xf.rule_op = (int*)alloc((size_t)C * kMaxFillRules * sizeof(int));
-      xf.rule_search = (float*)alloc((size_t)C * kMaxFillRules * sizeof(float));
-      xf.rule_fill = (float*)alloc((size_t)C * kMaxFillRules * sizeof(float));
-    }
+    // a second call replaces the table: the buffers it replaces are released first (a synchronous free: launches in flight finish)
+    has_xf = false;
+    mem.release(xf.kind); mem.release(xf.n_rules); mem.release(xf.eps); mem.release(xf.log_eps);
+    mem.release(xf.rule_op); mem.release(xf.rule_search); mem.release(xf.rule_fill);
     const size_t nr = (size_t)C * kMaxFillRules;
-    WX_HIP(hipMemcpy((void*)xf.kind, kind, C * sizeof(int), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.n_rules, n_rules, C * sizeof(int), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.eps, eps, C * sizeof(float), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.log_eps, log_eps, C * sizeof(float), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.rule_op, rule_op, nr * sizeof(int), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.rule_search, rule_search, nr * sizeof(float), hipMemcpyHostToDevice));
-    WX_HIP(hipMemcpy((void*)xf.rule_fill, rule_fill, nr * sizeof(float), hipMemcpyHostToDevice));
+    xf.kind = mem.upload(kind, C); xf.n_rules = mem.upload(n_rules, C);
+    xf.eps = mem.upload(eps, C); xf.log_eps = mem.upload(log_eps, C);
+    xf.rule_op = mem.upload(rule_op, nr); xf.rule_search = mem.upload(rule_search, nr); xf.rule_fill = mem.upload(rule_fill, nr);
     has_xf = true;
   }
   void apply(const float* const* fields, float* x, int batch, hipStream_t stream) {
@@ -205,36 +216,20 @@ class PreBlock {
     }
     p.ch_field = ch_field; p.ch_level = ch_level; p.f_levels = f_levels; p.mean = d_mean; p.stdv = d_std;
     p.x = x; p.C = C; p.T = T; p.hw = hw; p.batch = batch;
-    if (has_xf) {
-      if ((int64_t)batch * C * T > 65535) throw std::runtime_error("wx_pre_apply: batch * channels * frames exceeds 65535 planes");
-      hipLaunchKernelGGL(pre_xform_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * T)), dim3(256), 0, stream, p, xf);
-    } else {
-      hipLaunchKernelGGL(pre_assemble_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * T)), dim3(256), 0, stream, p);
-    }
-    WX_HIP(hipGetLastError());
+    const int64_t planes = (int64_t)batch * C * T;
+    const char* too_many = "wx_pre_apply: batch * channels * frames exceeds 65535 planes";
+    if (has_xf) launch_plane_pass<pre_xform_kernel>(planes, hw, stream, too_many, p, xf);
+    else launch_plane_pass<pre_assemble_kernel>(planes, hw, stream, too_many, p);
   }
 
  private:
   int nf, T, hw, device, C = 0;
+  DeviceArena mem;
   std::vector<int> levels;
-  std::vector<void*> allocs;
   int *ch_field = nullptr, *ch_level = nullptr, *f_levels = nullptr;
   float *d_mean = nullptr, *d_std = nullptr;
   PreXform xf = {};
   bool has_xf = false;
-  void* alloc(size_t bytes) {
-    void* d = nullptr;
-    WX_HIP(hipMalloc(&d, bytes));
-    allocs.push_back(d);
-    return d;
-  }
-  void* up(const void* src, size_t bytes) {
-    void* d = nullptr;
-    WX_HIP(hipMalloc(&d, bytes));
-    allocs.push_back(d);
-    WX_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    return d;
-  }
 };
 
 }  // namespace wx

@@ -110,26 +110,21 @@ struct SwinStage : SwinStageBase {
     std::vector<bool> seen = std::vector<bool>(14, false);
   };
   std::vector<Block> blocks;
-  std::vector<void*> allocs;
+  DeviceArena mem;
   T *qkv = nullptr, *attn_o = nullptr, *branch = nullptr, *hidden = nullptr;
   char* zero_page = nullptr;
   char* sink = nullptr;
   bool use_stream = false;   // the four Linear layers on gemm_stream_kernel (wx_gemm_stream.h) instead of the 128 x 128 tile kernel
   bool ready = false;
 
-  void* dalloc(size_t n) {
-    void* p = nullptr;
-    WX_HIP(hipMalloc(&p, n ? n : 16));
-    allocs.push_back(p);
-    return p;
-  }
+  void* dalloc(size_t n) { return mem.alloc(n ? n : 16); }   // a zero-size request still gets a distinct, non-null buffer
   // split (T = float; WX_PREC_FP32_SPLIT): the four Linear layers run split-bf16 arithmetic -- every GEMM weight gets a re-encoded shadow copy
   // (wx_gemm.h split_encode_chunks) that `linear` hands to the implicit-GEMM kernel with ConvGemmParams::split; the attention kernel
   // (general head dimension, seam mask, cosine mode) and the LayerNorm kernels stay exact fp32
   bool split = false;
   std::map<const void*, T*> split_of;
   const Options opt;   // the run-time switches, read once by wx_swin_create / wx_fuxi_create (wx_options.h)
-  SwinStage(const SwinDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), split(split_mma && sizeof(T) == 4), opt(o) {
+  SwinStage(const SwinDesc& desc, int dev, const Options& o, bool split_mma = false) : d(desc), device(dev), mem(dev), split(split_mma && sizeof(T) == 4), opt(o) {
     constexpr int VEC = 16 / (int)sizeof(T);
     if (d.C % 64 || d.hidden % 64 || d.C % d.heads) throw std::runtime_error("swin: C and hidden must be multiples of 64, C of heads");
     const int hd = d.C / d.heads;
@@ -169,10 +164,6 @@ struct SwinStage : SwinStageBase {
     hidden = (T*)dalloc(M * d.hidden * sizeof(T));
     zero_page = (char*)dalloc(256);
     WX_HIP(hipMemset(zero_page, 0, 256));
-  }
-  ~SwinStage() override {
-    (void)hipSetDevice(device);
-    for (void* p : allocs) (void)hipFree(p);
   }
   void put_w(T* dst, const float* src, int64_t n, int64_t want, T* dst_kb = nullptr, int64_t K = 0) {
     if (n != want) throw std::runtime_error("swin: tensor has " + std::to_string(n) + " elements, expected " + std::to_string(want));

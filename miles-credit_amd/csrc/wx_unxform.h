@@ -51,10 +51,8 @@ __device__ __forceinline__ float scale_unfused(float y, float s, float m) {
 }
 
 __global__ __launch_bounds__(256) void unxform_kernel(const UnxParams p) {
-  const int64_t plane = (int64_t)blockIdx.y;           // (b, c, t)
-  const int t = (int)(plane % p.T);
-  const int c = (int)((plane / p.T) % p.C);
-  const int b = (int)(plane / ((int64_t)p.T * p.C));
+  int b, c, t;
+  plane_decode(p.C, p.T, b, c, t);
   const int f = p.ch_var[c], l = p.ch_level[c];
   const float* __restrict__ src = p.src[f] + (int64_t)b * p.bstride[f] + ((int64_t)l * p.T + t) * p.hw;
   float* __restrict__ dst = p.dst[f] + (((int64_t)b * p.v_levels[f] + l) * p.T + t) * p.hw;
@@ -62,27 +60,13 @@ __global__ __launch_bounds__(256) void unxform_kernel(const UnxParams p) {
   const float m = scale ? p.mean[c] : 0.f, s = scale ? p.stdv[c] : 1.f;
   const int kind = p.v_kind[f];
   const float eps = p.v_eps[f], log_eps = p.v_log_eps[f];
-  const int i = (blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i >= p.hw) return;
-  const bool vec = (p.hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-  const int n = vec ? 4 : min(4, p.hw - i);
-  float v[4] = {0.f, 0.f, 0.f, 0.f};
-  if (vec) {
-    const float4 q = *reinterpret_cast<const float4*>(src + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    for (int k = 0; k < n; ++k) v[k] = src[i + k];
-  }
+  plane_pass4(src, dst, p.hw, [=](float (&v)[4]) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (scale) v[j] = scale_unfused(v[j], s, m);
-    v[j] = xform_inverse(v[j], kind, eps, log_eps);
-  }
-  if (vec) {
-    *reinterpret_cast<float4*>(dst + i) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-    for (int k = 0; k < n; ++k) dst[i + k] = v[k];
-  }
+    for (int j = 0; j < 4; ++j) {
+      if (scale) v[j] = scale_unfused(v[j], s, m);
+      v[j] = xform_inverse(v[j], kind, eps, log_eps);
+    }
+  });
 }
 
 class Unxform {
@@ -91,29 +75,24 @@ class Unxform {
   // variable has statistics
   Unxform(int n_vars, const int32_t* n_levels, int H, int W, const int32_t* kind, const float* eps, const float* log_eps,
           const int32_t* has_stats, const float* mean, const float* stdv, int dev)
-      : nv(n_vars), hw(H * W), device(dev) {
+      : nv(n_vars), hw(H * W), device(dev), mem(dev) {
     WX_HIP(hipSetDevice(device));
     std::vector<int> cv, cl, vl(n_levels, n_levels + n_vars), vk(kind, kind + n_vars), vs(has_stats, has_stats + n_vars);
     for (int v = 0; v < n_vars; ++v)
       for (int l = 0; l < n_levels[v]; ++l) { cv.push_back(v); cl.push_back(l); }
     C = (int)cv.size();
-    ch_var = (int*)up(cv.data(), C * sizeof(int));
-    ch_level = (int*)up(cl.data(), C * sizeof(int));
-    v_levels = (int*)up(vl.data(), nv * sizeof(int));
-    v_kind = (int*)up(vk.data(), nv * sizeof(int));
-    v_stats = (int*)up(vs.data(), nv * sizeof(int));
-    v_eps = (float*)up(eps, nv * sizeof(float));
-    v_log_eps = (float*)up(log_eps, nv * sizeof(float));
-    if (mean) { d_mean = (float*)up(mean, C * sizeof(float)); d_std = (float*)up(stdv, C * sizeof(float)); }
-  }
-  ~Unxform() {
-    (void)hipSetDevice(device);
-    for (void* p : allocs) (void)hipFree(p);
+    ch_var = mem.upload(cv.data(), C);
+    ch_level = mem.upload(cl.data(), C);
+    v_levels = mem.upload(vl.data(), nv);
+    v_kind = mem.upload(vk.data(), nv);
+    v_stats = mem.upload(vs.data(), nv);
+    v_eps = mem.upload(eps, nv);
+    v_log_eps = mem.upload(log_eps, nv);
+    if (mean) { d_mean = mem.upload(mean, C); d_std = mem.upload(stdv, C); }
   }
   int variables() const { return nv; }
   void apply(const float* const* src, const int64_t* batch_stride, float* const* dst, int batch, int n_time, hipStream_t stream) {
     if (batch < 1 || n_time < 1) throw std::runtime_error("wx_unxform_apply: batch and n_time must be >= 1");
-    if ((int64_t)batch * C * n_time > 65535) throw std::runtime_error("wx_unxform_apply: batch * levels * n_time exceeds 65535 planes");
     WX_HIP(hipSetDevice(device));
     UnxParams p;
     std::memset(&p, 0, sizeof(p));
@@ -125,22 +104,14 @@ class Unxform {
     p.ch_var = ch_var; p.ch_level = ch_level; p.v_levels = v_levels; p.v_kind = v_kind; p.v_stats = v_stats;
     p.v_eps = v_eps; p.v_log_eps = v_log_eps; p.mean = d_mean; p.stdv = d_std;
     p.C = C; p.T = n_time; p.hw = hw;
-    hipLaunchKernelGGL(unxform_kernel, dim3(cdiv(hw, 1024), (unsigned)((int64_t)batch * C * n_time)), dim3(256), 0, stream, p);
-    WX_HIP(hipGetLastError());
+    launch_plane_pass<unxform_kernel>((int64_t)batch * C * n_time, hw, stream, "wx_unxform_apply: batch * levels * n_time exceeds 65535 planes", p);
   }
 
  private:
   int nv, hw, device, C = 0;
-  std::vector<void*> allocs;
+  DeviceArena mem;
   int *ch_var = nullptr, *ch_level = nullptr, *v_levels = nullptr, *v_kind = nullptr, *v_stats = nullptr;
   float *v_eps = nullptr, *v_log_eps = nullptr, *d_mean = nullptr, *d_std = nullptr;
-  void* up(const void* src, size_t bytes) {
-    void* d = nullptr;
-    WX_HIP(hipMalloc(&d, bytes));
-    allocs.push_back(d);
-    WX_HIP(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-    return d;
-  }
 };
 
 }  // namespace wx

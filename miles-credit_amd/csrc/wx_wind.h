@@ -346,23 +346,15 @@ class Wind {
  public:
   // w / n: smoothing latitude, smoothing longitude, falloff latitude, falloff longitude (host arrays, checked by wind_check_create)
   Wind(int H_, int W_, const float* const w[4], const int n[4], int dil_lat_, int dil_lon_, float threshold, bool preserve_, int dev)
-      : H(H_), W(W_), dil_lat(dil_lat_), dil_lon(dil_lon_), thr(threshold), preserve(preserve_), device(dev) {
+      : H(H_), W(W_), dil_lat(dil_lat_), dil_lon(dil_lon_), thr(threshold), preserve(preserve_), device(dev), mem(dev) {
     WX_HIP(hipSetDevice(device));
     for (int i = 0; i < 4; ++i) {
       k[i] = n[i];
-      WX_HIP(hipMalloc(&wdev[i], n[i] * sizeof(float)));
-      WX_HIP(hipMemcpy(wdev[i], w[i], n[i] * sizeof(float), hipMemcpyHostToDevice));
+      wdev[i] = mem.upload(w[i], n[i]);
     }
     grid.H = H; grid.W = W;
     grid.tiles_x = (W + kWindTW - 1) / kWindTW;
     grid.tiles_y = (H + kWindTH - 1) / kWindTH;
-  }
-  ~Wind() {
-    (void)hipSetDevice(device);
-    for (float* p : wdev) (void)hipFree(p);
-    (void)hipFree(dil);
-    (void)hipFree(mask);
-    (void)hipFree(partial);
   }
   int launches() const { return preserve ? 4 : 3; }
   // mask_out: [batch][H][W] on the device, or nullptr (the mask then lives in the object's own buffer)
@@ -401,19 +393,20 @@ class Wind {
   float thr;
   bool preserve;
   int device;
+  DeviceArena mem;
   int k[4] = {0, 0, 0, 0};
   float* wdev[4] = {nullptr, nullptr, nullptr, nullptr};
   WindGrid grid;
   float *dil = nullptr, *mask = nullptr;
   double* partial = nullptr;
   size_t dil_floats = 0, mask_floats = 0, partial_doubles = 0;
-  // scratch sized by the batch seen so far (hipFree waits for the kernels that still read the old buffer)
+  // scratch sized by the batch seen so far (release is a plain hipFree, which waits for the kernels that still read the old buffer)
   template <typename T>
   void grow(T*& p, size_t& have, size_t want) {
     if (want <= have) return;
-    if (p) WX_HIP(hipFree(p));
-    p = nullptr; have = 0;
-    WX_HIP(hipMalloc(&p, want * sizeof(T)));
+    have = 0;
+    mem.release(p);
+    p = (T*)mem.alloc(want * sizeof(T));
     have = want;
   }
 };

@@ -201,6 +201,65 @@ def _check(status: int):
         raise WXEngineError(f"wxengine error {status}: {msg}")
 
 
+class NativeHandle:
+    """One handle of the C ABI and the wx_*_destroy that frees it.  ctypes takes the object itself wherever a handle is an argument
+    (`_as_parameter_`); `out` is the out argument of the wx_*_create call that fills it."""
+
+    def __init__(self, destroy):
+        self._as_parameter_ = C.c_void_p()
+        self._destroy = destroy
+
+    @property
+    def out(self):
+        return C.byref(self._as_parameter_)
+
+    def close(self) -> None:
+        h, self._as_parameter_ = self._as_parameter_, C.c_void_p()
+        if h.value:
+            self._destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _gpu_tensor(t, ndim=None, contiguous=False, item_contiguous=False, device=None, dtype=None) -> bool:
+    """The test of a tensor that goes to the library as a raw pointer: a torch tensor on the GPU, float32 (or `dtype`) and, where
+    asked, of `ndim` dims, contiguous as a whole or per batch item, on GPU `device`.  The caller words the error."""
+    import torch
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == (dtype or torch.float32)
+            and (ndim is None or t.dim() == ndim) and (not contiguous or t.is_contiguous())
+            and (not item_contiguous or t[0].is_contiguous()) and (device is None or t.device.index == device))
+
+
+def _f32(a):
+    """float* to a numpy argument (made contiguous float32 if it is not; the pointer keeps the array alive); None stays None."""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _i32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _stream_ptr(device=None):
+    """torch's current stream on `device` (None: the current device) as the ABI's stream argument."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _named_tensor_args(ts):
+    """A list of named tensors [B, n_levels, T, H, W] (checked by the caller: float32, one device, batch items contiguous), read
+    where they lie -> (source pointer array, batch strides in floats -- 0 when B = 1 --, levels, fresh contiguous outputs, their
+    pointer array)."""
+    import torch
+    n, B = len(ts), ts[0].shape[0]
+    outs = [torch.empty(t.shape, dtype=torch.float32, device=t.device) for t in ts]
+    return ((C.c_void_p * n)(*[t.data_ptr() for t in ts]), (C.c_int64 * n)(*[t.stride(0) if B > 1 else 0 for t in ts]),
+            (C.c_int32 * n)(*[t.shape[1] for t in ts]), outs, (C.c_void_p * n)(*[o.data_ptr() for o in outs]))
+
+
 def make_c_config(cfg: WXConfig, precision: str = "bf16", max_batch: int = 1) -> wx_config:
     c = wx_config()
     c.abi_version = WX_ABI_VERSION
@@ -245,18 +304,10 @@ class WXEngine:
         self.cfg = cfg
         self.precision = precision
         self.device = device
-        self._h = C.c_void_p()
+        self._h = NativeHandle(self.lib.wx_destroy)
         cc = make_c_config(cfg, precision)
-        _check(self.lib.wx_create(C.byref(cc), device, C.byref(self._h)))
+        _check(self.lib.wx_create(C.byref(cc), device, self._h.out))
         self._finalized = False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self.lib.wx_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
     # ---- weights -----------------------------------------------------------------
     def expected_tensors(self) -> Dict[str, Tuple[int, ...]]:
@@ -276,7 +327,7 @@ class WXEngine:
                 v = v.detach().to("cpu").float().numpy()
             a = np.ascontiguousarray(v, dtype=np.float32)
             shp = (C.c_int64 * max(a.ndim, 1))(*a.shape) if a.ndim else (C.c_int64 * 1)(1)
-            _check(self.lib.wx_load_tensor(self._h, k.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), max(a.ndim, 1), shp))
+            _check(self.lib.wx_load_tensor(self._h, k.encode(), _f32(a), max(a.ndim, 1), shp))
         self._finalized = False
 
     def finalize(self) -> None:
@@ -285,17 +336,11 @@ class WXEngine:
 
     # ---- glue configuration --------------------------------------------------------
     def set_denorm(self, mean, std) -> None:
-        m = np.ascontiguousarray(mean, dtype=np.float32).ravel()
-        s = np.ascontiguousarray(std, dtype=np.float32).ravel()
-        _check(self.lib.wx_set_denorm(self._h, m.ctypes.data_as(C.POINTER(C.c_float)), s.ctypes.data_as(C.POINTER(C.c_float)), m.size))
+        m, s = _fp(mean).ravel(), _fp(std).ravel()
+        _check(self.lib.wx_set_denorm(self._h, _f32(m), _f32(s), m.size))
 
     def set_tracer_fixer(self, inds, thres, thres_max=None, denorm: bool = False) -> None:
-        i = np.ascontiguousarray(inds, dtype=np.int32)
-        t = np.ascontiguousarray(thres, dtype=np.float32)
-        tm = None if thres_max is None else np.ascontiguousarray(thres_max, dtype=np.float32)
-        _check(self.lib.wx_set_tracer_fixer(
-            self._h, i.ctypes.data_as(C.POINTER(C.c_int32)), t.ctypes.data_as(C.POINTER(C.c_float)),
-            None if tm is None else tm.ctypes.data_as(C.POINTER(C.c_float)), i.size, int(denorm)))
+        _check(self.lib.wx_set_tracer_fixer(self._h, _i32(inds), _f32(thres), _f32(thres_max), np.size(inds), int(denorm)))
 
     def set_layout(self, n_prog: int, n_static: int, n_dyn: int) -> None:
         _check(self.lib.wx_set_layout(self._h, n_prog, n_static, n_dyn))
@@ -307,20 +352,18 @@ class WXEngine:
         (wxengine.rollout.build_channel_layout produces it from a CREDIT config)."""
         code = {"prognostic": 0, "dynamic_forcing": 1, "static": 2}
         rows = [(code.get(k, k), int(x0), int(0 if s0 is None else s0), int(n)) for k, x0, s0, n in groups]
-        arr = [np.ascontiguousarray([r[i] for r in rows], dtype=np.int32) for i in range(4)]
-        _check(self.lib.wx_set_layout_groups(self._h, len(rows), *[a.ctypes.data_as(C.POINTER(C.c_int32)) for a in arr]))
+        _check(self.lib.wx_set_layout_groups(self._h, len(rows), *[_i32([r[i] for r in rows]) for i in range(4)]))
         # the C side sizes the forcing tensor as max(src_start + count) over the forcing groups (wx_engine.hip, set_layout_groups)
         self._n_dyn = max([r[2] + r[3] for r in rows if r[0] == 1], default=0)
 
     # ---- hot path -------------------------------------------------------------------
     @staticmethod
     def _stream():
-        import torch
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _stream_ptr()
 
-    def _chk_in(self, t, name):
-        import torch
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+    @staticmethod
+    def _chk_in(t, name):
+        if not _gpu_tensor(t, contiguous=True):
             raise WXEngineError(f"{name} must be a contiguous float32 tensor on the GPU")
 
     def forward(self, x, out=None):
@@ -429,7 +472,7 @@ class WXEngine:
         shape = (C.c_int64 * 3)()
         _check(self.lib.wx_debug_read(self._h, name.encode(), None, 0, shape))
         out = np.empty((shape[0], shape[1], shape[2]), dtype=np.float32)
-        _check(self.lib.wx_debug_read(self._h, name.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, shape))
+        _check(self.lib.wx_debug_read(self._h, name.encode(), _f32(out), out.size, shape))
         return out
 
     def query(self, key: str) -> int:
@@ -474,48 +517,30 @@ class WXPostBlock:
         if not torch.cuda.is_available():
             raise WXEngineError("no GPU visible: the post block has no CPU fallback")
         self.shape = (H, W, c_in, frames, c_out)
-        self._p = C.c_void_p()
-        _check(self.lib.wx_post_create(H, W, c_in, frames, c_out, device, C.byref(self._p)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_p", None) and self._p.value:
-                self.lib.wx_post_destroy(self._p)
-                self._p = C.c_void_p()
-        except Exception:
-            pass
-
-    @staticmethod
-    def _ptr(a):
-        return a.ctypes.data_as(C.POINTER(C.c_float))
+        self._p = NativeHandle(self.lib.wx_post_destroy)
+        _check(self.lib.wx_post_create(H, W, c_in, frames, c_out, device, self._p.out))
 
     def set_band(self, row0: int, rows: int):
         """Lat-band mode: this block sees rows [row0, row0+rows) only (call before set_grid*; the grid arrays stay whole-grid)."""
         _check(self.lib.wx_post_set_band(self._p, int(row0), int(rows)))
 
     def set_grid(self, lat2d, lon2d, p_levels, midpoint: bool = False):
-        la, lo, pl = _fp(lat2d), _fp(lon2d), _fp(p_levels)
-        _check(self.lib.wx_post_set_grid(self._p, self._ptr(la), self._ptr(lo), self._ptr(pl), pl.size, int(midpoint)))
+        pl = _fp(p_levels)
+        _check(self.lib.wx_post_set_grid(self._p, _f32(lat2d), _f32(lon2d), _f32(pl), pl.size, int(midpoint)))
 
     def set_grid_sigma(self, lat2d, lon2d, coef_a, coef_b, sp_ind: int, midpoint: bool = False):
         """Hybrid sigma-pressure levels p = a + b * surface pressure (credit/physics_core.py:300-368); `sp_ind` is the
         surface-pressure channel (same index in x and y, credit/postblock/gen1.py:306-308)."""
-        la, lo, ca, cb = _fp(lat2d), _fp(lon2d), _fp(coef_a), _fp(coef_b)
+        ca, cb = _fp(coef_a), _fp(coef_b)
         if ca.size != cb.size:
             raise ValueError("coef_a and coef_b must have the same length")
-        _check(self.lib.wx_post_set_grid_sigma(self._p, self._ptr(la), self._ptr(lo), self._ptr(ca), self._ptr(cb), ca.size,
-                                               int(midpoint), int(sp_ind)))
+        _check(self.lib.wx_post_set_grid_sigma(self._p, _f32(lat2d), _f32(lon2d), _f32(ca), _f32(cb), ca.size, int(midpoint), int(sp_ind)))
 
     def set_stats(self, mean_in, std_in, mean_out, std_out):
-        a = [_fp(v).ravel() for v in (mean_in, std_in, mean_out, std_out)]
-        _check(self.lib.wx_post_set_stats(self._p, *[self._ptr(v) for v in a]))
+        _check(self.lib.wx_post_set_stats(self._p, *[_f32(_fp(v).ravel()) for v in (mean_in, std_in, mean_out, std_out)]))
 
     def add_tracer_fixer(self, inds, thres, thres_max=None, denorm=False):
-        i = np.ascontiguousarray(inds, dtype=np.int32)
-        t = _fp(thres)
-        tm = None if thres_max is None else _fp(thres_max)
-        _check(self.lib.wx_post_add_tracer_fixer(self._p, i.ctypes.data_as(C.POINTER(C.c_int32)), self._ptr(t),
-                                                 None if tm is None else self._ptr(tm), i.size, int(denorm)))
+        _check(self.lib.wx_post_add_tracer_fixer(self._p, _i32(inds), _f32(thres), _f32(thres_max), np.size(inds), int(denorm)))
 
     def add_mass_fixer(self, q_start, fix_level_num, denorm=False):
         _check(self.lib.wx_post_add_mass_fixer(self._p, q_start, fix_level_num, int(denorm)))
@@ -524,45 +549,31 @@ class WXPostBlock:
         _check(self.lib.wx_post_add_water_fixer(self._p, q_start, precip_ind, evapor_ind, float(n_seconds), int(denorm)))
 
     def add_energy_fixer(self, T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm=False):
-        r = np.ascontiguousarray(rad_inds, dtype=np.int32)
-        assert r.size == 6
-        g = _fp(gph_surf)
-        _check(self.lib.wx_post_add_energy_fixer(self._p, T_start, q_start, U_start, V_start,
-                                                 r.ctypes.data_as(C.POINTER(C.c_int32)), self._ptr(g), float(n_seconds), int(denorm)))
+        assert np.size(rad_inds) == 6
+        _check(self.lib.wx_post_add_energy_fixer(self._p, T_start, q_start, U_start, V_start, _i32(rad_inds), _f32(gph_surf),
+                                                 float(n_seconds), int(denorm)))
 
     def add_energy_fixer_signed(self, T_start, q_start, U_start, V_start, toa, surf, gph_surf, n_seconds, denorm=False):
         """toa / surf: lists of (channel, sign): R_T = sum sign * y[channel] (<= 4 terms), F_S likewise (<= 8)."""
-        ti = np.ascontiguousarray([c for c, _ in toa], dtype=np.int32)
-        ts = np.ascontiguousarray([s for _, s in toa], dtype=np.float32)
-        si = np.ascontiguousarray([c for c, _ in surf], dtype=np.int32)
-        ss = np.ascontiguousarray([s for _, s in surf], dtype=np.float32)
-        g = _fp(gph_surf)
-        ip, fp = C.POINTER(C.c_int32), C.POINTER(C.c_float)
-        _check(self.lib.wx_post_add_energy_fixer_signed(self._p, T_start, q_start, U_start, V_start, ti.size, ti.ctypes.data_as(ip),
-                                                        ts.ctypes.data_as(fp), si.size, si.ctypes.data_as(ip), ss.ctypes.data_as(fp),
-                                                        self._ptr(g), float(n_seconds), int(denorm)))
+        _check(self.lib.wx_post_add_energy_fixer_signed(self._p, T_start, q_start, U_start, V_start, len(toa), _i32([c for c, _ in toa]),
+                                                        _f32([s for _, s in toa]), len(surf), _i32([c for c, _ in surf]),
+                                                        _f32([s for _, s in surf]), _f32(gph_surf), float(n_seconds), int(denorm)))
 
     def add_energy_fixer_updown(self, T_start, q_start, U_start, V_start, flux_inds, gph_surf, n_seconds, denorm=False):
         """GlobalEnergyFixerUpDown (credit/postblock/gen1.py:825-1030); flux_inds = [TOA down solar, TOA up solar, TOA up OLR,
         surf down solar, surf up solar, surf down LW, surf up LW, SH, LH]."""
-        r = np.ascontiguousarray(flux_inds, dtype=np.int32)
-        assert r.size == 9
-        g = _fp(gph_surf)
-        _check(self.lib.wx_post_add_energy_fixer_updown(self._p, T_start, q_start, U_start, V_start,
-                                                        r.ctypes.data_as(C.POINTER(C.c_int32)), self._ptr(g), float(n_seconds),
-                                                        int(denorm)))
+        assert np.size(flux_inds) == 9
+        _check(self.lib.wx_post_add_energy_fixer_updown(self._p, T_start, q_start, U_start, V_start, _i32(flux_inds), _f32(gph_surf),
+                                                        float(n_seconds), int(denorm)))
 
     def apply(self, x, y):
         """x [C_in, frames, H, W], y [C_out, H, W] float32 CUDA tensors (leading batch dim of 1 allowed); y is fixed in place."""
-        import torch
-        for t, n in ((x, "x"), (y, "y")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise WXEngineError(f"{n} must be a contiguous float32 tensor on the GPU")
+        WXEngine._chk_in(x, "x")
+        WXEngine._chk_in(y, "y")
         H, W, c_in, fr, c_out = self.shape
         if x.numel() != c_in * fr * H * W or y.numel() != c_out * H * W:
             raise WXEngineError("post block: tensor sizes do not match the geometry")
-        _check(self.lib.wx_post_apply(self._p, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()),
-                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        _check(self.lib.wx_post_apply(self._p, C.c_void_p(x.data_ptr()), C.c_void_p(y.data_ptr()), _stream_ptr()))
         return y
 
 
@@ -576,21 +587,12 @@ class WXDiag:
         if not torch.cuda.is_available():
             raise WXEngineError("no GPU visible: the pressure-level products have no CPU fallback")
         self.H, self.W, self.L, self.device = int(H), int(W), int(n_levels), int(device)
-        self._d = C.c_void_p()
-        _check(self.lib.wx_diag_create(self.H, self.W, self.L, self.device, C.byref(self._d)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_d", None) and self._d.value:
-                self.lib.wx_diag_destroy(self._d)
-                self._d = C.c_void_p()
-        except Exception:
-            pass
+        self._d = NativeHandle(self.lib.wx_diag_destroy)
+        _check(self.lib.wx_diag_create(self.H, self.W, self.L, self.device, self._d.out))
 
     def set_levels(self, a_half=None, b_half=None, a_mid=None, b_mid=None, flip_vertical: bool = True):
         """Hybrid coefficients in the stored level order: a_half / b_half [n_levels + 1] for the geopotential, a_mid / b_mid
         [n_levels] for the interpolation; either pair may be None."""
-        fp = C.POINTER(C.c_float)
         arrs = []
         for name, a, n in (("a_half", a_half, self.L + 1), ("b_half", b_half, self.L + 1), ("a_mid", a_mid, self.L), ("b_mid", b_mid, self.L)):
             if a is None:
@@ -600,11 +602,11 @@ class WXDiag:
             if a.size != n:
                 raise WXEngineError(f"n_levels mismatch: {name} has {a.size} entries, the block was created for {self.L} levels ({n} expected)")
             arrs.append(a)
-        _check(self.lib.wx_diag_set_levels(self._d, *[None if a is None else a.ctypes.data_as(fp) for a in arrs], int(bool(flip_vertical))))
+        _check(self.lib.wx_diag_set_levels(self._d, *[_f32(a) for a in arrs], int(bool(flip_vertical))))
 
     def set_pressure_levels(self, p_pa, temp_height: float = 150.0):
         p = _fp(p_pa).ravel()
-        _check(self.lib.wx_diag_set_pressure_levels(self._d, p.ctypes.data_as(C.POINTER(C.c_float)), p.size, float(temp_height)))
+        _check(self.lib.wx_diag_set_pressure_levels(self._d, _f32(p), p.size, float(temp_height)))
         self.n_plev = p.size
 
     def apply(self, sp, phis, T=None, q=None, t_ns=None, fields=(), z_in=None, want_z=False, want_plev=False, want_mslp=False):
@@ -623,9 +625,9 @@ class WXDiag:
         for name, t, nl in named:
             if t is None:
                 continue
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 5):
+            if not _gpu_tensor(t, ndim=5):
                 raise WXEngineError(f"{name} must be a float32 [B, n_levels, n_time, H, W] tensor on the GPU")
-            if t.device.index != self.device:
+            if not _gpu_tensor(t, device=self.device):
                 raise WXEngineError(f"{name} is on cuda:{t.device.index} but this block was created for cuda:{self.device}")
             if nl == self.L and t.shape[1] != self.L:
                 raise WXEngineError(f"n_levels mismatch: {name} has {t.shape[1]} levels, the block was created for {self.L}")
@@ -645,7 +647,7 @@ class WXDiag:
             out["mslp"] = torch.empty((B, 1, nT, self.H, self.W), **kw)
         ins = [t for _, t, _ in named if t is not None]
         whole = all(t.is_contiguous() for t in ins) and phis.shape[0] == B
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = _stream_ptr(self.device)
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
         for b in ([None] if whole else range(B)):
             def item(t, shared=False):

@@ -22,7 +22,7 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .engine import PREC, WXEngineError, _check, load_library
+from .engine import PREC, NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, load_library
 from .swin import TIMM_DERIVED_SUFFIXES, effective_logit_scale, relative_position_bias, timm_block_tensors
 from .synth import keyed_normal, power_iterate
 
@@ -320,22 +320,13 @@ class FuxiHIP:
         g = cfg.groups
         d = wx_fuxi_desc(PREC[precision], cfg.image_height, cfg.image_width, cfg.in_chans, cfg.out_chans, cfg.frames, cfg.patch_height,
                          cfg.patch_width, cfg.dim, cfg.num_heads, cfg.window_size, cfg.depth, g[0], g[1], STAGE_VARIANT[cfg.stage])
-        self._h = C.c_void_p()
+        self._h = NativeHandle(self.lib.wx_fuxi_destroy)
         self.lib.wx_fuxi_create.argtypes = [C.POINTER(wx_fuxi_desc), C.c_int, C.POINTER(C.c_void_p)]
-        _check(self.lib.wx_fuxi_create(C.byref(d), self.device, C.byref(self._h)))
+        _check(self.lib.wx_fuxi_create(C.byref(d), self.device, self._h.out))
         self._loaded = False
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self.lib.wx_fuxi_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def _put(self, name: str, arr) -> None:
-        a = np.ascontiguousarray(np.asarray(arr, dtype=np.float32))
-        _check(self.lib.wx_fuxi_load(self._h, name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(a.size)))
+        _check(self.lib.wx_fuxi_load(self._h, name.encode(), _f32(arr), C.c_int64(np.size(arr))))
 
     def load_state_dict(self, sd, strict: bool = True) -> None:
         """sd with the reference's keys (see the module docstring); strict: unknown / missing keys raise KeyError."""
@@ -386,7 +377,7 @@ class FuxiHIP:
         shape = (C.c_int64 * 3)()
         _check(self.lib.wx_fuxi_debug_map(self._h, name.encode(), None, C.c_int64(0), shape))
         out = np.empty(tuple(int(s) for s in shape), dtype=np.float32)
-        _check(self.lib.wx_fuxi_debug_map(self._h, name.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(out.size), shape))
+        _check(self.lib.wx_fuxi_debug_map(self._h, name.encode(), _f32(out), C.c_int64(out.size), shape))
         return out
 
     def forward(self, x, out=None):
@@ -395,7 +386,7 @@ class FuxiHIP:
         if not self._loaded:
             raise WXEngineError("load_state_dict first")
         want = (cfg.in_chans, cfg.frames, cfg.image_height, cfg.image_width)
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and tuple(x.shape[1:]) == want):
+        if not (_gpu_tensor(x, ndim=5) and tuple(x.shape[1:]) == want):
             raise WXEngineError(f"x must be a float32 GPU tensor [B, {', '.join(map(str, want))}], got "
                                 f"{tuple(x.shape) if hasattr(x, 'shape') else type(x)}")
         if x.device.index != self.device:
@@ -405,7 +396,7 @@ class FuxiHIP:
         if out is None:
             out = torch.empty((B, cfg.out_chans, 1, cfg.image_height, cfg.image_width), dtype=torch.float32, device=x.device)
         with torch.cuda.device(self.device):
-            s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            s = _stream_ptr(self.device)
             for b in range(B):
                 _check(self.lib.wx_fuxi_forward(self._h, C.c_void_p(x[b].data_ptr()), C.c_void_p(out[b].data_ptr()), s))
         return out

@@ -20,7 +20,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .config import WXConfig
-from .engine import WXEngine, WXEngineError, _check, load_library, make_c_config, wx_band_msg
+from .engine import NativeHandle, WXEngine, WXEngineError, _check, load_library, make_c_config, wx_band_msg
 
 
 class BandPlan:
@@ -29,20 +29,12 @@ class BandPlan:
     def __init__(self, cfg: WXConfig, nranks: int, precision: str = "bf16"):
         self.lib = load_library()
         self.nranks = nranks
-        self._p = C.c_void_p()
+        self._p = NativeHandle(self.lib.wx_band_plan_destroy)
         cc = make_c_config(cfg, precision)
-        _check(self.lib.wx_band_plan_create(C.byref(cc), nranks, C.byref(self._p)))
+        _check(self.lib.wx_band_plan_create(C.byref(cc), nranks, self._p.out))
         n = C.c_int()
         _check(self.lib.wx_band_plan_num_exchanges(self._p, C.byref(n)))
         self.num_exchanges = n.value
-
-    def __del__(self):
-        try:
-            if getattr(self, "_p", None) and self._p.value:
-                self.lib.wx_band_plan_destroy(self._p)
-                self._p = C.c_void_p()
-        except Exception:
-            pass
 
     def name(self, xid: int) -> str:
         s = C.c_char_p()

@@ -20,7 +20,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .engine import WXEngineError, _check, load_library
+from .engine import NativeHandle, WXEngineError, _check, _f32, _i32, _stream_ptr, load_library
 
 FIELD_TYPE_RANK = {"prognostic": 0, "static": 1, "dynamic_forcing": 2, "diagnostic": 3}
 
@@ -40,24 +40,26 @@ def ordered_keys(sources: Dict[str, Dict]) -> list:
     return out
 
 
+def _level_stats(key, nl, value, neutral):
+    """One statistic of one variable as an [nl] float32 vector: a scalar serves every level, None is `neutral`."""
+    if value is None:
+        return np.full(nl, neutral, np.float32)
+    a = np.asarray(value, np.float32).ravel()
+    if a.size == 1:
+        a = np.repeat(a, nl)
+    if a.size != nl:
+        raise ValueError(f"{key}: {a.size} statistics for {nl} levels")
+    return a
+
+
 def channel_stats(keys, levels, mean: Optional[Dict], std: Optional[Dict]):
     """Per-output-channel (mean, std) from per-variable stats (scalar or per-level vectors); variables without stats
     pass through unchanged (norm.py:84-85) = mean 0, std 1."""
     if mean is None:
         return None, None
-    m, s = [], []
-    for k, nl in zip(keys, levels):
-        name = k.split("/")[-1]
-        if name in mean:
-            mv, sv = np.asarray(mean[name], np.float32).ravel(), np.asarray(std[name], np.float32).ravel()
-            if mv.size == 1:
-                mv, sv = np.repeat(mv, nl), np.repeat(sv, nl)
-            if mv.size != nl:
-                raise ValueError(f"{k}: {mv.size} statistics for {nl} levels")
-        else:
-            mv, sv = np.zeros(nl, np.float32), np.ones(nl, np.float32)
-        m.append(mv)
-        s.append(sv)
+    names = [k.split("/")[-1] for k in keys]
+    m = [_level_stats(k, nl, mean.get(n), 0.0) for k, n, nl in zip(keys, names, levels)]
+    s = [_level_stats(k, nl, std[n] if n in mean else None, 1.0) for k, n, nl in zip(keys, names, levels)]
     return np.concatenate(m).astype(np.float32), np.concatenate(s).astype(np.float32)
 
 
@@ -94,25 +96,13 @@ class DevicePreblock:
         self.channels = sum(self.levels)
         from .transforms import compile_channel_table
         self.transform_table = compile_channel_table(transforms, example_input, self.keys, self.levels) if transforms else None
-        lv = (C.c_int32 * len(self.levels))(*self.levels)
-        fp = C.POINTER(C.c_float)
-        self._p = C.c_void_p()
-        _check(self.lib.wx_pre_create(len(self.levels), lv, self.T, self.H, self.W,
-                                      self.mean.ctypes.data_as(fp) if self.mean is not None else None,
-                                      self.std.ctypes.data_as(fp) if self.std is not None else None, self.device, C.byref(self._p)))
+        self._p = NativeHandle(self.lib.wx_pre_destroy)
+        _check(self.lib.wx_pre_create(len(self.levels), _i32(self.levels), self.T, self.H, self.W, _f32(self.mean), _f32(self.std),
+                                      self.device, self._p.out))
         if self.transform_table is not None:
-            t, ip = self.transform_table, C.POINTER(C.c_int32)
-            _check(self.lib.wx_pre_set_transforms(self._p, t["kind"].ctypes.data_as(ip), t["eps"].ctypes.data_as(fp), t["log_eps"].ctypes.data_as(fp),
-                                                  t["n_rules"].ctypes.data_as(ip), t["rule_op"].ctypes.data_as(ip),
-                                                  t["rule_search"].ctypes.data_as(fp), t["rule_fill"].ctypes.data_as(fp)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_p", None):
-                self.lib.wx_pre_destroy(self._p)
-                self._p = C.c_void_p()
-        except Exception:
-            pass
+            t = self.transform_table
+            _check(self.lib.wx_pre_set_transforms(self._p, _i32(t["kind"]), _f32(t["eps"]), _f32(t["log_eps"]), _i32(t["n_rules"]),
+                                                  _i32(t["rule_op"]), _f32(t["rule_search"]), _f32(t["rule_fill"])))
 
     def __call__(self, batch_input: Dict[str, Dict]):
         """-> x [B, C, T, H, W] float32 on the GPU (normalised + concatenated)."""
@@ -133,6 +123,5 @@ class DevicePreblock:
         x = torch.empty((B, self.channels, self.T, self.H, self.W), dtype=torch.float32, device=ts[0].device)
         ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         with torch.cuda.device(self.device):   # the entry point selects its own device; keep torch's notion of "current" intact
-            _check(self.lib.wx_pre_apply(self._p, ptrs, C.c_void_p(x.data_ptr()), B,
-                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            _check(self.lib.wx_pre_apply(self._p, ptrs, C.c_void_p(x.data_ptr()), B, _stream_ptr(self.device)))
         return x

@@ -17,7 +17,7 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import PREC, WXEngineError, _check, load_library
+from .engine import PREC, NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, load_library
 
 KIND = {"block": 0, "dilated": 1, "shifted": 3}
 
@@ -87,18 +87,9 @@ class WindowAttention:
         ls = None if logit_scale is None else np.ascontiguousarray(logit_scale, dtype=np.float32).ravel()
         if ls is not None and ls.size != heads:
             raise ValueError("logit_scale needs one value per head")
-        self._h = C.c_void_p()
+        self._h = NativeHandle(self.lib.wx_winattn_destroy)
         self.lib.wx_winattn_create.argtypes = [C.POINTER(wx_winattn_desc), fp, C.c_int, fp, C.c_int, C.POINTER(C.c_void_p)]
-        _check(self.lib.wx_winattn_create(C.byref(d), None if b is None else b.ctypes.data_as(fp), 0 if b is None else b.shape[0],
-                                          None if ls is None else ls.ctypes.data_as(fp), self.device, C.byref(self._h)))
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self.lib.wx_winattn_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        _check(self.lib.wx_winattn_create(C.byref(d), _f32(b), 0 if b is None else b.shape[0], _f32(ls), self.device, self._h.out))
 
     def __call__(self, qkv, out=None):
         """qkv [H, W, 3C] (or [H*W, 3C]) on the GPU, bf16 / float32 matching `precision`, q | k | v head-major -> [H, W, C]."""
@@ -106,7 +97,7 @@ class WindowAttention:
         want = torch.bfloat16 if self.precision == "bf16" else torch.float32
         H, W = self.feat
         c = self.heads * self.head_dim
-        if not (isinstance(qkv, torch.Tensor) and qkv.is_cuda and qkv.dtype == want and qkv.is_contiguous()):
+        if not _gpu_tensor(qkv, contiguous=True, dtype=want):
             raise WXEngineError(f"qkv must be a contiguous {want} tensor on the GPU")
         if qkv.numel() != H * W * 3 * c or qkv.shape[-1] != 3 * c:
             raise WXEngineError(f"qkv has shape {tuple(qkv.shape)}, expected [{H}, {W}, {3 * c}]")
@@ -114,11 +105,10 @@ class WindowAttention:
             raise WXEngineError(f"qkv is on cuda:{qkv.device.index}, the operator was created for cuda:{self.device}")
         if out is None:
             out = torch.empty((H, W, c), dtype=want, device=qkv.device)
-        elif not (out.is_cuda and out.dtype == want and out.is_contiguous() and out.numel() == H * W * c):
+        elif not (_gpu_tensor(out, contiguous=True, dtype=want) and out.numel() == H * W * c):
             raise WXEngineError("out must be a contiguous tensor of H*W*C elements in the operator's precision")
         with torch.cuda.device(self.device):
-            _check(self.lib.wx_winattn_apply(self._h, C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            _check(self.lib.wx_winattn_apply(self._h, C.c_void_p(qkv.data_ptr()), C.c_void_p(out.data_ptr()), _stream_ptr(self.device)))
         return out
 
 
@@ -177,22 +167,13 @@ class SwinStage:
         self.device = torch.cuda.current_device() if device is None else int(device)
         d = wx_swin_desc(PREC[precision], self.feat[0], self.feat[1], self.dim, self.heads, self.window[0], self.window[1], self.depth,
                          self.hidden, self.shift[0], self.shift[1], -100.0, 1e-5, 3 if variant == "timm" else 1)
-        self._h = C.c_void_p()
+        self._h = NativeHandle(self.lib.wx_swin_destroy)
         self.lib.wx_swin_create.argtypes = [C.POINTER(wx_swin_desc), C.c_int, C.POINTER(C.c_void_p)]
-        _check(self.lib.wx_swin_create(C.byref(d), self.device, C.byref(self._h)))
+        _check(self.lib.wx_swin_create(C.byref(d), self.device, self._h.out))
         self._loaded = False
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self.lib.wx_swin_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
     def _put(self, block: int, name: str, arr) -> None:
-        a = np.ascontiguousarray(np.asarray(arr, dtype=np.float32))
-        _check(self.lib.wx_swin_load(self._h, block, name.encode(), a.ctypes.data_as(C.POINTER(C.c_float)), a.size))
+        _check(self.lib.wx_swin_load(self._h, block, name.encode(), _f32(arr), np.size(arr)))
 
     def load_state_dict(self, sd, prefix: str = "blocks.") -> None:
         """sd: {key: array-like} with the reference stage's keys; missing keys raise (KeyError names the first one)."""
@@ -225,18 +206,16 @@ class SwinStage:
         H, W = self.feat
         if not self._loaded:
             raise WXEngineError("load_state_dict first")
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == want and x.is_contiguous() and x.numel() == H * W * self.dim
-                and x.shape[-1] == self.dim):
+        if not (_gpu_tensor(x, contiguous=True, dtype=want) and x.numel() == H * W * self.dim and x.shape[-1] == self.dim):
             raise WXEngineError(f"x must be a contiguous {want} tensor [{H}, {W}, {self.dim}] on the GPU")
         if x.device.index != self.device:
             raise WXEngineError(f"x is on cuda:{x.device.index}, the stage was created for cuda:{self.device}")
         if out is None:
             out = torch.empty_like(x)
-        elif not (out.is_cuda and out.dtype == want and out.is_contiguous() and out.shape == x.shape):
+        elif not (_gpu_tensor(out, contiguous=True, dtype=want) and out.shape == x.shape):
             raise WXEngineError("out must match x")
         with torch.cuda.device(self.device):
-            _check(self.lib.wx_swin_apply(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            _check(self.lib.wx_swin_apply(self._h, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), _stream_ptr(self.device)))
         return out
 
 

@@ -25,13 +25,13 @@ No CPU fallback: construction raises without a GPU.
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import WXEngineError, _check, load_library
+from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _i32, _named_tensor_args, _stream_ptr, load_library
+from .preblock import channel_stats
 
 MAX_FILL_RULES = 8          # WX_MAX_FILL_RULES
 MAX_VARIABLES = 64          # kMaxFields
@@ -208,15 +208,7 @@ class _Unxform:
         if not torch.cuda.is_available():
             raise WXEngineError("no GPU visible: the device transforms have no CPU fallback")
         self.lib = load_library()
-        self._handles = {}
-
-    def __del__(self):
-        try:
-            for h in self._handles.values():
-                self.lib.wx_unxform_destroy(h)
-            self._handles = {}
-        except Exception:
-            pass
+        self._handles = {}   # signature -> NativeHandle
 
     def run(self, nested: Dict[str, Dict], plan):
         """plan: [(key, kind, eps, log_eps, mean or None, std or None)]; rebinds nested[source][key] to fresh tensors."""
@@ -228,43 +220,29 @@ class _Unxform:
         ts = [nested[p[0].split("/")[0]][p[0]] for p in plan]
         t0 = ts[0]
         for p, t in zip(plan, ts):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 5):
+            if not _gpu_tensor(t, ndim=5):
                 raise WXEngineError(f"{p[0]} must be a float32 [B, n_levels, n_time, H, W] tensor on the GPU")
             if t.device != t0.device or (t.shape[0], *t.shape[2:]) != (t0.shape[0], *t0.shape[2:]):
                 raise WXEngineError(f"{p[0]}: shape {tuple(t.shape)} on {t.device} does not match {tuple(t0.shape)} on {t0.device}")
-            if not t[0].is_contiguous():
+            if not _gpu_tensor(t, item_contiguous=True):
                 raise WXEngineError(f"{p[0]}: a batch item must be contiguous [n_levels, n_time, H, W] memory")
         B, _, nT, H, W = t0.shape
         dev = t0.device.index
         sig = (tuple((p[0], t.shape[1]) for p, t in zip(plan, ts)), H, W, dev)
         if sig not in self._handles:
-            fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-            lv = np.array([t.shape[1] for t in ts], np.int32)
-            kind = np.array([p[1] for p in plan], np.int32)
-            eps = np.array([p[2] for p in plan], np.float32)
-            leps = np.array([p[3] for p in plan], np.float32)
-            has = np.array([p[4] is not None for p in plan], np.int32)
-            mean, std = [], []
-            for p, nl in zip(plan, lv):
-                for src, dst, neutral in ((p[4], mean, 0.0), (p[5], std, 1.0)):
-                    a = np.full(nl, neutral, np.float32) if src is None else np.asarray(src, np.float32).ravel()
-                    if a.size == 1:
-                        a = np.repeat(a, nl)
-                    if a.size != nl:
-                        raise ValueError(f"{p[0]}: {a.size} statistics for {nl} levels")
-                    dst.append(a)
-            mean, std = np.concatenate(mean).astype(np.float32), np.concatenate(std).astype(np.float32)
-            h = C.c_void_p()
-            _check(self.lib.wx_unxform_create(len(plan), lv.ctypes.data_as(ip), H, W, kind.ctypes.data_as(ip), eps.ctypes.data_as(fp),
-                                              leps.ctypes.data_as(fp), has.ctypes.data_as(ip), mean.ctypes.data_as(fp) if has.any() else None,
-                                              std.ctypes.data_as(fp) if has.any() else None, dev, C.byref(h)))
+            lv = [t.shape[1] for t in ts]
+            has = [p[4] is not None for p in plan]
+            # per-(variable, level) statistics, keyed like the input side's: by the variable's short name
+            named = [(p[0].split("/")[-1], p) for p in plan if p[4] is not None]
+            mean, std = channel_stats([p[0] for p in plan], lv, {n: p[4] for n, p in named}, {n: p[5] for n, p in named})
+            h = NativeHandle(self.lib.wx_unxform_destroy)
+            _check(self.lib.wx_unxform_create(len(plan), _i32(lv), H, W, _i32([p[1] for p in plan]), _f32([p[2] for p in plan]),
+                                              _f32([p[3] for p in plan]), _i32(has), _f32(mean) if any(has) else None,
+                                              _f32(std) if any(has) else None, dev, h.out))
             self._handles[sig] = h
-        outs = [torch.empty(t.shape, dtype=torch.float32, device=t.device) for t in ts]
-        src = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        dst = (C.c_void_p * len(ts))(*[o.data_ptr() for o in outs])
-        bs = (C.c_int64 * len(ts))(*[t.stride(0) if B > 1 else 0 for t in ts])
+        src, bs, _, outs, dst = _named_tensor_args(ts)
         with torch.cuda.device(dev):
-            _check(self.lib.wx_unxform_apply(self._handles[sig], src, bs, dst, B, nT, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _check(self.lib.wx_unxform_apply(self._handles[sig], src, bs, dst, B, nT, _stream_ptr(dev)))
         for p, o in zip(plan, outs):
             nested[p[0].split("/")[0]][p[0]] = o
 

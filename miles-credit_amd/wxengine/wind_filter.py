@@ -24,7 +24,7 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from .conservation import _pred, _set_pred
-from .engine import WXEngineError, _check, load_library
+from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _i32, _named_tensor_args, _stream_ptr, load_library
 
 logger = logging.getLogger(__name__)
 
@@ -112,39 +112,28 @@ class WindArtifactFilter:
         self.kernels = filter_kernels(smooth_sigma, smooth_sigma_zonal, smooth_sigma_meridional, falloff_sigma)
         self._levels = np.array(sorted(self.target_levels), np.int32)
         self._warned = set()
-        self._handles = {}
+        self._handles = {}   # (H, W, device) -> NativeHandle
         import torch
         if not torch.cuda.is_available():
             raise WXEngineError("no GPU visible: the wind artifact filter has no CPU fallback")
         self.lib = load_library()
 
-    def __del__(self):
-        try:
-            for h in self._handles.values():
-                self.lib.wx_wind_destroy(h)
-            self._handles = {}
-        except Exception:
-            pass
-
     def _handle(self, H, W, dev):
         if (H, W, dev) not in self._handles:
-            fp = C.POINTER(C.c_float)
-            k = [np.ascontiguousarray(self.kernels[n], np.float32) for n in ("smooth_lat", "smooth_lon", "falloff_lat", "falloff_lon")]
             args = []
-            for a in k:
-                args += [a.ctypes.data_as(fp), a.size]
-            h = C.c_void_p()
+            for n in ("smooth_lat", "smooth_lon", "falloff_lat", "falloff_lon"):
+                args += [_f32(self.kernels[n]), self.kernels[n].size]
+            h = NativeHandle(self.lib.wx_wind_destroy)
             _check(self.lib.wx_wind_create(H, W, *args, self.dilation_meridional, self.dilation_zonal, self.speed_threshold,
-                                           int(self.preserve_amplitude), dev, C.byref(h)))
+                                           int(self.preserve_amplitude), dev, h.out))
             self._handles[(H, W, dev)] = h
         return self._handles[(H, W, dev)]
 
     @staticmethod
     def _check_tensor(key, t):
-        import torch
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 5 and t.shape[2] == 1):
+        if not (_gpu_tensor(t, ndim=5) and t.shape[2] == 1):
             raise WXEngineError(f"{key} must be a float32 [B, n_levels, 1, H, W] tensor on the GPU")
-        if not t[0].is_contiguous():
+        if not _gpu_tensor(t, item_contiguous=True):
             raise WXEngineError(f"{key}: a batch item must be contiguous [n_levels, 1, H, W] memory")
 
     def __call__(self, batch_dict: dict) -> dict:
@@ -172,20 +161,13 @@ class WindArtifactFilter:
                                out_of_range, t.shape[1], key)
         dev = u.device.index
         h = self._handle(H, W, dev)
-        outs = [torch.empty(t.shape, dtype=torch.float32, device=t.device) for t in ts]
+        src, bs, nl, outs, dst = _named_tensor_args(ts)
         mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=u.device) if self.return_mask else None
-        n = len(ts)
-        src = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-        dst = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-        bs = (C.c_int64 * n)(*[t.stride(0) if B > 1 else 0 for t in ts])
-        nl = (C.c_int32 * n)(*[t.shape[1] for t in ts])
         um, vm = u[:, self.mask_level], v[:, self.mask_level]
         with torch.cuda.device(dev):
             _check(self.lib.wx_wind_apply(h, C.c_void_p(um.data_ptr()), u.stride(0) if B > 1 else 0, C.c_void_p(vm.data_ptr()),
-                                          v.stride(0) if B > 1 else 0, n, src, bs, nl, dst,
-                                          self._levels.ctypes.data_as(C.POINTER(C.c_int32)), int(self._levels.size), B,
-                                          C.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                          v.stride(0) if B > 1 else 0, len(ts), src, bs, nl, dst, _i32(self._levels), int(self._levels.size), B,
+                                          C.c_void_p(mask.data_ptr()) if mask is not None else None, _stream_ptr(dev)))
         for key, o in zip(self.target_vars, outs):
             _set_pred(batch_dict, key, o)
         if self.return_mask:

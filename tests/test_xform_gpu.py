@@ -154,7 +154,9 @@ def test_untouched_variables_and_repeats_are_bit_identical_to_the_plain_kernel(r
 @pytest.mark.parametrize("name", ["al16", "sqrt", "arco"])
 def test_tensors_that_start_on_4_byte_boundaries(runs, name):
     """hw % 4 == 0 does not make a plane 16-byte aligned: fields and y_pred that begin one float into their storage (and, at B = 2, the
-    channel-slice views of such a y_pred) must give the same bits as the aligned ones."""
+    channel-slice views of such a y_pred) must give the same bits as the aligned ones -- on the fused input pass, the plain input
+    pass and the output launch."""
+    from wxengine.preblock import DevicePreblock
     r = runs[name]
 
     def shifted(t):
@@ -165,6 +167,8 @@ def test_tensors_that_start_on_4_byte_boundaries(runs, name):
         return s
     inp = {SRC: {k: shifted(t) for k, t in r["inp"][SRC].items()}}
     assert same_bits(r["pre"](inp), r["x"])
+    plain = DevicePreblock(r["inp"], r["mean"], r["std"])
+    assert plain.transform_table is None and same_bits(plain(inp), plain(r["inp"]))
     y = shifted(r["y"])
     yp = r["fused"](reconstructed(name, y))["y_processed"][SRC]
     for v in out_variables(name):
@@ -226,6 +230,27 @@ def test_abi_refusals_return_a_status_and_a_reason(runs):
         assert status == -1 and reason in lib.wx_last_error().decode(), (reason, status, lib.wx_last_error().decode())
     assert lib.wx_unxform_apply(None, src, bs, dst, 1, 1, None) == -1
     assert lib.wx_unxform_destroy(u) == 0
+
+
+def test_plane_limit_on_the_plain_pass():
+    """One plane per (batch, channel, frame) in the launch's y dimension: 65535 planes run (one field of 65535 levels on a 1 x 1 grid,
+    no statistics: a copy, bit for bit), 65536 are refused with a reason before anything is launched -- as on the fused pass."""
+    from wxengine.engine import load_library
+    lib = load_library()
+    src = torch.randn(65536, generator=torch.Generator().manual_seed(7)).cuda()
+    for n in (65535, 65536):
+        pre = C.c_void_p()
+        assert lib.wx_pre_create(1, (C.c_int32 * 1)(n), 1, 1, 1, None, None, 0, C.byref(pre)) == 0
+        x = torch.full((n,), float("nan"), device="cuda")
+        status = lib.wx_pre_apply(pre, (C.c_void_p * 1)(src.data_ptr()), C.c_void_p(x.data_ptr()), 1, None)
+        torch.cuda.synchronize()
+        if n == 65535:
+            assert status == 0, lib.wx_last_error().decode()
+            assert same_bits(x, src[:n])
+        else:
+            assert status == -1 and "exceeds 65535 planes" in lib.wx_last_error().decode(), (status, lib.wx_last_error().decode())
+            assert bool(torch.isnan(x).all())                                           # nothing was launched
+        assert lib.wx_pre_destroy(pre) == 0
 
 
 def test_host_refusals_on_the_device_objects(runs):
