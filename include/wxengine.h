@@ -448,6 +448,47 @@ int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, 
                   const float* const* src_dev, const int64_t* batch_stride, const int32_t* n_levels, float* const* dst_dev,
                   const int32_t* target_levels, int n_target_levels, int batch, float* mask_out_dev, void* stream);
 
+/* ---- semi-Lagrangian tracer advection on the device (csrc/wx_advect.h) -------------------------------------------------------------
+ * credit/postblock/advect.py in two launches and one scratch volume, whatever the number of tracers; float32 throughout.
+ *   wx_advect_create / wx_advect_destroy <-> _SemiLagrangianAdvectionEngine.__init__ (advect.py:216-275) and the metric terms
+ *                         _grid_coords / advect_nested rebuild at every call (:295-320, :351-376).  a_half / b_half: [n_levels + 1]
+ *                         HOST arrays top -> surface, already sliced by `levels` (:262-264).  row_tables: [6][H] HOST floats the
+ *                         caller computes from the latitudes with the reference's float32 expressions, so that the reference's
+ *                         results are met to rounding: cos(lat); R * max(cos(lat), coslat_floor); torch.gradient(lat_rad) (signed
+ *                         radians per row); and the three coefficients a, b, c of torch.gradient's coordinate-aware difference
+ *                         a f[h - 1] + b f[h] + c f[h + 1] (:116) -- on the first and the last row b holds the one-sided spacing
+ *                         lat[1] - lat[0] / lat[H - 1] - lat[H - 2] and the difference is (f[h + 1] - f[h]) / b, (f[h] - f[h - 1]) / b.
+ *                         The results meet the reference's to rounding ONLY with tables built by these torch expressions
+ *                         (wxengine.advect.metric_tables builds them; the C library's cosf is not torch.cos); the cos(lat) floor
+ *                         is already inside the second table and is not seen here.
+ *                         dlon_rad: deg2rad(lon[1] - lon[0]) (:319).  surface_to_top != 0: the DATA's level axis is flipped
+ *                         (level_order = "surface_to_top", :340-345 and :421-422); an index flip, not a copy.  WX_ERR_INVALID with
+ *                         the reason: H, W or n_levels < 2 (the reference's torch.gradient raises on a single level), n_iterations
+ *                         < 1, a non-finite table entry, time step or floor, a zero spacing, n_levels * H * W >= 2^31.
+ *   wx_advect_apply       <-> _SemiLagrangianAdvectionEngine.advect_nested (:325-423), n_time == 1:
+ *       u_dev, v_dev      batch item b at u_dev + b * u_batch_stride floats: [n_levels][H][W] contiguous, in the data's level order
+ *       sp_dev            surface pressure [Pa], batch item b at sp_dev + b * sp_batch_stride floats: [H][W]
+ *       omega_dev         NULL: omega from mass continuity (omega_from_continuity, :121-156, over horizontal_divergence, :85-118);
+ *                         otherwise the omega_var tensor [Pa / s], laid out like u_dev (:368-369)
+ *       src_dev[t]        tracer t, batch item b at src_dev[t] + b * batch_stride[t] floats: [n_levels][H][W] contiguous, read where
+ *                         it lies -- channel slices of y_pred included -- and never modified; n_tracers <= 32.  A tracer may be
+ *                         u_dev or v_dev itself: the winds are read from the inputs.
+ *       dst_dev[t]        [batch][n_levels][H][W] contiguous, written completely: the trilinear interpolant of the tracer at the
+ *                         departure point of the iterative-midpoint back-trajectory (:392-423).  Must not overlap any input.
+ *     Sampling in index space (:167-203): the column as a floating remainder modulo W with neighbours i, (i + 1) mod W; row and
+ *     level clamped to [0, n - 1], upper neighbour min(i + 1, n - 1).  Zero winds return the input bit for bit; repeated calls give
+ *     identical bits.  The handle holds one scratch volume of batch * n_levels * H * W 16-byte velocity records, grown to the
+ *     largest batch seen: ONE handle serves ONE stream at a time (two calls on the same handle from different streams would share
+ *     the volume).  batch * n_levels * H * W must stay below 2^31; byte offsets are 64-bit. */
+typedef struct wx_advect* wx_advect_handle;
+int wx_advect_create(int H, int W, int n_levels, const float* a_half, const float* b_half, const float* row_tables, float dlon_rad,
+                     float timestep_seconds, int n_iterations, float dp_dlevel_floor, int surface_to_top, int device,
+                     wx_advect_handle* out);
+int wx_advect_destroy(wx_advect_handle a);
+int wx_advect_apply(wx_advect_handle a, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride,
+                    const float* sp_dev, int64_t sp_batch_stride, const float* omega_dev, int64_t omega_batch_stride, int n_tracers,
+                    const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

@@ -326,6 +326,40 @@ int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, 
     });
   });
 }
+// ---- semi-Lagrangian tracer advection (omega, back-trajectory, trilinear gather; csrc/wx_advect.h) -----------------------------
+struct wx_advect {
+  std::unique_ptr<wx::Advect> impl;
+};
+int wx_advect_create(int H, int W, int n_levels, const float* a_half, const float* b_half, const float* row_tables, float dlon_rad,
+                     float timestep_seconds, int n_iterations, float dp_dlevel_floor, int surface_to_top, int device,
+                     wx_advect_handle* out) {
+  return guarded([&] {
+    if (!out || !row_tables) throw wx::ConfigError("wx_advect_create: null argument");
+    const float* rows[6];
+    for (int i = 0; i < 6; ++i) rows[i] = row_tables + (size_t)i * (H > 0 ? H : 0);
+    const std::string why = wx::advect_check_create(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations,
+                                                    dp_dlevel_floor);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_advect_create: " + why);
+    need_device(device, "wx_advect_create");
+    std::unique_ptr<wx_advect> a(new wx_advect);
+    a->impl.reset(new wx::Advect(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations, dp_dlevel_floor,
+                                 surface_to_top != 0, device));
+    *out = a.release();
+  });
+}
+int wx_advect_destroy(wx_advect_handle a) { return guarded([&] { delete a; }); }
+int wx_advect_apply(wx_advect_handle a, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride,
+                    const float* sp_dev, int64_t sp_batch_stride, const float* omega_dev, int64_t omega_batch_stride, int n_tracers,
+                    const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch, void* stream) {
+  return guarded([&] {
+    if (!a || !a->impl) throw wx::ConfigError("wx_advect_apply: null advection handle");
+    if (!u_dev || !v_dev || !sp_dev || !src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_advect_apply: null argument");
+    remap<wx::ConfigError>([&] {
+      a->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, sp_dev, sp_batch_stride, omega_dev, omega_batch_stride, n_tracers,
+                     src_dev, batch_stride, dst_dev, batch, (hipStream_t)stream);
+    });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

@@ -40,6 +40,7 @@
 #include "wx_unxform.h"
 #include "wx_diag.h"
 #include "wx_wind.h"
+#include "wx_advect.h"
 #include "wx_noise.h"
 #include "wx_options.h"
 #include "wx_spec.h"

@@ -5,6 +5,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   model     the registry-facing nn.Module (reference constructor kwargs and state-dict key names)
   rollout   the autoregressive step loop;  latband: one forecast sharded over ranks by latitude
   wind_filter       the wind artifact filter post block (WindArtifactFilter, exported here)
+  advect            semi-Lagrangian tracer advection, post and pre block (SemiLagrangianAdvection, SemiLagrangianAdvectionPre, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
 There is no CPU fallback: without the HIP library or a GPU, construction raises.
 """
@@ -14,4 +15,7 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name == "WindArtifactFilter":
         from .wind_filter import WindArtifactFilter
         return WindArtifactFilter
+    if name in ("SemiLagrangianAdvection", "SemiLagrangianAdvectionPre"):
+        from . import advect
+        return getattr(advect, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect]
 """
 import argparse
 import os
@@ -755,23 +755,10 @@ def diag_golden():
     inputs, coefficients, SHA-256 of every regenerated input, the fp32 outputs and d_ref = the reference's own fp32-against-fp64
     distance per output variable) and diag_<case>_f64.npz (the fp64 outputs as float32 differences from the fp32 ones).
     The generator refuses to write a fixture in which a discrete choice could flip between fp32 and fp64."""
-    import types
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from diag_cases import DIAG_CASES, FIELD_ORDER, KEYS, SRC, case_inputs, distance, input_digest, output_names
     coef = {}
-
-    class _DS:
-        def __enter__(self):
-            return self
-
-        def __exit__(self, *exc):
-            return False
-
-        def __getitem__(self, name):
-            return types.SimpleNamespace(values=coef[name])
-    standin = types.ModuleType("xarray")
-    standin.open_dataset = lambda _path, **_kw: _DS()
-    sys.modules["xarray"] = standin
+    standin = oracle_stub.serve_xarray(coef)
     import credit.postblock.geopotential as RG
     import credit.postblock.mslp as RM
     import credit.postblock.pressure_interp as RP
@@ -905,6 +892,78 @@ def wind_golden():
         assert max(sizes) < 1000000, (name, sizes)
         print(f"[golden] wind {name}: {c['B']} x {c['L']} x {c['H']} x {c['W']}, mask > 0.5 on {100 * float((res32['mask'] > 0.5).mean()):.1f} %, "
               f"files {sizes[0] // 1024} + {sizes[1] // 1024} KB, d_ref " + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()))
+
+
+def advect_golden():
+    """Semi-Lagrangian advection: the reference's SemiLagrangianAdvectionPost (credit/postblock/advect.py) run unmodified on float32
+    and on double tensors, on every case of tests/advect_cases.py.  The class reads its coefficients and coordinates through xarray,
+    which is absent: the stand-in `xarray` module of diag_golden serves the case's arrays, and `get_meta_file_path` is the identity.
+    Written per case: advect_<case>.npz (SHA-256 of every regenerated input, the fp32 tracers, d_ref = the reference's own
+    fp32-against-fp64 distance per tracer AND row region) and advect_<case>_f64.npz (the fp64 tracers as float32 differences from the
+    fp32 ones).  The generator refuses to write a fixture that misses one of the conditions the cases are there for; the departure
+    points it looks at are those of tests/advect_oracle.py in fp64, whose tracers it first checks against the reference's."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import advect_oracle as AO
+    from advect_cases import (ADVECT_CASES, KEYS, REGIONS, SRC, block_args, case_inputs, input_digest, input_names, oracle_args,
+                              region_distance, region_rows)
+    coef = {}
+    standin = oracle_stub.serve_xarray(coef)
+    import credit.postblock.advect as RA
+    RA.xr = standin
+    RA.get_meta_file_path = lambda path: path
+
+    for name, c in ADVECT_CASES.items():
+        inp = case_inputs(name)
+        a = block_args(name)
+        coef.update(a_half=a.pop("model_a_half"), b_half=a.pop("model_b_half"), latitude=a.pop("latitude"), longitude=a.pop("longitude"))
+        blk = RA.SemiLagrangianAdvectionPost(**a)
+        res = {}
+        for dtype in (torch.float32, torch.float64):
+            batch = {"y_processed": {SRC: {KEYS[k]: torch.from_numpy(inp[k]).to(dtype) for k in inp}}}
+            with torch.no_grad():
+                y = blk(batch)["y_processed"][SRC]
+            res[dtype] = {t: y[KEYS[t]].contiguous().numpy() for t in c["tracers"]}
+            assert all(v.dtype == (np.float32 if dtype == torch.float32 else np.float64) and v.shape == inp[t].shape
+                       for t, v in res[dtype].items()), name
+        rows = region_rows(c["H"])
+        fix, f64, d_ref = {}, {}, {}
+        for k in input_names(name):
+            fix[f"sha256:{k}"] = np.array(input_digest(inp[k]))
+        for t in c["tracers"]:
+            a32, a64 = res[torch.float32][t], res[torch.float64][t]
+            assert np.isfinite(a32).all() and np.isfinite(a64).all(), (name, t)
+            fix[f"f32:{t}"] = a32
+            f64[f"d64:{t}"] = (a64 - a32.astype(np.float64)).astype(np.float32)
+            for r in REGIONS:
+                d_ref[(t, r)] = region_distance(a32, a64, rows[r])
+                fix[f"d_ref:{t}:{r}"] = np.float64(d_ref[(t, r)])
+        # ---- what the cases are there for (fp64)
+        oa = oracle_args(name)
+        o64, dep = AO.advect({KEYS[k]: torch.from_numpy(inp[k]) for k in inp}, dtype=torch.float64, want_departure=True, **oa)
+        for t in c["tracers"]:
+            assert np.abs(o64[KEYS[t]].numpy() - res[torch.float64][t]).max() <= 1e-9 * np.abs(res[torch.float64][t]).max(), (name, t)
+        col, row, lev = (x.numpy() for x in dep)       # [B, L, H, W], levels top -> surface
+        L, H, W = c["L"], c["H"], c["W"]
+        ri = rows["interior"]
+        disp = (np.abs(col - np.arange(W).reshape(1, 1, 1, W))[:, :, ri].max(), np.abs(row - np.arange(H).reshape(1, 1, H, 1))[:, :, ri].max(),
+                np.abs(lev - np.arange(L).reshape(1, L, 1, 1))[:, :, ri].max())
+        wraps = bool(((col[:, :, ri] < 0) | (col[:, :, ri] >= W)).any())
+        clamped = (bool(((row < 0) | (row > H - 1)).any()), bool(((lev < 0) | (lev > L - 1)).any()))
+        moved = {t: float(np.abs(res[torch.float64][t] - inp[t]).max() / np.abs(inp[t]).max()) for t in c["tracers"]}
+        np.savez_compressed(os.path.join(GOLD, f"advect_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"advect_{name}_f64.npz"), **f64)
+        sizes = [os.path.getsize(os.path.join(GOLD, f"advect_{name}{s}.npz")) for s in ("", "_f64")]
+        print(f"[golden] advect {name}: {c['B']} x {L} x {H} x {W}, files {sizes[0] // 1024} + {sizes[1] // 1024} KB; interior displacement "
+              f"{disp[0]:.2f} columns, {disp[1]:.2f} rows, {disp[2]:.2f} levels; wrap {wraps}; clamped rows {clamped[0]}, levels {clamped[1]}; moved "
+              + ", ".join(f"{t} {m:.2f}" for t, m in moved.items()) + "; d_ref "
+              + ", ".join(f"{t} {r} {d:.2e}" for (t, r), d in d_ref.items()), flush=True)
+        assert all(d_ref[(t, "interior")] <= 1e-5 for t in c["tracers"]), name
+        assert name == "polewind" or all(d_ref[(t, "edge")] <= 2e-4 for t in c["tracers"]), name
+        assert wraps or name == "omega", name
+        assert disp[0] >= 3.0 and disp[1] >= 0.5 and disp[2] >= 0.3, (name, disp)
+        assert all(clamped), (name, clamped)
+        assert all(m >= 0.1 for m in moved.values()), (name, moved)
+        assert max(sizes) < 133000, (name, sizes)
 
 
 def xform_golden():
@@ -1269,6 +1328,8 @@ def main():
             diag_golden()
         elif item == "wind":        # wind artifact filter: jet mask, masked Gaussian blend
             wind_golden()
+        elif item == "advect":      # semi-Lagrangian tracer advection: omega, back-trajectory, trilinear gather
+            advect_golden()
         elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
             xform_golden()
         elif item == "rec":

@@ -74,3 +74,22 @@ def install():
         sys.meta_path.insert(0, _HollowFinder())
     if REFERENCE_ROOT not in sys.path:
         sys.path.insert(0, REFERENCE_ROOT)
+
+
+def serve_xarray(arrays):
+    """Put a stand-in `xarray` module into sys.modules whose `open_dataset(path)` serves `arrays[name]` as `ds[name].values`, whatever the
+    path -- for the reference classes that read coefficients and coordinates from NetCDF files.  `arrays` is read at access time, so the
+    caller may update it between cases.  Returns the module (assign it to `<reference module>.xr` where that was imported earlier)."""
+    class _Dataset:
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+        def __getitem__(self, name):
+            return types.SimpleNamespace(values=arrays[name])
+    standin = types.ModuleType("xarray")
+    standin.open_dataset = lambda _path, **_kw: _Dataset()
+    sys.modules["xarray"] = standin
+    return standin
