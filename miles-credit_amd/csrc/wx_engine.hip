@@ -276,21 +276,24 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     acts_ready = true;
   }
 
-  T* stream_ptr(int s) {
-    if (band_on) {   // lat-band mode: the long layout has its own buffer; the short one sits behind 1 halo row of the concat buffer
-      if (b_long[s]) return blong[s];
-      return s < 3 ? bcat[s] + (int64_t)sw[s] * 2 * cfg.dim[s] + cfg.dim[s] : bx3;
-    }
-    return s < 3 ? cat[s] + cfg.dim[s] : x3;
+  // one stage's token stream as a sub-block sees it: the whole map, or in lat-band mode the rows this rank holds in one layout
+  struct StageView { int s; T* x; int64_t ld; int h, w; int attn_kind = -1; };   // attn_kind >= 0 replaces AttnL::kind
+  StageView whole(int s) const { return {s, s < 3 ? cat[s] + cfg.dim[s] : x3, s < 3 ? 2 * cfg.dim[s] : cfg.dim[s], sh[s], sw[s]}; }
+  // lat-band mode: the long layout has its own buffer; the short one sits behind 1 halo row of the concat buffer
+  StageView band_view(int s, bool is_long) const {
+    if (is_long) return {s, blong[s], cfg.dim[s], bplan.g.rows_long(s, b_rank), sw[s], 2};
+    StageView v = whole(s);
+    v.x = s < 3 ? bcat[s] + (int64_t)sw[s] * 2 * cfg.dim[s] + cfg.dim[s] : bx3;
+    v.h = bplan.g.rows_short(s, b_rank);
+    return v;
   }
-  int64_t stream_ld(int s) { return (s < 3 && !(band_on && b_long[s])) ? 2 * cfg.dim[s] : cfg.dim[s]; }
 
   // ------------------------------------------------------------------ step glue state
   void set_denorm(const float* mean, const float* stdv, int n) override {
     if (n != C_out) throw ShapeError("wx_set_denorm: n must equal the number of output channels");
     WX_HIP(hipSetDevice(device));
     roll_invalidate();
-    alloc_small();
+    need_finalized();
     WX_HIP(hipMemcpy(d_mean, mean, n * sizeof(float), hipMemcpyHostToDevice));
     WX_HIP(hipMemcpy(d_std, stdv, n * sizeof(float), hipMemcpyHostToDevice));
     have_denorm = true;
@@ -298,7 +301,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   void set_tracer(const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) override {
     WX_HIP(hipSetDevice(device));
     roll_invalidate();
-    alloc_small();
+    need_finalized();
     if (n == 0) { have_tracer = false; return; }
     std::vector<float> lo(C_out, -3.4e38f), hi(C_out, 3.4e38f);
     for (int i = 0; i < n; ++i) {
@@ -374,7 +377,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         WX_HIP(hipMemcpyAsync(x_next + g.x0 * plane, frc + g.src0 * plane, g.n * plane * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
   }
-  void alloc_small() {
+  void need_finalized() const {
     if (!acts_ready) throw StateError("call wx_finalize_weights before configuring the step glue");
   }
 
@@ -473,12 +476,13 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     }
     tail(y, nullptr, nullptr);
     timed("post_block", 0.0, 0.0, [&] { post->apply(x_item, y, cur_stream); });
-    if (y_phys || x_next) {
-      const int64_t plane = (int64_t)Ho * Wo;
-      hipLaunchKernelGGL(finish_kernel, dim3(2048), dim3(256), 0, cur_stream, y, plane, C_out, have_denorm ? d_mean : nullptr,
-                         have_denorm ? d_std : nullptr, y_phys, x_next, n_prog < 0 ? 0 : n_prog, d_xmap);
-      WX_HIP(hipGetLastError());
-    }
+    if (y_phys || x_next) launch_finish(y, (int64_t)Ho * Wo, y_phys, x_next);
+  }
+  // after the post block: y_phys and the prognostic channels of x_next from the corrected y (planes of `plane` floats)
+  void launch_finish(float* y, int64_t plane, float* y_phys, float* x_next) {
+    hipLaunchKernelGGL(finish_kernel, dim3(2048), dim3(256), 0, cur_stream, y, plane, C_out, have_denorm ? d_mean : nullptr,
+                       have_denorm ? d_std : nullptr, y_phys, x_next, n_prog < 0 ? 0 : n_prog, d_xmap);
+    WX_HIP(hipGetLastError());
   }
   bool dbg_on = false;
   struct DbgT { int64_t c, h, w; std::vector<float> data; };
@@ -781,25 +785,26 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // qkv_ready: the previous fused feed-forward kernel already wrote this attention's q|k|v into `scratch`
   // the whole attention sub-block in one launch?  (bf16 engine, C = 128 / 256, unsharded maps; q|k|v and the attention output never
   // exist in memory on this path: a debug run captures the sub-block's output only)
-  bool attn_block_ok(const AttnL& a, int s) const {
-    if (sizeof(T) != 2 || !opt.attn_block || band_on || attn_kind_override >= 0 || a.bias_tb < 0 || cfg.dim_head != 32) return false;
+  bool attn_block_ok(const AttnL& a, const StageView& v) const {
+    const int s = v.s;
+    if (sizeof(T) != 2 || !opt.attn_block || band_on || a.bias_tb < 0 || cfg.dim_head != 32) return false;
     if (opt.attn_block == 2) {
-      const bool big_s0 = cfg.dim[s] == 128 && attn_nkf(a.wsz) == 7 && (int64_t)(sh[s] / a.wsz) * (sw[s] / a.wsz) >= 2048;
+      const bool big_s0 = cfg.dim[s] == 128 && attn_nkf(a.wsz) == 7 && (int64_t)(v.h / a.wsz) * (v.w / a.wsz) >= 2048;
       const bool small_map = small_map_tokens(s);   // launch-bound maps (1-degree model): one launch instead of three
       if (!big_s0 && !small_map) return false;
     }
     // 2 x 2 windows: one 16-token fragment per window loses even on launch-bound maps (37 us against 26 for the three launches); four
     // windows per fragment (AttnBlockParams::pack) win there
-    if (a.wsz == 2 && !(opt.attn_pack2 && small_map_tokens(s) && ((sh[s] / 2) * (sw[s] / 2)) % 4 == 0)) return false;
+    if (a.wsz == 2 && !(opt.attn_pack2 && small_map_tokens(s) && ((v.h / 2) * (v.w / 2)) % 4 == 0)) return false;
     return a.wsz > 1 && attn_block_supported(cfg.dim[s], a.wsz, true) &&
            (a.kind == 0 || a.kind == 1) && a.qkv.cin == cfg.dim[s] && a.out.cin == cfg.dim[s];
   }
-  void attention(const AttnL& a, int s, const std::string& dbg_name, bool defer_out = false, bool qkv_ready = false) {
-    const int c = cfg.dim[s], h = sh[s], w = sw[s], m = h * w;
-    const int64_t ld = stream_ld(s);
-    T* x = stream_ptr(s);
+  void attention(const AttnL& a, const StageView& v, const std::string& dbg_name, bool defer_out = false, bool qkv_ready = false) {
+    const int c = cfg.dim[v.s], h = v.h, w = v.w, m = h * w;
+    const int64_t ld = v.ld;
+    T* x = v.x;
     if constexpr (sizeof(T) == 2) {
-      if (attn_block_ok(a, s)) {
+      if (attn_block_ok(a, v)) {
         if (defer_out || qkv_ready) throw StateError("attention block: the fused feed-forward variants must be off for this layer");
         AttnBlockParams bp;
         bp.x = reinterpret_cast<bf16_t*>(x); bp.ld = ld;
@@ -824,7 +829,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
       // k-blocked (see KBlk); outputs bitwise the row-major chain's
       if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_on && !band_on && cfg.dim_head == 32 &&
-          !qkv_ready && !defer_out && attn_kind_override < 0 && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
+          !qkv_ready && !defer_out && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
           m >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
         blk = KBlk::attn;
         ++n_attn_blk;
@@ -833,7 +838,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       AttnParams p;
       p.trace = nullptr;
       p.qkv = scratch; p.ld_qkv = 3 * c; p.out = attn_o; p.ld_out = c; p.bias = f_dev + a.bias_tab; p.tb = a.bias_tb >= 0 ? f_dev + a.bias_tb : nullptr;
-      p.H = h; p.W = w; p.C = c; p.heads = c / cfg.dim_head; p.wsz = a.wsz; p.kind = attn_kind_override >= 0 ? attn_kind_override : a.kind;
+      p.H = h; p.W = w; p.C = c; p.heads = c / cfg.dim_head; p.wsz = a.wsz; p.kind = v.attn_kind >= 0 ? v.attn_kind : a.kind;
       p.scale = (float)(1.0 / std::sqrt((double)cfg.dim_head));   // fp32 engine only: the bf16 engine's q already carries scale * log2(e)
       p.pack = attn_pack(a.wsz);
       p.mma3 = split_mma ? 1 : 0;
@@ -854,15 +859,14 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   }
   // The fused feed-forward kernel gives every workgroup 128 (C = 128) or 64 (C = 256) pixels: below one workgroup per CU the
   // plain GEMM chain fills the chip better (1-degree model: 45 and 22 workgroups; 507 -> 527 steps/s without the fusion)
-  bool ff_big_enough() const {
-    if (cur_stage < 0 || cur_stage > 3) return true;
-    const int64_t m = (int64_t)sh[cur_stage] * sw[cur_stage];
+  bool ff_big_enough(const StageView& v) const {
+    const int64_t m = (int64_t)v.h * v.w;
     // C = 128 on a launch-bound map (1-degree grid stage 1: 45 workgroups): one launch instead of two wins from 40 workgroups on
     // (724 -> 729 steps/s); C = 256 at 23 workgroups loses (710)
-    if (cfg.dim[cur_stage] == 128 || cfg.dim[cur_stage] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
+    if (cfg.dim[v.s] == 128 || cfg.dim[v.s] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
     return cdiv(m, 64) >= opt.ff_min_wgs;
   }
-  bool ff_takes_out(const FFL& f) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_on && ff_big_enough() && cfg.dim_head == 32; }
+  bool ff_takes_out(const FFL& f, const StageView& v) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_on && ff_big_enough(v) && cfg.dim_head == 32; }
   // split-bf16 precision: the one-launch FeedForward (wx_ff_split.h) of this layer ...
   bool ff_split_fused_ok(const FFL& f, int c) const {
     return sizeof(T) == 4 && split_mma && opt.ff_split_fused && !opt.dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || opt.ff_split_256) && f.w1.cin == c &&
@@ -870,30 +874,29 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   }
   // ... and whether it also applies the attention's out-projection + residual in front (its PRE form: to_out's launch, the write of x1 by
   // one kernel and its read by the next are gone)
-  bool ff_split_takes_out(const FFL& f, const AttnL& a) const {
-    if (cur_stage < 0 || cur_stage > 3) return false;
-    const int c = cfg.dim[cur_stage];
+  bool ff_split_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
+    const int c = cfg.dim[v.s];
     return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_on && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
   }
-  bool ff_takes_out(const FFL& f, const AttnL& a) const {
-    if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a);
-    return ff_takes_out(f) && !attn_block_ok(a, cur_stage);
+  bool ff_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
+    if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a, v);
+    return ff_takes_out(f, v) && !attn_block_ok(a, v);
   }
-  bool ff_makes_qkv(const FFL& f) const {
+  bool ff_makes_qkv(const FFL& f, const StageView& v) const {
     if constexpr (sizeof(T) == 4) {   // split-bf16 precision: the to_qkv tail of the one-launch FeedForward (its POST form; rides on the PRE form)
-      if (cur_stage < 0 || cur_stage > 3 || !f.next) return false;
-      const int c = cfg.dim[cur_stage];
+      if (!f.next) return false;
+      const int c = cfg.dim[v.s];
       const ConvW& q = f.next->qkv;
       return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_on && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
              q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
     }
-    return ff_takes_out(f) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, cur_stage));
+    return ff_takes_out(f, v) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, v));
   }
-  bool ff_split_ok(const FFL& f, int s, const AttnL* pre) const {
-    const int c = cfg.dim[s];
-    const int64_t m = (int64_t)sh[s] * sw[s];
+  bool ff_split_ok(const FFL& f, const StageView& v, const AttnL* pre) const {
+    const int c = cfg.dim[v.s];
+    const int64_t m = (int64_t)v.h * v.w;
     return sizeof(T) == 2 && opt.ff_split_max >= 2 && !pre && f.pack >= 0 && opt.fuse_ff && opt.fuse_ln && !band_on && !opt.dbg_flags &&
-           ff_fused_supported(c, 4 * c) && small_map_tokens(s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= opt.ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
+           ff_fused_supported(c, 4 * c) && small_map_tokens(v.s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= opt.ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
   }
   // the form of a FeedForward (feedforward() below):
   //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
@@ -902,20 +905,20 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   //   split_bf16  split-bf16 precision, C = 128 / 256: both layers in one launch (wx_ff_split.h), plain / PRE / POST
   //   chain       ff1 + ff2 on gemm()
   enum class FFForm { fused, split, split_bf16, chain };
-  FFForm ff_form(const FFL& f, int s, const AttnL* pre) const {
+  FFForm ff_form(const FFL& f, const StageView& v, const AttnL* pre) const {
     if (sizeof(T) == 2) {
-      if (ff_split_ok(f, s, pre)) return FFForm::split;
-      if (f.pack >= 0 && opt.fuse_ff && ff_big_enough()) return FFForm::fused;
-    } else if (ff_split_fused_ok(f, cfg.dim[s])) {
+      if (ff_split_ok(f, v, pre)) return FFForm::split;
+      if (f.pack >= 0 && opt.fuse_ff && ff_big_enough(v)) return FFForm::fused;
+    } else if (ff_split_fused_ok(f, cfg.dim[v.s])) {
       return FFForm::split_bf16;
     }
     return FFForm::chain;
   }
-  void feedforward(const FFL& f, int s, const std::string& dbg_name, const AttnL* pre = nullptr) {
-    const int c = cfg.dim[s], h = sh[s], w = sw[s], m = h * w;
-    const int64_t ld = stream_ld(s);
-    T* x = stream_ptr(s);
-    const FFForm form = ff_form(f, s, pre);
+  void feedforward(const FFL& f, const StageView& v, const std::string& dbg_name, const AttnL* pre = nullptr) {
+    const int c = cfg.dim[v.s], h = v.h, w = v.w, m = h * w;
+    const int64_t ld = v.ld;
+    T* x = v.x;
+    const FFForm form = ff_form(f, v, pre);
     if (pre && form != FFForm::fused && form != FFForm::split_bf16) throw StateError("feedforward: out-projection deferred to a layer that cannot take it");
     if constexpr (sizeof(T) == 2) {
       auto block_params = [&](int64_t pack) {   // the one-launch block's operands
@@ -946,7 +949,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         stat_tiles_ready = conv_gemm_finish_slots(c);
       };
       if (form == FFForm::fused) {
-        const bool post = pre && ff_makes_qkv(f);
+        const bool post = pre && ff_makes_qkv(f, v);
         FFParams fp = block_params(post ? f.pack_pp : pre ? f.pack_pre : f.pack);
         fp.qkv = post ? reinterpret_cast<bf16_t*>(scratch) : nullptr; fp.ld_qkv = 3 * c;
         fp.csq = post ? f_dev + f.next->qkv.colsum : nullptr; fp.bq = post ? f_dev + f.next->qkv.bias : nullptr;
@@ -980,7 +983,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           ++n_split_gemms;
           ++n_ff_split_pre;
         }
-        const bool post = pre && ff_makes_qkv(f);
+        const bool post = pre && ff_makes_qkv(f, v);
         if (post) {
           q.qkv = reinterpret_cast<float*>(scratch); q.ld_qkv = 3 * c;
           q.wqs = reinterpret_cast<const float*>(ws_dev + f.next->qkv.wt); q.bq = f_dev + f.next->qkv.bias;
@@ -1073,17 +1076,18 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // a2: the CrossEmbed of stage s.  `in` = stage-0: packed input buffer of Hb rows (xin layout); later stages: rows of the
   // previous stream, in_h of them, whose first row is row `in_row0` relative to stride*first-output-row (0 for the whole map,
   // -emb_lo in lat-band mode where the conv halo is materialised).
-  void cross_embed(int s, const T* in, const T* in_planar, int in_h, int in_row0, int64_t in_ld_s) {
+  void cross_embed(const StageView& v, const T* in, const T* in_planar, int in_h, int in_row0, int64_t in_ld_s) {
+    const int s = v.s;
     const StageL& st = stages[s];
-    T* x = stream_ptr(s);
-    const int64_t ld = stream_ld(s);
-    if (sh[s] <= 0) return;
+    T* x = v.x;
+    const int64_t ld = v.ld;
+    if (v.h <= 0) return;
     int choff = 0;
     if (s >= 1 && st.merged.wt >= 0 && opt.embed_merge && !band_on) {
       const int k = st.embed_k.back(), stv = cfg.embed_strides[s], pd = (k - stv) / 2;
       // ... which also leaves the LayerNorm partials of its rows for the stage's first sub-block
       stat_tiles_ready = gemm("gemm_embed", st.merged, {.in = in, .in_h = in_h, .in_w = sw[s - 1], .in_ld = in_ld_s, .out = x, .out_ld = ld, .stride = stv,
-                                                        .pad_y = pd + in_row0, .pad_x = pd, .out_h = sh[s], .out_w = sw[s], .want_stats = true}).stat_slots;
+                                                        .pad_y = pd + in_row0, .pad_x = pd, .out_h = v.h, .out_w = v.w, .want_stats = true}).stat_slots;
       return;
     }
     // stages 1-3: every branch's epilogue (or split-K finish) leaves the LayerNorm partials of ITS channel range in the shared row of
@@ -1092,7 +1096,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     bool share = s >= 1 && opt.fuse_ln && opt.use_dma && !band_on && !opt.dbg_flags && opt.stat_share && st.embed.size() <= 8;
     for (size_t b = 0; share && b < st.embed.size(); ++b) {
       const ConvW& w = st.embed[b];
-      slots[b] = plain_split_ways(w, (int64_t)sh[s] * sw[s]) > 1 ? conv_gemm_finish_slots(w.n) : conv_gemm_n_tiles(w.n);
+      slots[b] = plain_split_ways(w, (int64_t)v.h * v.w) > 1 ? conv_gemm_finish_slots(w.n) : conv_gemm_n_tiles(w.n);
       total_slots += slots[b];
     }
     share = share && total_slots <= 8;
@@ -1107,7 +1111,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         EmbedPatchParams ep;
         std::memset(&ep, 0, sizeof(ep));
         ep.xin = in; ep.xin_planar = in_planar; ep.Hb = in_h; ep.Wb = Wp + 2 * halo; ep.cpad = cpad0; ep.org = halo - 15;
-        ep.out_ld = ld; ep.out_h = sh[0]; ep.out_w = sw[0]; ep.dbg = opt.dbg_flags;
+        ep.out_ld = ld; ep.out_h = v.h; ep.out_w = v.w; ep.dbg = opt.dbg_flags;
         ep.slot_tab = f_dev + st.patch_tab; ep.bias64 = f_dev + st.patch_bias64; ep.out_row = x;
         double fl = 0.0;
         int off = 0;
@@ -1115,21 +1119,21 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           const PatchW& pw = st.patch[j];
           const int kj = st.embed_k[j];
           if (pw.wt >= 0) {
-            fl += 2.0 * sh[0] * sw[0] * pw.n * kj * kj * C_in;
+            fl += 2.0 * v.h * v.w * pw.n * kj * kj * C_in;
             if (kj == 32) ep.wt32 = wt_dev + pw.wt;
             if (kj == 16) ep.wt16 = wt_dev + pw.wt;
             if (kj == 8) ep.wt8 = wt_dev + pw.wt;
           } else if (kj == 4 && st.ride4) {
-            fl += 2.0 * sh[0] * sw[0] * st.embed[j].n * kj * kj * C_in;
+            fl += 2.0 * v.h * v.w * st.embed[j].n * kj * kj * C_in;
           }
           off += st.embed[j].n;
         }
         // small maps (1-degree grid, lat-band ranks): the serial walk over the channel chunks bounds the launch -> split it four
         // ways over blockIdx.y, fp32 partial sums, fixed-order finish kernel
         const int chunks0 = cpad0 / (16 / (int)sizeof(T));
-        if (opt.embed_split && embed_patch_small_map(sh[0], sw[0], opt.dbg_flags) && chunks0 >= 8) {
+        if (opt.embed_split && embed_patch_small_map(v.h, v.w, opt.dbg_flags) && chunks0 >= 8) {
           const int n_split = opt.embed_split_ways;
-          const size_t need = (size_t)n_split * sh[0] * sw[0] * 64 * sizeof(float);
+          const size_t need = (size_t)n_split * v.h * v.w * 64 * sizeof(float);
           if (need > embed_partial_bytes) {
             embed_partial = (float*)mem.alloc(need);   // grows at most a few times (batch / band geometry); the arena frees the older ones at destroy
             embed_partial_bytes = need;
@@ -1138,9 +1142,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           ep.chunk_per = cdiv(chunks0, n_split);
         } else if (opt.embed_tail_split && !opt.dbg_flags) {
           // big maps: the partly filled last round of tiles (0.25 degrees: 125 of 625) runs as ONE round of half-chunk workgroups
-          const int tail = embed_patch_tail_rows(sh[0], sw[0], chunks0);
+          const int tail = embed_patch_tail_rows(v.h, v.w, chunks0);
           if (tail > 0) {
-            const size_t need = (size_t)2 * tail * sw[0] * 64 * sizeof(float);
+            const size_t need = (size_t)2 * tail * v.w * 64 * sizeof(float);
             if (need > embed_tail_bytes) { embed_tail = (float*)mem.alloc(need); embed_tail_bytes = need; }
             ep.tail_partial = embed_tail;
           }
@@ -1159,7 +1163,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           if (ep.chunk_per) ep.chunk_per = cdiv(3 * cpad0 / 8, opt.embed_split_ways);
           ++n_split_gemms;
         }
-        timed("embed_patch", fl, (double)(in_h * Wp) * cpad0 * sizeof(T) + (double)sh[0] * sw[0] * 64 * sizeof(T), [&] {
+        timed("embed_patch", fl, (double)(in_h * Wp) * cpad0 * sizeof(T) + (double)v.h * v.w * 64 * sizeof(T), [&] {
           if constexpr (sizeof(T) == 4) {
             if (split_patch) { launch_embed_patch<bf16_t, float>(ep, zero_page, cur_stream); return; }
           }
@@ -1168,10 +1172,10 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       } else if (s == 0) {
         // the branch that does not ride in the patch kernel (k = 4 of the 0.25-degree model: 64 channels, its own implicit GEMM)
         gemm("gemm_embed", st.embed[b], {.in = in, .in_h = in_h, .in_w = Wp + 2 * halo, .in_ld = cpad0, .out = x + choff, .out_ld = ld, .stride = stv,
-                                         .pad_y = pd - halo, .pad_x = pd - halo, .out_h = sh[0], .out_w = sw[0]});
+                                         .pad_y = pd - halo, .pad_x = pd - halo, .out_h = v.h, .out_w = v.w});
       } else {
         const int made = gemm("gemm_embed", st.embed[b], {.in = in, .in_h = in_h, .in_w = sw[s - 1], .in_ld = in_ld_s, .out = x + choff, .out_ld = ld,
-                                                          .stride = stv, .pad_y = pd + in_row0, .pad_x = pd, .out_h = sh[s], .out_w = sw[s], .want_stats = share,
+                                                          .stride = stv, .pad_y = pd + in_row0, .pad_x = pd, .out_h = v.h, .out_w = v.w, .want_stats = share,
                                                           .stat_stride = share ? total_slots : 0, .stat_slot0 = share ? slot_at : 0}).stat_slots;
         if (share && made && made != slots[b]) throw StateError("cross_embed: LayerNorm partial slots of a branch differ from the prediction");
         all_made = all_made && made > 0;
@@ -1184,27 +1188,28 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // a4-a7: the transformer blocks of stage s on the rows the stream currently holds
   void stage_blocks(int s) {
     const StageL& st = stages[s];
+    const StageView v = whole(s);
     const std::string sp = "layers." + std::to_string(s);
     bool qkv_made = false;  // the previous fused kernel already produced this attention's q|k|v
     for (size_t d = 0; d < st.blocks.size(); ++d) {
       const std::string bp = sp + ".1.layers." + std::to_string(d);
       const BlockL& bl = st.blocks[d];
-      const bool ds = ff_takes_out(bl.sf, bl.sa), dl = ff_takes_out(bl.lf, bl.la);
-      attention(bl.sa, s, bp + ".0", ds, qkv_made);
-      feedforward(bl.sf, s, bp + ".1", ds ? &bl.sa : nullptr);
-      attention(bl.la, s, bp + ".2", dl, ds && ff_makes_qkv(bl.sf));
-      feedforward(bl.lf, s, bp + ".3", dl ? &bl.la : nullptr);
-      qkv_made = dl && ff_makes_qkv(bl.lf);
+      const bool ds = ff_takes_out(bl.sf, bl.sa, v), dl = ff_takes_out(bl.lf, bl.la, v);
+      attention(bl.sa, v, bp + ".0", ds, qkv_made);
+      feedforward(bl.sf, v, bp + ".1", ds ? &bl.sa : nullptr);
+      attention(bl.la, v, bp + ".2", dl, ds && ff_makes_qkv(bl.sf, v));
+      feedforward(bl.lf, v, bp + ".3", dl ? &bl.la : nullptr);
+      qkv_made = dl && ff_makes_qkv(bl.lf, v);
     }
   }
-  void block_half(int s, int d, bool long_half) {   // lat-band mode: one (attention, feed-forward) pair
-    if (sh[s] <= 0) return;
-    const BlockL& bl = stages[s].blocks[d];
+  void block_half(const StageView& v, int d, bool long_half) {   // lat-band mode: one (attention, feed-forward) pair
+    if (v.h <= 0) return;
+    const BlockL& bl = stages[v.s].blocks[d];
     const AttnL& a = long_half ? bl.la : bl.sa;
     const FFL& f = long_half ? bl.lf : bl.sf;
-    const bool df = ff_takes_out(f, a);
-    attention(a, s, "", df, false);
-    feedforward(f, s, "", df ? &a : nullptr);
+    const bool df = ff_takes_out(f, a, v);
+    attention(a, v, "", df, false);
+    feedforward(f, v, "", df ? &a : nullptr);
   }
   // ------------------------------------------------------------------ ensemble noise (wx_noise.h)
   // tape entries of slot l in the reference's draw order: per active layer (latent, pixel), or one latent first when correlated
@@ -1297,15 +1302,16 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     for (int s = 0; s < 4; ++s) {
       cur_stage = s;
       stat_tiles_ready = 0;  // the CrossEmbed output has no partials yet
-      if (s == 0) cross_embed(0, xin, xin_planar, Hp + 2 * halo, 0, 0);
-      else cross_embed(s, stream_ptr(s - 1), nullptr, sh[s - 1], 0, stream_ld(s - 1));
+      const StageView v = whole(s);
+      if (s == 0) cross_embed(v, xin, xin_planar, Hp + 2 * halo, 0, 0);
+      else cross_embed(v, whole(s - 1).x, nullptr, sh[s - 1], 0, whole(s - 1).ld);
       const std::string sp = "layers." + std::to_string(s);
-      capture(sp + ".0", stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
+      capture(sp + ".0", v.x, v.h, v.w, cfg.dim[s], v.ld, v.w);
       stage_blocks(s);
-      capture(sp + ".1", stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
+      capture(sp + ".1", v.x, v.h, v.w, cfg.dim[s], v.ld, v.w);
       if (s < 3 && noise_slot_on(s)) {   // in place: the noisy map is both the skip and the next stage's input
-        noise_inject(s, stream_ptr(s), stream_ld(s), sh[s], sw[s]);
-        capture(noise_prefix(s), stream_ptr(s), sh[s], sw[s], cfg.dim[s], stream_ld(s), sw[s]);
+        noise_inject(s, v.x, v.ld, v.h, v.w);
+        capture(noise_prefix(s), v.x, v.h, v.w, cfg.dim[s], v.ld, v.w);
       }
     }
     // decoder
@@ -1356,16 +1362,18 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     }
     capture("up_block4", dec, Hd, Wd, C_out, ld_dec, Wd);
   }
-  void tail(float* y, float* y_phys, float* x_next) {
+  void tail(float* y, float* y_phys, float* x_next) { launch_tail(dec, 0, 0, Ho, y, y_phys, x_next); }
+  // output rows [oy0, oy0 + rows) from the decoder buffer `dec_buf`, whose first row is decoder row `dec_row0`
+  void launch_tail(const T* dec_buf, int dec_row0, int oy0, int rows, float* y, float* y_phys, float* x_next) {
     TailParams p;
-    p.dec = dec; p.ld = ld_dec; p.Hd = Hd; p.Wd = Wd;
+    p.dec = dec_buf; p.ld = ld_dec; p.Hd = Hd; p.Wd = Wd;
     p.off_y = cfg.pad_activate ? cfg.pad_lat[0] : 0; p.off_x = cfg.pad_activate ? cfg.pad_lon[0] : 0;
     p.Hu = Hu; p.Wu = Wu; p.H = Ho; p.W = Wo; p.C = C_out; p.interp = cfg.interp;
     p.y = y; p.y_phys = y_phys; p.x_next = x_next; p.n_prog = n_prog < 0 ? 0 : n_prog; p.xmap = d_xmap;
     p.mean = have_denorm ? d_mean : nullptr; p.stdv = have_denorm ? d_std : nullptr;
     p.thr_lo = have_tracer ? d_lo : nullptr; p.thr_hi = have_tracer ? d_hi : nullptr;
     p.tracer_denorm = tracer_denorm;
-    p.oy0 = 0; p.dec_row0 = 0; p.Hloc = Ho;
+    p.oy0 = oy0; p.dec_row0 = dec_row0; p.Hloc = rows;
     const size_t lds = (size_t)C_out * 65 * sizeof(float);
     static uint64_t attr_done_mask = 0;   // hipFuncSetAttribute is per device: one bit per device id
     if (!attr_done_on_device(attr_done_mask)) {
@@ -1373,9 +1381,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       attr_mark_device(attr_done_mask);
     }
     if (!tail_channels_ok(C_out)) throw StateError("tail: a channel count ModelSpec::derive() should have refused");
-    const double plane = (double)Ho * Wo * C_out;
+    const double plane = (double)rows * Wo * C_out;
     timed("tail", 0.0, plane * (2.0 * sizeof(T) + 4.0 * ((y ? 1 : 0) + (y_phys ? 1 : 0)) + (x_next ? 4.0 : 0.0)), [&] {
-      hipLaunchKernelGGL(tail_kernel<T>, dim3(cdiv(Wo, 64), Ho), dim3(256), lds, cur_stream, p);
+      hipLaunchKernelGGL(tail_kernel<T>, dim3(cdiv(Wo, 64), rows), dim3(256), lds, cur_stream, p);
       WX_HIP(hipGetLastError());
     });
   }
@@ -1387,7 +1395,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   bool band_on = false;
   int b_rank = 0, b_n = 1;
   BandPlan bplan;
-  int gsh[4] = {0, 0, 0, 0};           // global stage rows; sh[] holds the LOCAL rows of the current layout while a band step runs
   T *bcat[3] = {nullptr, nullptr, nullptr}, *bx3 = nullptr, *blong[4] = {nullptr, nullptr, nullptr, nullptr};
   T *bps[3] = {nullptr, nullptr, nullptr}, *bps4 = nullptr;   // wxformer: pixel-shuffled maps (2 / 1 halo rows, rows beyond the map stay zero)
   T *bxin = nullptr, *bxin_planar = nullptr, *bemb_in = nullptr, *bdec_in = nullptr, *bscut = nullptr, *bta = nullptr, *btb = nullptr,
@@ -1395,7 +1402,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   float* bxneed = nullptr;
   double *gn_all = nullptr, *fix_all = nullptr;
   float* by_internal = nullptr;   // y band when a post block runs and the caller did not ask for y
-  bool b_long[4] = {false, false, false, false};
   char *b_send = nullptr, *b_recv = nullptr;
   int64_t b_send_need = 0, b_recv_need = 0;
   std::vector<std::function<void()>> b_ops;
@@ -1440,7 +1446,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   int b_unpack_slots = 0;   // > 0: the last band_unpack left that many LayerNorm partials per token of the layout it filled
   const float *bx_own = nullptr, *bfrc_own = nullptr;
   float *by = nullptr, *by_phys = nullptr, *bx_next = nullptr;
-  int attn_kind_override = -1;
 
   int b_rows(int s) const { return bplan.g.rows_short(s, b_rank); }
   int b_own_rows() const { return bplan.g.po[b_rank + 1] - bplan.g.po[b_rank]; }
@@ -1458,7 +1463,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       mem.release(splitk_buf);
       splitk_buf = (float*)mem.alloc(splitk_bytes);
     }
-    for (int s = 0; s < 4; ++s) gsh[s] = sh[s];
     bplan.build(band_model(*this, n, (int)sizeof(T), post ? post->n_fixers() : 0));
     b_rank = rank; b_n = n;
     const BandGeom& g = bplan.g;
@@ -1699,11 +1703,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (b_xid.empty() || b_xid.back() >= 0) throw StateError("band: two exchanges after one op at " + name);
     b_xid.back() = band_take(name);
   }
-  void band_layout(int s, bool is_long) {
-    b_long[s] = is_long;
-    sh[s] = is_long ? bplan.g.rows_long(s, b_rank) : bplan.g.rows_short(s, b_rank);
-    attn_kind_override = is_long ? 2 : -1;
-    // LayerNorm partials belong to the rows that just left -- unless the unpack of the redistribution that brought the new rows took them
+  // the stream's rows were just replaced by an exchange: the LayerNorm partials belonged to the rows that left -- unless the unpack of the
+  // redistribution that brought the new rows took them along
+  void band_adopt_unpacked_stats() {
     stat_tiles_ready = b_unpack_slots;
     b_unpack_slots = 0;
   }
@@ -1752,14 +1754,12 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     band_op([this, r] {
       const BandGeom& g = bplan.g;
       const int st0 = cfg.embed_strides[0], a0 = g.ps[0][r], rows0 = g.rows_short(0, r);
-      for (int s = 0; s < 4; ++s) { b_long[s] = false; sh[s] = g.rows_short(s, r); }
-      attn_kind_override = -1;
       cur_stage = 0;
       stat_tiles_ready = 0;
       const int Hb = st0 * rows0 + 2 * halo;
       pack_input(bxneed, bxin, bxin_planar, Hb, bplan.pad_lo[r], bplan.pad_hi[r] - bplan.pad_lo[r], bplan.pad_lo[r] - (st0 * a0 - halo),
                  bplan.x_need_lo[r], bplan.x_need_hi[r] - bplan.x_need_lo[r]);
-      cross_embed(0, bxin, bxin_planar, Hb, 0, 0);
+      cross_embed(band_view(0, false), bxin, bxin_planar, Hb, 0, 0);
     });
     for (int s = 0; s < 4; ++s) {
       if (s > 0) {
@@ -1767,20 +1767,20 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         band_op([this, s, r] {
           const BandGeom& g = bplan.g;
           cur_stage = s;
-          band_layout(s, false);
+          band_adopt_unpacked_stats();
           const int rows = g.rows_short(s, r);
-          cross_embed(s, bemb_in, nullptr, cfg.embed_strides[s] * rows + bplan.m.emb_lo[s] + bplan.m.emb_hi[s], -bplan.m.emb_lo[s], cfg.dim[s - 1]);
+          cross_embed(band_view(s, false), bemb_in, nullptr, cfg.embed_strides[s] * rows + bplan.m.emb_lo[s] + bplan.m.emb_hi[s], -bplan.m.emb_lo[s], cfg.dim[s - 1]);
         });
       }
       const bool a2a = cfg.global_window_size[s] > 1;
       for (int d = 0; d < cfg.depth[s]; ++d) {
         const std::string tag = ".s" + std::to_string(s) + "." + std::to_string(d);
         if (a2a) {
-          band_op([this, s, d] { cur_stage = s; block_half(s, d, false); }, "to_long", tag);
-          band_op([this, s, d] { band_layout(s, true); block_half(s, d, true); }, "to_short", tag);
-          band_op([this, s] { band_layout(s, false); });
+          band_op([this, s, d] { cur_stage = s; block_half(band_view(s, false), d, false); }, "to_long", tag);
+          band_op([this, s, d] { band_adopt_unpacked_stats(); block_half(band_view(s, true), d, true); }, "to_short", tag);
+          band_op([this] { band_adopt_unpacked_stats(); });
         } else {
-          band_op([this, s, d] { cur_stage = s; block_half(s, d, false); block_half(s, d, true); });
+          band_op([this, s, d] { cur_stage = s; block_half(band_view(s, false), d, false); block_half(band_view(s, false), d, true); });
         }
       }
     }
@@ -1824,7 +1824,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         const BandGeom& g = bplan.g;
         const UpL& u = ups[i];
         const int rows = g.rows_short(so, r);
-        band_gn_finish(bta, u.cout, (int64_t)rows * sw[so], (int64_t)gsh[so] * sw[so], u.g1, u.b1, nullptr, 0,
+        band_gn_finish(bta, u.cout, (int64_t)rows * sw[so], (int64_t)sh[so] * sw[so], u.g1, u.b1, nullptr, 0,
                        btb + (int64_t)sw[so] * u.cout, u.cout);
       }, "halo_tb", lv);
       band_op([this, i, so, r] {
@@ -1838,7 +1838,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         const UpL& u = ups[i];
         const int rows = g.rows_short(so, r);
         const int64_t row_el = (int64_t)sw[so] * 2 * cfg.dim[so];
-        band_gn_finish(bta, u.cout, (int64_t)rows * sw[so], (int64_t)gsh[so] * sw[so], u.g2, u.b2, bscut + (int64_t)sw[so] * u.cout, u.cout,
+        band_gn_finish(bta, u.cout, (int64_t)rows * sw[so], (int64_t)sh[so] * sw[so], u.g2, u.b2, bscut + (int64_t)sw[so] * u.cout, u.cout,
                        bcat[so] + row_el, 2 * cfg.dim[so]);
       });
     }
@@ -1880,10 +1880,6 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       }
       band_op([this] { band_finish_post(); });
     }
-    band_op([this] {
-      for (int s = 0; s < 4; ++s) sh[s] = gsh[s];   // leave the whole-map geometry behind
-      attn_kind_override = -1;
-    });
     if (b_next_x != (int)bplan.xs.size()) throw StateError("band: program does not consume every exchange of the plan");
     (void)g;
   }
@@ -1897,35 +1893,16 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     const int64_t plane_b = (int64_t)own * cfg.image_width;
     copy_layout_groups(bx_own, bfrc_own, bx_next, plane_b, cur_stream);
   }
-  void band_finish_post() {   // after the post block: y_phys and the prognostic channels of x_next from the corrected y
+  void band_finish_post() {
     const int own = b_own_rows();
-    if (own > 0 && (by_phys || bx_next)) {
-      hipLaunchKernelGGL(finish_kernel, dim3(2048), dim3(256), 0, cur_stream, by ? by : by_internal, (int64_t)own * Wo, C_out,
-                         have_denorm ? d_mean : nullptr, have_denorm ? d_std : nullptr, by_phys, bx_next, n_prog < 0 ? 0 : n_prog, d_xmap);
-      WX_HIP(hipGetLastError());
-    }
+    if (own > 0 && (by_phys || bx_next)) launch_finish(by ? by : by_internal, (int64_t)own * Wo, by_phys, bx_next);
     band_x_next_copies();
   }
   void band_tail(int dec_row0, bool post_mode) {
-    const int own0 = bplan.g.po[b_rank], own = b_own_rows();
+    const int own = b_own_rows();
     if (own <= 0) return;
-    TailParams p;
-    p.dec = bdec; p.ld = ld_dec; p.Hd = Hd; p.Wd = Wd;
-    p.off_y = cfg.pad_activate ? cfg.pad_lat[0] : 0; p.off_x = cfg.pad_activate ? cfg.pad_lon[0] : 0;
-    p.Hu = Hu; p.Wu = Wu; p.H = Ho; p.W = Wo; p.C = C_out; p.interp = cfg.interp;
-    p.y = post_mode ? (by ? by : by_internal) : by; p.y_phys = post_mode ? nullptr : by_phys; p.x_next = post_mode ? nullptr : bx_next;
-    p.n_prog = n_prog < 0 ? 0 : n_prog; p.xmap = d_xmap;
-    p.mean = have_denorm ? d_mean : nullptr; p.stdv = have_denorm ? d_std : nullptr;
-    p.thr_lo = have_tracer ? d_lo : nullptr; p.thr_hi = have_tracer ? d_hi : nullptr;
-    p.tracer_denorm = tracer_denorm;
-    p.oy0 = own0; p.dec_row0 = dec_row0; p.Hloc = own;
-    const size_t lds = (size_t)C_out * 65 * sizeof(float);
-    WX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tail_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const double plane = (double)own * Wo * C_out;
-    timed("tail", 0.0, plane * (2.0 * sizeof(T) + 4.0 * ((p.y ? 1 : 0) + (p.y_phys ? 1 : 0)) + (p.x_next ? 4.0 : 0.0)), [&] {
-      hipLaunchKernelGGL(tail_kernel<T>, dim3(cdiv(Wo, 64), own), dim3(256), lds, cur_stream, p);
-      WX_HIP(hipGetLastError());
-    });
+    float* y = post_mode ? (by ? by : by_internal) : by;
+    launch_tail(bdec, dec_row0, bplan.g.po[b_rank], own, y, post_mode ? nullptr : by_phys, post_mode ? nullptr : bx_next);
     if (!post_mode) band_x_next_copies();
   }
   int band_run() {

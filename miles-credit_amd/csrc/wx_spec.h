@@ -341,8 +341,7 @@ struct ModelSpec {
 };
 
 // ------------------------------------------------------------------ what the lat-band planner needs of a model (wx_band.h)
-// elem: bytes per activation element; n_fix: conservation fixers of the attached post block.  e.sh[] must hold the whole-map rows
-// (a band step overwrites them with a rank's local rows while it runs)
+// elem: bytes per activation element; n_fix: conservation fixers of the attached post block
 inline BandModel band_model(const ModelSpec& e, int n, int elem, int n_fix) {
   BandModel m;
   m.n = n; m.C_in = e.C_in; m.H = e.cfg.image_height; m.W = e.cfg.image_width;
