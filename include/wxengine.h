@@ -489,6 +489,40 @@ int wx_advect_apply(wx_advect_handle a, const float* u_dev, int64_t u_batch_stri
                     const float* sp_dev, int64_t sp_batch_stride, const float* omega_dev, int64_t omega_batch_stride, int n_tracers,
                     const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch, void* stream);
 
+/* ---- hybrid-level interpolation on the device (csrc/wx_hybrid.h) ------------------------------------------------------------------
+ * credit/postblock/hybrid_interp.py (and the pre block of credit/preblock/hybrid_interp.py over the same engine): 3-D variables from
+ * one set of hybrid sigma-pressure levels onto another, linear in log p with constant extrapolation; float32 throughout.
+ *   wx_hybrid_create / wx_hybrid_destroy <-> _HybridLevelInterpEngine.__init__ (hybrid_interp.py:74-106).  a_src / b_src [n_src] and
+ *                         a_dst / b_dst [n_dst]: HOST arrays of MIDPOINT coefficients in stored order, as
+ *                         load_hybrid_level_coefficients returns them (_interp_utils.py:69-80: vcoord rows, interface averaging,
+ *                         the `levels` subset, the float32 cast -- wxengine.hybrid_interp.midpoint_coefficients).  The library
+ *                         determines the source orientation from a + b * 101325 Pa itself (:100-106; a source stored surface -> top
+ *                         is an index flip of the data's level axis, :133-134, not a copy) and sorts the destination levels by their
+ *                         pressure at 101325 Pa; outputs are in the destination's stored order.  WX_ERR_INVALID with the reason:
+ *                         n_src outside 2 .. 137 (a single source level has no bracket: the reference's gather fails there), n_dst
+ *                         outside 1 .. 137, a null array, a non-finite coefficient, H or W < 1.
+ *   wx_hybrid_apply       <-> _HybridLevelInterpEngine.interp_nested (:108-161) over interp_column_hybrid_to_hybrid (:32-63) and
+ *                         loglinear_interp_columns (_interp_utils.py:14-40):
+ *       src_dev[v]        variable v, batch item b at src_dev[v] + b * batch_stride[v] floats (0 when batch == 1):
+ *                         [n_src][n_time][H][W] contiguous, in the data's level order, read where it lies -- channel slices
+ *                         included -- and never modified; 1 <= n_vars <= 32, in launches of at most eight (every grouping gives
+ *                         the same bits per variable)
+ *       dst_dev[v]        [batch][n_dst][n_time][H][W] contiguous, written completely.  Must not overlap any input.
+ *       sp_dev            surface pressure [Pa], batch item b at sp_dev + b * sp_batch_stride floats: [n_time][H][W]
+ *     p = max(a + b sp, 0.57 Pa) for both level sets from the same sp (:29, :61-62); per destination level the bracket
+ *     hi = clamp(#{m : p_dst >= p_src[m]}, 1, n_src - 1), lo = hi - 1 (_interp_utils.py:33-34), the weight
+ *     clamp(log(p_dst / p_lo) / log(p_hi / p_lo), 0, 1) (:37, as a quotient of logs of ratios) and y_lo + w (y_hi - y_lo) (:40).
+ *     The count holds wherever the column's source pressures are non-decreasing (the reference's precondition); otherwise every
+ *     index still lies in [0, n_src - 1].  Repeated calls give identical bits; a level set interpolated onto itself returns the
+ *     input's bits at every level but the one of highest pressure.  Nothing is allocated at apply; batch * n_time * H * W must stay
+ *     below 2^31. */
+typedef struct wx_hybrid* wx_hybrid_handle;
+int wx_hybrid_create(int H, int W, int n_src, const float* a_src, const float* b_src, int n_dst, const float* a_dst, const float* b_dst,
+                     int device, wx_hybrid_handle* out);
+int wx_hybrid_destroy(wx_hybrid_handle h);
+int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev,
+                    int batch, int n_time, const float* sp_dev, int64_t sp_batch_stride, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

@@ -360,6 +360,33 @@ int wx_advect_apply(wx_advect_handle a, const float* u_dev, int64_t u_batch_stri
     });
   });
 }
+// ---- hybrid-level interpolation (one set of hybrid levels onto another, linear in log p; csrc/wx_hybrid.h) ----------------------
+struct wx_hybrid {
+  std::unique_ptr<wx::Hybrid> impl;
+};
+int wx_hybrid_create(int H, int W, int n_src, const float* a_src, const float* b_src, int n_dst, const float* a_dst, const float* b_dst,
+                     int device, wx_hybrid_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_hybrid_create: null argument");
+    const std::string why = wx::hybrid_check_create(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_hybrid_create: " + why);
+    need_device(device, "wx_hybrid_create");
+    std::unique_ptr<wx_hybrid> h(new wx_hybrid);
+    h->impl.reset(new wx::Hybrid(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst, device));
+    *out = h.release();
+  });
+}
+int wx_hybrid_destroy(wx_hybrid_handle h) { return guarded([&] { delete h; }); }
+int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev,
+                    int batch, int n_time, const float* sp_dev, int64_t sp_batch_stride, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_hybrid_apply: null hybrid-interpolation handle");
+    if (!src_dev || !batch_stride || !dst_dev || !sp_dev) throw wx::ConfigError("wx_hybrid_apply: null argument");
+    remap<wx::ConfigError>([&] {
+      h->impl->apply(n_vars, src_dev, batch_stride, dst_dev, batch, n_time, sp_dev, sp_batch_stride, (hipStream_t)stream);
+    });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

@@ -41,6 +41,7 @@
 #include "wx_diag.h"
 #include "wx_wind.h"
 #include "wx_advect.h"
+#include "wx_hybrid.h"
 #include "wx_noise.h"
 #include "wx_options.h"
 #include "wx_spec.h"

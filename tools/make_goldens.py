@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid]
 """
 import argparse
 import os
@@ -966,6 +966,56 @@ def advect_golden():
         assert max(sizes) < 133000, (name, sizes)
 
 
+def hybrid_golden():
+    """Hybrid-level interpolation: the reference's HybridLevelInterpPost (credit/postblock/hybrid_interp.py) run unmodified on float32
+    and on double tensors, on every case of tests/hybrid_cases.py.  The class reads its coefficients through xarray, which is absent:
+    the stand-in `xarray` module serves the case's arrays to credit.postblock._interp_utils, and `get_meta_file_path` is the identity.
+    Written per case: hybrid_<case>.npz (SHA-256 of every regenerated input, the fp32 outputs, d_ref = the reference's own
+    fp32-against-fp64 distance per variable) and hybrid_<case>_f64.npz (the fp64 outputs as float32 differences from the fp32 ones).
+    The generator refuses to write a fixture that misses one of the conditions its case is there for (hybrid_cases.check_conditions)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from hybrid_cases import HYBRID_CASES, KEYS, SRC, case_inputs, check_conditions, distance, input_digest, reference_args, variables
+    coef = {}
+    standin = oracle_stub.serve_xarray(coef)
+    import credit.postblock._interp_utils as RU
+    import credit.postblock.hybrid_interp as RH
+    RU.xr = standin
+    RU.get_meta_file_path = lambda path: path
+
+    for name, c in HYBRID_CASES.items():
+        inp = case_inputs(name)
+        summary = check_conditions(name, inp)
+        kw, arrays = reference_args(name)
+        coef.clear()
+        coef.update(arrays)
+        blk = RH.HybridLevelInterpPost(**kw)
+        res = {}
+        for dtype in (torch.float32, torch.float64):
+            batch = {"y_processed": {SRC: {KEYS[k]: torch.from_numpy(inp[k]).to(dtype) for k in inp}}}
+            with torch.no_grad():
+                y = blk(batch)["y_processed"][SRC]
+            res[dtype] = {v: y[KEYS[v]].contiguous().numpy() for v in variables(name)}
+            n_dst = blk.engine.dest_a.shape[0]
+            assert all(o.dtype == (np.float32 if dtype == torch.float32 else np.float64)
+                       and o.shape == (c["B"], n_dst, c["T"]) + inp["sp"].shape[3:] for o in res[dtype].values()), name
+        fix, f64, d_ref = {}, {}, {}
+        for k in inp:
+            fix[f"sha256:{k}"] = np.array(input_digest(inp[k]))
+        for v in variables(name):
+            a32, a64 = res[torch.float32][v], res[torch.float64][v]
+            assert np.isfinite(a32).all() and np.isfinite(a64).all(), (name, v)
+            fix[f"f32:{v}"] = a32
+            f64[f"d64:{v}"] = (a64 - a32.astype(np.float64)).astype(np.float32)
+            d_ref[v] = distance(a32, a64)
+            fix[f"d_ref:{v}"] = np.float64(d_ref[v])
+        np.savez_compressed(os.path.join(GOLD, f"hybrid_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"hybrid_{name}_f64.npz"), **f64)
+        sizes = [os.path.getsize(os.path.join(GOLD, f"hybrid_{name}{s}.npz")) for s in ("", "_f64")]
+        assert max(sizes) < 1000000, (name, sizes)
+        print(f"[golden] hybrid {name}: {summary}; files {sizes[0] // 1024} + {sizes[1] // 1024} KB; d_ref "
+              + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()), flush=True)
+
+
 def xform_golden():
     """Variable transforms: the reference's own FillValues / LogTransform / SqrtTransform (credit/preblock/{fill_values,log,sqrt}.py)
     and ExpTransform / SquareTransform (credit/postblock/{exp,square}.py) run unmodified, stacked as the cases of tests/xform_cases.py
@@ -1330,6 +1380,8 @@ def main():
             wind_golden()
         elif item == "advect":      # semi-Lagrangian tracer advection: omega, back-trajectory, trilinear gather
             advect_golden()
+        elif item == "hybrid":      # hybrid-level interpolation: one set of hybrid levels onto another, linear in log p
+            hybrid_golden()
         elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
             xform_golden()
         elif item == "rec":
