@@ -523,6 +523,40 @@ int wx_hybrid_destroy(wx_hybrid_handle h);
 int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev,
                     int batch, int n_time, const float* sp_dev, int64_t sp_batch_stride, void* stream);
 
+/* ---- verification metrics on the device (csrc/wx_metrics.h) ----------------------------------------------------------------------
+ * credit/metrics/base.py, common.py, anomaly.py: the eight per-variable scores of the gen-2 metrics framework from ONE reduction
+ * over prediction, target and climatology, in place of three to eight elementwise passes and a host sync per metric and variable.
+ *   wx_metrics_create / wx_metrics_destroy: the grid and the latitude weights.  lat_w: HOST array [H] (the reference's
+ *                         cos(lat) / mean, base.py:212) or NULL for w = 1.  WX_ERR_INVALID with the reason: H or W < 1, a
+ *                         non-finite weight.
+ *   wx_metrics_apply      <-> BaseVariableMetric._score_variable (base.py:329-356), R2ScoreMetric / LogVarianceRatioMetric
+ *                         (common.py:113-119, :184-191), _AnomalyMetricBase.forward (anomaly.py:284-291) and _score_anomaly (:335-361):
+ *       pred_dev[v], target_dev[v]   variable v, batch item b at pointer + b * batch stride floats (0 when batch == 1):
+ *                         [n_levels[v]][n_time[v]][H][W] contiguous, read where it lies -- channel slices included, a view that
+ *                         starts one float into its buffer too -- and never modified; 1 <= n_vars <= 32
+ *       clim_dev[v]       the climatology of variable v or NULL: level l, time t at clim_dev[v] + l * clim_level_stride[v] +
+ *                         t * clim_time_stride[v] floats ([H][W] contiguous; stride 0 = one level / no time axis), shared by the
+ *                         batch.  clim_dev itself may be NULL (no variable has one: the stream is not read, the stride arrays are
+ *                         not looked at)
+ *       scores_dev        [n_vars][8] float32, written completely, in the order rmse, mse, mae, bias, r2score,
+ *                         log_variance_ratio, acc, activity; acc and activity are NaN for a variable without climatology
+ *     With d = p - t and every mean taken over ALL batch * n_levels * n_time * H * W elements (not divided by the sum of w):
+ *     mse = mean(w d^2), rmse = sqrt(mse), mae = mean(w |d|), bias = mean(w d), r2score = 1 - mse / (mean(w (t - tbar)^2) + 1e-12)
+ *     with tbar = mean(w t), log_variance_ratio = log10(mean(w (p - pbar)^2) + eps) - log10(mean(w (t - tbar)^2) + eps),
+ *     d_f = (p - c) - mean(w (p - c)), d_t = (t - c) - mean(w (t - c)), activity = sqrt(mean(w d_f^2) + 1e-12),
+ *     acc = mean(w d_f d_t) / (activity sqrt(mean(w d_t^2) + 1e-12)).
+ *     Two reading passes (the means, then the centred sums), every sum and score in fp64, float32 at the output only.  Four launches
+ *     per call; no floating-point atomics: repeated calls and any grouping of variables into calls give identical bits.  One handle
+ *     serves one stream at a time (its scratch is the handle's); a call with more tiles than any before grows the scratch, every
+ *     other call allocates nothing. */
+typedef struct wx_metrics* wx_metrics_handle;
+int wx_metrics_create(int H, int W, const float* lat_w, int device, wx_metrics_handle* out);
+int wx_metrics_destroy(wx_metrics_handle h);
+int wx_metrics_apply(wx_metrics_handle h, int n_vars, const float* const* pred_dev, const int64_t* pred_batch_stride,
+                     const float* const* target_dev, const int64_t* target_batch_stride, const float* const* clim_dev,
+                     const int64_t* clim_level_stride, const int64_t* clim_time_stride, const int32_t* n_levels, const int32_t* n_time,
+                     int batch, double eps, float* scores_dev, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

@@ -387,6 +387,36 @@ int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev,
     });
   });
 }
+// ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
+struct wx_metrics {
+  std::unique_ptr<wx::Metrics> impl;
+};
+int wx_metrics_create(int H, int W, const float* lat_w, int device, wx_metrics_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_metrics_create: null argument");
+    const std::string why = wx::metrics_check_create(H, W, lat_w);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_metrics_create: " + why);
+    need_device(device, "wx_metrics_create");
+    std::unique_ptr<wx_metrics> h(new wx_metrics);
+    h->impl.reset(new wx::Metrics(H, W, lat_w, device));
+    *out = h.release();
+  });
+}
+int wx_metrics_destroy(wx_metrics_handle h) { return guarded([&] { delete h; }); }
+int wx_metrics_apply(wx_metrics_handle h, int n_vars, const float* const* pred_dev, const int64_t* pred_batch_stride,
+                     const float* const* target_dev, const int64_t* target_batch_stride, const float* const* clim_dev,
+                     const int64_t* clim_level_stride, const int64_t* clim_time_stride, const int32_t* n_levels, const int32_t* n_time,
+                     int batch, double eps, float* scores_dev, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_metrics_apply: null metrics handle");
+    if (!pred_dev || !pred_batch_stride || !target_dev || !target_batch_stride || !n_levels || !n_time || !scores_dev)
+      throw wx::ConfigError("wx_metrics_apply: null argument");
+    remap<wx::ConfigError>([&] {
+      h->impl->apply(n_vars, pred_dev, pred_batch_stride, target_dev, target_batch_stride, clim_dev, clim_level_stride, clim_time_stride,
+                     n_levels, n_time, batch, eps, scores_dev, (hipStream_t)stream);
+    });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,metrics]
 """
 import argparse
 import os
@@ -1016,6 +1016,102 @@ def hybrid_golden():
               + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()), flush=True)
 
 
+def metrics_reference(case, inp):
+    """The reference's BaseCombinedMetric for a case of tests/metrics_cases.py: the class runs unmodified; the two loaders that read
+    files (the scaler's variances, the grid's latitude) serve the case's arrays."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import metrics_cases as MC
+    import metrics_oracle as MO
+    import credit.metrics.base as RB
+    kw, variances = MC.reference_args(case, inp)
+    RB._load_target_variances = lambda path: dict(variances)
+    RB._cos_lat_weights = lambda path: MO.lat_weights(inp["lat"])
+    return RB.BaseCombinedMetric(**kw)
+
+
+def metrics_hooks_f64(ref, full64):
+    """The reference's own per-variable hooks called on DOUBLE tensors (its forward casts to float32): _score_variable for the
+    plain metrics, the anomaly lines of _AnomalyMetricBase.forward (anomaly.py:269-291) and _score_anomaly for acc and activity.
+    To be called right after ref(full) of the same call, so that the online climatology is the one of that call."""
+    pred = {k: v for s in full64["y_processed"].values() for k, v in s.items()}
+    target = {k: v for s in full64["y_target_processed"].values() for k, v in s.items()}
+    out = {}
+    with torch.no_grad():
+        for name, mod in ref.metric_modules.items():
+            for k in mod.var_keys:
+                p, t = pred[k], target[k]
+                if hasattr(mod, "_score_anomaly"):
+                    clim = mod._get_clim(k, p)
+                    if clim is None:
+                        clim = t.mean(dim=0, keepdim=True)
+                    clim = clim.to(p.device, p.dtype).expand_as(p)
+                    lat_w = mod._lat_w(p)
+                    w = lat_w if lat_w is not None else 1.0
+                    d_f = (p - clim) - (w * (p - clim)).mean()
+                    d_t = (t - clim) - (w * (t - clim)).mean()
+                    out[f"{name}/{k}"] = mod._score_anomaly(d_f, d_t, w).item()
+                else:
+                    out[f"{name}/{k}"] = mod._score_variable(p, t, var_key=k).item()
+    return out
+
+
+def metrics_golden():
+    """Verification metrics: the reference's BaseCombinedMetric forward (float32) on every case of tests/metrics_cases.py, and the
+    float64 restatement of tests/metrics_oracle.py cross-checked against the reference's _score_variable / _score_anomaly hooks on
+    double tensors.  Written per case: metrics_<case>.npz with the SHA-256 of every regenerated input, the keys of the returned dict
+    and per call the fp32 values, the fp64 values, d_ref (the reference's fp32-against-fp64 distance) and the scale of the distance.
+    The sp2d fixture is refused unless a float32 raw-moment evaluation of r2score, log_variance_ratio and acc misses the gate on the
+    pressure variable with sequential and with pairwise summation."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import metrics_cases as MC
+    import metrics_oracle as MO
+    for case, c in MC.METRICS_CASES.items():
+        inp = MC.case_inputs(c["inputs"])
+        ref = metrics_reference(case, inp)
+        mine = MO.Restatement(dtype=torch.float64, **MC.block_args(case, inp))
+        rows = {"f32": [], "f64": [], "d_ref": [], "scale": []}
+        keys = None
+        for call in range(MC.INPUTS[c["inputs"]]["calls"]):
+            full = MC.state_dicts(inp, call, torch.from_numpy)
+            full64 = MC.state_dicts(inp, call, lambda a: torch.from_numpy(a).double())
+            with torch.no_grad():
+                o32 = ref(full)
+            hooks = metrics_hooks_f64(ref, full64)
+            o64 = mine(full64, all_scores=True)
+            assert list(o32) == list(o64), case
+            keys = list(o32)
+            for k, v in hooks.items():
+                assert abs(v - o64[k]) <= 1e-10 * max(1.0, abs(v)), (case, call, k, v, o64[k])
+            sc = MC.scales(mine.last_all_scores, mine.weights, mine.var_keys)
+            assert all(np.isfinite(o32[k]) and np.isfinite(o64[k]) for k in keys), case
+            rows["f32"].append([o32[k] for k in keys])
+            rows["f64"].append([o64[k] for k in keys])
+            rows["scale"].append([sc[k] for k in keys])
+            rows["d_ref"].append([MC.distance(o32[k], o64[k], sc[k]) for k in keys])
+            if case == "sp2d":
+                key = MC.KEYS["sp"]
+                p, t = inp["pred"][0]["sp"], inp["target"][0]["sp"]
+                cl = np.broadcast_to(inp["clim"]["sp"], p.shape)
+                w = np.broadcast_to(MO.lat_weights(inp["lat"]).numpy().reshape(1, 1, 1, -1, 1), p.shape)
+                for pairwise in (False, True):
+                    raw = MC.raw_moments(p, t, cl, w, pairwise)
+                    for m, v in raw.items():
+                        k = f"{m}/{key}"
+                        bound = MC.gate(MC.distance(o32[k], o64[k], sc[k]))[1]
+                        miss = MC.distance(v, o64[k], sc[k])
+                        print(f"[golden] metrics sp2d raw moments ({'pairwise' if pairwise else 'sequential'}) {m}: {v!r} against "
+                              f"{o64[k]!r}: distance {miss:.2e}, gate {bound:.2e}")
+                        assert miss > bound, (m, pairwise, miss, bound)
+        fix = {f"sha256:{k}": np.array(MC.input_digest(v)) for k, v in MC.flat_inputs(inp).items()}
+        fix["keys"] = np.array(keys)
+        fix.update({k: np.array(v, dtype=np.float64) for k, v in rows.items()})
+        path = os.path.join(GOLD, f"metrics_{case}.npz")
+        np.savez_compressed(path, **fix)
+        d = fix["d_ref"]
+        print(f"[golden] metrics {case}: {len(keys)} keys x {d.shape[0]} calls, {os.path.getsize(path) // 1024} KB; max d_ref {d.max():.2e}, "
+              f"median {np.median(d):.2e}", flush=True)
+
+
 def xform_golden():
     """Variable transforms: the reference's own FillValues / LogTransform / SqrtTransform (credit/preblock/{fill_values,log,sqrt}.py)
     and ExpTransform / SquareTransform (credit/postblock/{exp,square}.py) run unmodified, stacked as the cases of tests/xform_cases.py
@@ -1382,6 +1478,8 @@ def main():
             advect_golden()
         elif item == "hybrid":      # hybrid-level interpolation: one set of hybrid levels onto another, linear in log p
             hybrid_golden()
+        elif item == "metrics":     # gen-2 verification metrics: rmse, mse, mae, bias, r2score, log_variance_ratio, acc, activity
+            metrics_golden()
         elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
             xform_golden()
         elif item == "rec":
