@@ -557,6 +557,42 @@ int wx_metrics_apply(wx_metrics_handle h, int n_vars, const float* const* pred_d
                      const int64_t* clim_level_stride, const int64_t* clim_time_stride, const int32_t* n_levels, const int32_t* n_time,
                      int batch, double eps, float* scores_dev, void* stream);
 
+/* ---- ensemble verification on the device (csrc/wx_ensemble.h) ----------------------------------------------------------------------
+ * credit/losses/gen_1/kcrps.py, almost_fair_crps.py, credit/metrics/gen_1/metrics.py:247 (LatWeightedMetricsEnsemble),
+ * credit/applications/rollout_metrics_noisy_model.py:107 (calculate_ensemble_metrics): CRPS (biased, fair, almost fair), spread and
+ * ensemble-mean error of n_members members against the truth from ONE reading pass of (n_members + 1) * 4 bytes per grid point, in
+ * place of a moved-axis copy and a sort copy of the ensemble, an [.., M, M] pairwise tensor and a host round trip per channel.
+ *   wx_ensemble_create / wx_ensemble_destroy: the grid, the latitude weights and the member count.  lat_w: HOST array [H] or NULL for
+ *                         w = 1.  WX_ERR_INVALID with the reason: n_members outside 2..64, H or W < 1, a non-finite weight.
+ *   wx_ensemble_apply:
+ *       member_dev[v * n_members + m]   variable v, member m, batch item b at pointer + b * member_batch_stride[v] floats (0 when
+ *                         batch == 1): [n_levels[v]][n_time[v]][H][W] contiguous, read where it lies and never modified -- separate
+ *                         per-member buffers, channel slices, or the reference's [B * M, ...] tensor (pointer of row m, batch stride
+ *                         M * stride(0)); 1 <= n_vars <= 32; a null member pointer is WX_ERR_INVALID
+ *       target_dev[v]     the truth of variable v, batch item b at pointer + b * target_batch_stride[v] floats
+ *       maps_dev          NULL, or [n_vars * 6] pointers, each NULL (not wanted) or a [batch][n_levels[v]][n_time[v]][H][W] float32
+ *                         map written in the same pass, in the order ens_mean, ens_std (ddof 1), ens_abs_err, crps, fair_crps, afcrps.
+ *                         A map that overlaps an input, the plane table or another map is WX_ERR_INVALID
+ *       planes_dev        [sum_v batch * n_levels[v] * n_time[v]][6] float64, written completely: per plane (v, b, level, t), variables
+ *                         in call order, the sums over H x W of  w skill, w pair, w err^2, w |err|, w ss, w sqrt(ss / (M - 1))
+ *     Per grid point, with d_i = x_i - y (M = n_members): skill = sum |d_i|, pair = sum_{i<j} |d_i - d_j|, err = sum d_i / M,
+ *     ss = sum (d_i - err)^2; w = lat_w[h] or 1, sums not divided by the sum of w.  The maps: ens_mean = y + err,
+ *     ens_std = sqrt(ss / (M - 1)), ens_abs_err = |err|, crps = skill / M - pair / M^2, fair_crps = skill / M - pair / (M (M - 1)),
+ *     afcrps = skill / M - (1 - (1 - alpha) / M) pair / (M (M - 1)).
+ *     The members of a point are sorted in registers; the plane sums are fp64.  Two launches per call; no floating-point atomics:
+ *     repeated calls and any grouping of variables into calls give identical bits, with maps or without, as long as the variable
+ *     takes the same load path (16-byte loads need W % 4 == 0 and every plane base of its members, truth and maps on 16 bytes; the
+ *     scalar path sums a tile in another order, so a layout that changes that alignment changes the last bits).  One handle serves one
+ *     stream at a time (its scratch and its pointer table are the handle's); the first call and a call with more tiles than any
+ *     before allocate, every other call allocates nothing.  A call does not wait for the kernels enqueued before it; it waits
+ *     only for the pointer-table upload of the call four calls earlier (the table is staged through four pinned host slots). */
+typedef struct wx_ensemble* wx_ensemble_handle;
+int wx_ensemble_create(int H, int W, const float* lat_w, int n_members, int device, wx_ensemble_handle* out);
+int wx_ensemble_destroy(wx_ensemble_handle h);
+int wx_ensemble_apply(wx_ensemble_handle h, int n_vars, const float* const* member_dev, const int64_t* member_batch_stride,
+                      const float* const* target_dev, const int64_t* target_batch_stride, const int32_t* n_levels, const int32_t* n_time,
+                      int batch, double alpha, float* const* maps_dev, double* planes_dev, void* stream);
+
 /* ---- lat-band sharding of ONE forecast (BASELINE config 4) -----------------------------------------
  * Replaces credit/domain_parallel (manager.py:22 DomainParallelManager, halo_exchange.py:21-79, layers.py:29-626,
  * sharding.py:13-68) and credit/parallel/domain.py:25-110 (shard_spatial / gather_spatial) for the inference path.

@@ -417,6 +417,35 @@ int wx_metrics_apply(wx_metrics_handle h, int n_vars, const float* const* pred_d
     });
   });
 }
+// ---- ensemble verification (CRPS, spread, ensemble-mean error from one reading pass; csrc/wx_ensemble.h) ---------------------------
+struct wx_ensemble {
+  std::unique_ptr<wx::Ensemble> impl;
+};
+int wx_ensemble_create(int H, int W, const float* lat_w, int n_members, int device, wx_ensemble_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_ensemble_create: null argument");
+    const std::string why = wx::ensemble_check_create(H, W, lat_w, n_members);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_ensemble_create: " + why);
+    need_device(device, "wx_ensemble_create");
+    std::unique_ptr<wx_ensemble> h(new wx_ensemble);
+    h->impl.reset(new wx::Ensemble(H, W, lat_w, n_members, device));
+    *out = h.release();
+  });
+}
+int wx_ensemble_destroy(wx_ensemble_handle h) { return guarded([&] { delete h; }); }
+int wx_ensemble_apply(wx_ensemble_handle h, int n_vars, const float* const* member_dev, const int64_t* member_batch_stride,
+                      const float* const* target_dev, const int64_t* target_batch_stride, const int32_t* n_levels, const int32_t* n_time,
+                      int batch, double alpha, float* const* maps_dev, double* planes_dev, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_ensemble_apply: null ensemble handle");
+    if (!member_dev || !member_batch_stride || !target_dev || !target_batch_stride || !n_levels || !n_time || !planes_dev)
+      throw wx::ConfigError("wx_ensemble_apply: null argument");
+    remap<wx::ConfigError>([&] {
+      h->impl->apply(n_vars, member_dev, member_batch_stride, target_dev, target_batch_stride, n_levels, n_time, batch, alpha, maps_dev,
+                     planes_dev, (hipStream_t)stream);
+    });
+  });
+}
 // ---- post block ------------------------------------------------------------------------------------------------
 struct wx_post {
   std::unique_ptr<wx::PostBlock> impl;

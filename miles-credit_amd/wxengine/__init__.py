@@ -8,6 +8,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   advect            semi-Lagrangian tracer advection, post and pre block (SemiLagrangianAdvection, SemiLagrangianAdvectionPre, exported here)
   hybrid_interp     hybrid-level interpolation, post and pre block (HybridLevelInterp, HybridLevelInterpPre, midpoint_coefficients, exported here)
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
+  ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
 There is no CPU fallback: without the HIP library or a GPU, construction raises.
 """
@@ -26,4 +27,7 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name in ("CombinedMetric", "PendingScores"):
         from . import metrics
         return getattr(metrics, name)
+    if name in ("EnsembleVerification", "PendingEnsembleScores", "EnsembleScores"):
+        from . import ensemble_metrics
+        return getattr(ensemble_metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -148,6 +148,11 @@ _PROTOTYPES = {
     "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
                           C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                           C.c_int, C.c_double, C.c_void_p, C.c_void_p], C.c_int),
+    "wx_ensemble_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_ensemble_destroy": ([C.c_void_p], C.c_int),
+    "wx_ensemble_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_double, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p],
+                          C.c_int),
     "wx_winattn_create": ([C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_winattn_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
     "wx_winattn_destroy": ([C.c_void_p], C.c_int),

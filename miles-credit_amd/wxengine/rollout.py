@@ -116,3 +116,24 @@ def ensemble_rollout(engine: WXEngine, x0: torch.Tensor, forcings: Sequence[Opti
         engine.rollout(x0, forcings, phys_out=phys)
         out.append(phys)
     return out
+
+
+def score_ensemble_rollout(out, targets, verifier, channel_map):
+    """Score the [member][step] output of `ensemble_rollout` where it lies: every step is submitted to `verifier` (an
+    ensemble_metrics.EnsembleVerification) without a host sync, the members read as channel slices of their own buffers.
+
+    channel_map: {var_key: slice, or {"slice": slice, ...} as in run_forecast's channel map} over the output channels; a variable of
+    n channels is scored as n levels.  targets[step]: a [1, C, H, W] tensor in the output's channel layout, or {var_key: [1, L, 1, H, W]}.
+    Returns the list of PendingEnsembleScores, one per step; call result() on them after the loop."""
+    if len(out) != verifier.n_members:
+        raise ValueError(f"score_ensemble_rollout: {len(out)} members for a verifier of {verifier.n_members}")
+    n_steps = len(out[0])
+    if any(len(m) != n_steps for m in out) or len(targets) != n_steps:
+        raise ValueError("score_ensemble_rollout: every member and the targets must have one entry per step")
+    slices = {k: (v["slice"] if isinstance(v, dict) else v) for k, v in channel_map.items()}
+    split = lambda y: {k: y[:, sl].unsqueeze(2) for k, sl in slices.items()}      # noqa: E731  [1, L, H, W] -> [1, L, 1, H, W] views
+    pending = []
+    for step in range(n_steps):
+        target = targets[step]
+        pending.append(verifier.submit([split(member[step]) for member in out], target if isinstance(target, dict) else split(target)))
+    return pending

@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,metrics]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,metrics,ensemble]
 """
 import argparse
 import os
@@ -1112,6 +1112,93 @@ def metrics_golden():
               f"median {np.median(d):.2e}", flush=True)
 
 
+def ensemble_reference(case, inp):
+    """The reference's own classes on a case of tests/ens_cases.py, float32 forward: KCRPSLoss(biased=True / False) and
+    AlmostFairKCRPSLoss(alpha) run unmodified on the [B * M, ...] layout.  -> {var name: {"crps" | "fair_crps" | "afcrps": map}}.
+    credit/metrics/gen_1/metrics.py (LatWeightedMetricsEnsemble) and credit/applications/rollout_metrics_noisy_model.py
+    (calculate_ensemble_metrics) do not import here (datetime.UTC; names credit.metrics no longer exports), and credit/ensemble/crps.py
+    needs properscoring: those three are pinned through tests/ens_oracle.py, which restates metrics.py:304-313,
+    rollout_metrics_noisy_model.py:107-135 and the identity of calculate_crps_per_channel with the plane mean of the biased CRPS."""
+    import ens_cases as EC
+    from credit.losses.gen_1.almost_fair_crps import AlmostFairKCRPSLoss
+    from credit.losses.gen_1.kcrps import KCRPSLoss
+    alpha = EC.ENS_CASES[case]["alpha"]
+    out = {}
+    with torch.no_grad():
+        for name in inp["truth"]:
+            y, x = torch.from_numpy(inp["truth"][name]), torch.from_numpy(EC.stacked(inp["members"][name]))
+            out[name] = {"crps": KCRPSLoss("none", biased=True)(y, x), "fair_crps": KCRPSLoss("none", biased=False)(y, x),
+                         # (its forward squeezes a single-level variable's level axis away: almost_fair_crps.py:23)
+                         "afcrps": AlmostFairKCRPSLoss(alpha=alpha, reduction="none")(y, x).reshape(y.shape)}
+            assert abs(AlmostFairKCRPSLoss(alpha=alpha, reduction="mean")(y, x).item() - out[name]["afcrps"].mean().item()) == 0.0
+    return out
+
+
+def ensemble_golden():
+    """Ensemble verification: per case of tests/ens_cases.py the float32 forward (the reference's KCRPSLoss and AlmostFairKCRPSLoss
+    live for the three CRPS maps and their means, the restatement of tests/ens_oracle.py in float32 for the rest) and the float64
+    restatement.  Written per case: ens_<case>.npz with the SHA-256 of every regenerated input, the flat scalar keys, their fp32
+    values, d_ref (the fp32-against-fp64 distance) and scale, and for the case's map variables the six fp32 maps with d_ref and
+    scale; ens_<case>_f64.npz with the fp64 scalars and each map's fp64 golden as its float32 difference from the fp32 one."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ens_cases as EC
+    import ens_oracle as EO
+    for case, c in EC.ENS_CASES.items():
+        inp = EC.case_inputs(case)
+        live = ensemble_reference(case, inp)
+        w = EO.lat_weights(inp["lat"]) if c["lat"] else None
+        members = {EC.KEYS[n]: torch.from_numpy(v) for n, v in inp["members"].items()}
+        truth = {EC.KEYS[n]: torch.from_numpy(v) for n, v in inp["truth"].items()}
+        r32, m32 = EO.restate(members, truth, c["alpha"], w, torch.float32)
+        r64, m64 = EO.restate(members, truth, c["alpha"], w, torch.float64)
+        wt32 = 1.0 if w is None else w.reshape(1, 1, 1, -1, 1)
+        for n, lv in live.items():          # the live classes replace the restatement wherever they speak
+            k = EC.KEYS[n]
+            for m, ref_map in lv.items():
+                scale = m64[m][k].abs().mean().item()
+                assert EC.map_distance(m32[m][k], ref_map, scale) <= 1e-6, (case, n, m)
+                m32[m][k] = ref_map
+                r32[f"{m}/{k}"] = (ref_map * wt32).mean().item()
+            r32[f"crps_per_channel/{k}"] = (lv["crps"] * wt32).mean(dim=[0, 2, 3, 4]).numpy().astype(np.float64)
+            y64, x64 = torch.from_numpy(inp["truth"][n]).double(), torch.from_numpy(EC.stacked(inp["members"][n])).double()
+            from credit.losses.gen_1.kcrps import KCRPSLoss
+            for m, biased in (("crps", True), ("fair_crps", False)):      # the reference's class on double tensors against the fp64 restatement
+                d = (KCRPSLoss("none", biased=biased)(y64, x64) - m64[m][k]).abs().max().item()
+                assert d <= 1e-11 * max(1.0, m64[m][k].abs().max().item()), (case, n, m, d)
+        f32, f64 = EC.flat_scalars(r32), EC.flat_scalars(r64)
+        keys = EC.scalar_keys(case)
+        assert list(f32) == keys == list(f64), case
+        scale = [abs(f64[k]) for k in keys]
+        fix = {f"sha256:{k}": np.array(EC.input_digest(v)) for k, v in EC.flat_inputs(inp).items()}
+        fix.update(keys=np.array(keys), f32=np.array([f32[k] for k in keys], dtype=np.float64), scale=np.array(scale, dtype=np.float64),
+                   d_ref=np.array([EC.distance(f32[k], f64[k], sc) for k, sc in zip(keys, scale)], dtype=np.float64),
+                   moved=np.array([inp["moved"][n] for n in c["vars"]]))
+        fix64 = {"f64": np.array([f64[k] for k in keys], dtype=np.float64)}
+        worst_map = 0.0
+        for n in c["map_vars"]:
+            k = EC.KEYS[n]
+            for m in EC.MAPS:
+                a32, a64 = m32[m][k].numpy().astype(np.float32), m64[m][k].numpy()
+                sc = float(np.abs(m64["ens_abs_err"][k].numpy()).mean()) if m == "ens_mean" else float(np.abs(a64).mean())
+                fix[f"map32:{m}:{n}"] = a32
+                fix[f"map_scale:{m}:{n}"] = np.array(sc)
+                fix[f"map_d_ref:{m}:{n}"] = np.array(EC.map_distance(a32, a64, sc))
+                fix64[f"d64:{m}:{n}"] = (a64 - a32.astype(np.float64)).astype(np.float32)
+                worst_map = max(worst_map, float(fix[f"map_d_ref:{m}:{n}"]))
+        paths = [os.path.join(GOLD, f"ens_{case}.npz"), os.path.join(GOLD, f"ens_{case}_f64.npz")]
+        np.savez_compressed(paths[0], **fix)
+        np.savez_compressed(paths[1], **fix64)
+        sizes = [os.path.getsize(p) for p in paths]
+        assert max(sizes) < 1_000_000, (case, sizes)
+        print(f"[golden] ensemble {case}: {len(keys)} scalars, {len(c['map_vars']) * len(EC.MAPS)} maps, files {sizes[0] // 1024} + "
+              f"{sizes[1] // 1024} KB; moved apart {dict(inp['moved'])}; max scalar d_ref {fix['d_ref'].max():.2e}, max map d_ref "
+              f"{worst_map:.2e}", flush=True)
+        if case == "m3":
+            k = EC.KEYS["sp"]
+            print("[golden] ensemble m3 surface pressure d_ref: " + ", ".join(
+                f"{m} {float(fix[f'map_d_ref:{m}:sp']):.2e}" for m in EC.MAPS), flush=True)
+
+
 def xform_golden():
     """Variable transforms: the reference's own FillValues / LogTransform / SqrtTransform (credit/preblock/{fill_values,log,sqrt}.py)
     and ExpTransform / SquareTransform (credit/postblock/{exp,square}.py) run unmodified, stacked as the cases of tests/xform_cases.py
@@ -1480,6 +1567,8 @@ def main():
             hybrid_golden()
         elif item == "metrics":     # gen-2 verification metrics: rmse, mse, mae, bias, r2score, log_variance_ratio, acc, activity
             metrics_golden()
+        elif item == "ensemble":    # ensemble verification: CRPS (biased, fair, almost fair), spread, ensemble-mean error
+            ensemble_golden()
         elif item == "xform":       # gen-2 variable transforms: fill_values, log / sqrt in, exp / square out
             xform_golden()
         elif item == "rec":
