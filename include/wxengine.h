@@ -249,7 +249,19 @@ int wx_swin_destroy(wx_swin_handle s);
  *     "u_transformer.up." with "u_transformer.up.conv.weight" [2 dim][dim][2][2] (ConvTranspose2d), "fc.weight" [C_out ph pw][dim],
  *     "fc.bias", and "u_transformer.layer.blocks.<i>.<wx_swin_load name>" for the stage.
  *   wx_fuxi_debug_map(name in {"embed", "down", "stage", "up"}): an intermediate token map [rows][cols][dim] of the LAST forward,
- *     converted to float32 (tests); host == NULL only reports the shape. */
+ *     converted to float32 (tests); host == NULL only reports the shape.  "patches" / "fc" are the two sides of the patch reshapes:
+ *     the gathered patch rows [Hp][Wp][k0_padded] the embed GEMM reads (column order = the Conv3d weight's flatten order
+ *     ((c frames + t) ph + py) pw + px; pad columns zero) and fc's output [Hp][Wp][nfc_padded] (column (py pw + px) C_out + c).
+ *     shape[2] is the map's own width.
+ *   wx_fuxi_query(key): one integer fact about the model / its LAST forward, by name (tests assert which kernel a case ran):
+ *     "patchify_rows"      1 = the last forward gathered patches with the row kernel (patch width 4, x on a 16-byte boundary), 0 = the
+ *                          generic gather; before the first forward, what a 16-byte aligned x takes
+ *     "unpatchify_lds"     1 = the patch -> pixel scatter runs through LDS (patch width divides 256, 256 C_out elements fit 64 KiB)
+ *     "unpatchify_chunks"  x-chunks of 256 / pw patches per patch sub-row in that kernel (0 with the generic scatter)
+ *     "k0", "k0_padded"    C_in frames ph pw, and the row width of the embed GEMM's input (64-byte multiples)
+ *     "nfc", "nfc_padded"  C_out ph pw, and fc's output width (multiples of 8)
+ *     "fc_dma"             1 = fc runs the LDS-DMA GEMM, 0 = the slow GEMM (nfc_padded < 48)
+ *     An unknown key is WX_ERR_INVALID. */
 typedef struct wx_fuxi_desc {
   int32_t precision;            /* WX_PREC_FP32 / WX_PREC_BF16 */
   int32_t H, W;                 /* image_height, image_width */
@@ -271,6 +283,7 @@ int wx_fuxi_load(wx_fuxi_handle f, const char* name, const float* host_data, int
 int wx_fuxi_finalize(wx_fuxi_handle f);
 int wx_fuxi_forward(wx_fuxi_handle f, const float* x_dev, float* y_dev, void* stream);
 int wx_fuxi_debug_map(wx_fuxi_handle f, const char* name, float* host, int64_t capacity, int64_t shape[3]);
+int wx_fuxi_query(wx_fuxi_handle f, const char* key, int64_t* value);
 int wx_fuxi_flops(wx_fuxi_handle f, double* flops);
 int wx_fuxi_destroy(wx_fuxi_handle f);
 

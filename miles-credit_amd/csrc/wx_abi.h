@@ -722,6 +722,13 @@ int wx_fuxi_debug_map(wx_fuxi_handle w, const char* name, float* host, int64_t c
     remap<wx::ShapeError>([&] { w->impl->debug_copy(name, host, capacity, shape); });
   });
 }
+int wx_fuxi_query(wx_fuxi_handle w, const char* key, int64_t* value) {
+  return guarded([&] {
+    if (!w) throw wx::StateError("null fuxi handle");
+    if (!key || !value) throw wx::ConfigError("wx_fuxi_query: null argument");
+    if (!w->impl->query(key, value)) throw wx::ConfigError(std::string("wx_fuxi_query: unknown key '") + key + "'");
+  });
+}
 int wx_fuxi_flops(wx_fuxi_handle w, double* flops) {
   return guarded([&] { if (!w || !flops) throw wx::ConfigError("fuxi: null argument"); *flops = w->impl->flops(); });
 }

@@ -135,6 +135,7 @@ struct FuxiBase {
   virtual void finalize() = 0;
   virtual void forward(const float* x, float* y, hipStream_t s) = 0;
   virtual void debug_copy(const char* name, float* host, int64_t cap, int64_t shape[3]) = 0;
+  virtual bool query(const char* key, int64_t* value) const = 0;
   virtual double flops() const = 0;
 };
 
@@ -155,6 +156,7 @@ struct FuxiModel : FuxiBase {
   float2* gn_part;   // [M tiles of 128 rows][dim] per-channel (sum, sum sq) written by the producing convolution's epilogue
   char* zero_page;
   bool ready = false;
+  bool ran_rows;     // the patch gather of the LAST forward (before the first: the one a 16-byte aligned x takes)
 
   void* dalloc(size_t n) { return mem.alloc(n ? n : 16); }   // a zero-size request still gets a distinct, non-null buffer
   // split (T = float; WX_PREC_FP32_SPLIT): every convolution / Linear of the forward and of the stage runs split-bf16 arithmetic from a
@@ -194,6 +196,10 @@ struct FuxiModel : FuxiBase {
     for (int i = 0; i < 4; ++i) { gn_d[i] = wf(dim); gn_u[i] = wf(dim); }
     P = wT(Mp * K0p); E = wT(Mp * dim); D0 = wT(Md * dim); TA = wT(Mp * dim); TB = wT((Mp + 2 * Wp) * dim); S = wT(Ms * dim); CAT = wT(Md * 2 * dim);
     U0 = wT(Mp * dim); UA = TA; UB = TB; U1 = wT(Mp * dim); F = wT(Mp * (size_t)Nfcp);
+    // the row gather writes whole groups of (c, t) planes and may stop short of K0p: the pad columns meet zero weights in the embed GEMM,
+    // which does not help when the allocation's old bytes read as NaN or Inf.  Neither gather is asked to write them on every forward.
+    WX_HIP(hipMemset(P, 0, Mp * K0p * sizeof(T)));
+    ran_rows = patchify_rows(nullptr).use;
     gn_acc = (double*)dalloc(2 * dim * sizeof(double));
     gn_part = (float2*)dalloc((size_t)cdiv((int64_t)Mp, 128) * dim * sizeof(float2));
     zero_page = (char*)dalloc(256);
@@ -313,12 +319,22 @@ struct FuxiModel : FuxiBase {
     return 2.0 * Mp * dim * K0 + 2.0 * Md * dim * 9 * dim * 3 + stage->flops() + 2.0 * Md * 4 * dim * 2 * dim + 2.0 * Mp * dim * 9 * dim * 2 + 2.0 * Mp * Nfc * dim;
   }
   // ---- launch helpers ---------------------------------------------------------------------------------------------------------
-  void conv(const T* in, int in_h, int in_w, int cin, const T* w, const float* bias, int n, int k, int stride, int pad, int out_h, int out_w, T* out,
-            int64_t out_ld, int out_mode, int cout, hipStream_t s, bool gn = false) {
+  static ConvGemmParams conv_params(const T* in, int in_h, int in_w, int cin, const T* w, const float* bias, int n, int k, int stride, int pad, int out_h,
+                                    int out_w, T* out, int64_t out_ld, int out_mode, int cout) {
     ConvGemmParams p;
     std::memset(&p, 0, sizeof(p));
     p.in = in; p.in_h = in_h; p.in_w = in_w; p.in_ld = cin; p.cin = cin; p.kh = p.kw = k; p.stride = stride; p.pad_y = p.pad_x = pad;
     p.out_h = out_h; p.out_w = out_w; p.wt = w; p.n = n; p.n_alloc = n; p.bias = bias; p.out = out; p.out_ld = out_ld; p.out_mode = out_mode; p.cout = cout;
+    return p;
+  }
+  ConvGemmParams fc_params() const { return conv_params(U1, 1, Hp * Wp, d.dim, w_fc, b_fc, Nfcp, 1, 1, 0, 1, Hp * Wp, F, Nfcp, 0, 0); }
+  void conv(const T* in, int in_h, int in_w, int cin, const T* w, const float* bias, int n, int k, int stride, int pad, int out_h, int out_w, T* out,
+            int64_t out_ld, int out_mode, int cout, hipStream_t s, bool gn = false) {
+    conv(conv_params(in, in_h, in_w, cin, w, bias, n, k, stride, pad, out_h, out_w, out, out_ld, out_mode, cout), s, gn);
+  }
+  void conv(ConvGemmParams p, hipStream_t s, bool gn = false) {
+    const T* w = static_cast<const T*>(p.wt);
+    const int cin = p.cin;
     if (gn) {   // GroupNorm partials from the epilogue (fast path only: dim % 64 == 0 guarantees it)
       if (!conv_gemm_is_dma<T>(p, zero_page)) throw std::runtime_error("fuxi: GroupNorm partials need the LDS-DMA GEMM path");
       p.gn_out = gn_part;
@@ -341,18 +357,50 @@ struct FuxiModel : FuxiBase {
                        (int64_t)c, out, out_ld);
     WX_HIP(hipGetLastError());
   }
+  // ---- which patch gather / scatter a forward takes: forward() and query() both ask these two -------------------------------------
+  struct RowsGather { bool use; int G, ldt; size_t lds; };
+  // the row gather (patch width 4) loads one float4 per patch and image row: x must sit on a 16-byte boundary (every row then does, W % 4 == 0);
+  // x == nullptr asks about the geometry alone
+  RowsGather patchify_rows(const float* x) const {
+    RowsGather r;
+    r.G = std::max(1, 128 / (d.ph * 4 * (int)sizeof(T)));             // (c, t) planes per workgroup: 128 bytes of every patch row
+    r.ldt = r.G * d.ph * 4 + 8 / (int)sizeof(T);
+    r.lds = (size_t)Wp * r.ldt * sizeof(T);
+    r.use = d.pw == 4 && d.W % 4 == 0 && (r.G * d.ph * 4 * (int)sizeof(T)) % 16 == 0 && r.lds <= 64 * 1024 && reinterpret_cast<uintptr_t>(x) % 16 == 0;
+    return r;
+  }
+  struct LdsScatter { bool use; int chunks; size_t lds; };
+  LdsScatter unpatchify_lds() const {
+    LdsScatter r;
+    r.lds = (size_t)(256 / std::max(1, std::min(d.pw, 256))) * d.pw * d.C_out * sizeof(T);
+    r.use = 256 % d.pw == 0 && r.lds <= 64 * 1024;
+    r.chunks = r.use ? (int)cdiv(Wp, 256 / d.pw) : 0;   // x-chunks of 256 / pw patches per patch sub-row
+    return r;
+  }
+  bool query(const char* key, int64_t* value) const override {
+    const std::string k(key);
+    if (k == "patchify_rows") *value = ran_rows;
+    else if (k == "unpatchify_lds") *value = unpatchify_lds().use;
+    else if (k == "unpatchify_chunks") *value = unpatchify_lds().chunks;
+    else if (k == "k0") *value = K0;
+    else if (k == "k0_padded") *value = K0p;
+    else if (k == "nfc") *value = Nfc;
+    else if (k == "nfc_padded") *value = Nfcp;
+    else if (k == "fc_dma") *value = conv_gemm_is_dma<T>(fc_params(), zero_page);
+    else return false;
+    return true;
+  }
   void forward(const float* x, float* y, hipStream_t s) override {
     if (!ready) throw std::runtime_error("fuxi: finalize first");
     WX_HIP(hipSetDevice(device));
     const int dim = d.dim;
     const int64_t Mp = (int64_t)Hp * Wp, Md = (int64_t)Hd * Wd;
     // CubeEmbedding
-    const int G = std::max(1, 128 / (d.ph * 4 * (int)sizeof(T)));             // (c, t) planes per workgroup: 128 bytes of every patch row
-    const int ldt = G * d.ph * 4 + 8 / (int)sizeof(T);
-    const size_t pat_lds = (size_t)Wp * ldt * sizeof(T);
-    if (d.pw == 4 && d.W % 4 == 0 && (G * d.ph * 4 * (int)sizeof(T)) % 16 == 0 && pat_lds <= 64 * 1024) {
+    const RowsGather rg = patchify_rows(x);
+    ran_rows = rg.use;
+    if (rg.use) {
       const int CT = d.C_in * d.frames;
-      hipLaunchKernelGGL(fuxi_patchify_rows_kernel<T>, dim3(Hp * cdiv(CT, G)), dim3(256), pat_lds, s, x, P, CT, d.H, d.W, d.ph, Hp, Wp, K0p, G, ldt);
+      hipLaunchKernelGGL(fuxi_patchify_rows_kernel<T>, dim3(Hp * cdiv(CT, rg.G)), dim3(256), rg.lds, s, x, P, CT, d.H, d.W, d.ph, Hp, Wp, K0p, rg.G, rg.ldt);
     } else {
       hipLaunchKernelGGL(fuxi_patchify_kernel<T>, dim3(2048), dim3(256), 0, s, x, P, d.C_in, d.frames, d.H, d.W, d.ph, d.pw, Hp, Wp, K0, K0p);
     }
@@ -376,10 +424,10 @@ struct FuxiModel : FuxiBase {
     conv(UB, Hp, Wp, dim, w_u3, b_u3, dim, 3, 1, 1, Hp, Wp, UA, dim, 0, 0, s, true);
     gn_silu(UA, Mp, gn_u[2], gn_u[3], d.groups_up, U0, U1, dim, s);
     // fc + patch -> pixel
-    conv(U1, 1, (int)Mp, dim, w_fc, b_fc, Nfcp, 1, 1, 0, 1, (int)Mp, F, Nfcp, 0, 0, s);
-    const size_t unp_lds = (size_t)(256 / std::max(1, std::min(d.pw, 256))) * d.pw * d.C_out * sizeof(T);
-    if (256 % d.pw == 0 && unp_lds <= 64 * 1024) {
-      hipLaunchKernelGGL(fuxi_unpatchify_lds_kernel<T>, dim3(Hp * d.ph * cdiv(Wp, 256 / d.pw)), dim3(256), unp_lds, s, F, (int64_t)Nfcp, y, d.C_out, d.ph, d.pw, Hp, Wp);
+    conv(fc_params(), s);
+    const LdsScatter us = unpatchify_lds();
+    if (us.use) {
+      hipLaunchKernelGGL(fuxi_unpatchify_lds_kernel<T>, dim3(Hp * d.ph * us.chunks), dim3(256), us.lds, s, F, (int64_t)Nfcp, y, d.C_out, d.ph, d.pw, Hp, Wp);
     } else {
       hipLaunchKernelGGL(fuxi_unpatchify_kernel<T>, dim3(2048), dim3(256), 0, s, F, (int64_t)Nfcp, y, d.C_out, d.ph, d.pw, Hp, Wp);
     }
@@ -391,24 +439,27 @@ struct FuxiModel : FuxiBase {
     hipLaunchKernelGGL(fuxi_copy_pixels_kernel<T>, dim3((unsigned)std::min<int64_t>(4096, cdiv(total, 256))), dim3(256), 0, s, src, src_ld, dst, dst_ld, rows,
                        cols, src_w, dst_w, d.dim * (int)sizeof(T) / 16);
   }
-  // intermediate maps for the parity tests: "embed" [Hp][Wp][dim], "down" (DownBlock output) [Hd][Wd][dim], "up" (UpBlock output) [Hp][Wp][dim]
+  // intermediate maps for the parity tests: "embed" [Hp][Wp][dim], "down" (DownBlock output) [Hd][Wd][dim], "up" (UpBlock output) [Hp][Wp][dim],
+  // and the two sides of the patch reshapes: "patches" = P [Hp][Wp][K0p] (pad columns included), "fc" = F [Hp][Wp][Nfcp]
   void debug_copy(const char* name, float* host, int64_t cap, int64_t shape[3]) override {
     WX_HIP(hipSetDevice(device));
     const std::string k(name);
-    const T* src; int64_t rows, ld;
+    const T* src; int64_t rows, ld, width = d.dim;
     if (k == "embed") { src = E; rows = (int64_t)Hp * Wp; ld = d.dim; shape[0] = Hp; shape[1] = Wp; }
     else if (k == "down") { src = CAT; rows = (int64_t)Hd * Wd; ld = 2 * d.dim; shape[0] = Hd; shape[1] = Wd; }
     else if (k == "stage") { src = CAT + d.dim; rows = (int64_t)Hd * Wd; ld = 2 * d.dim; shape[0] = Hd; shape[1] = Wd; }
     else if (k == "up") { src = U1; rows = (int64_t)Hp * Wp; ld = d.dim; shape[0] = Hp; shape[1] = Wp; }
+    else if (k == "patches") { src = P; rows = (int64_t)Hp * Wp; ld = width = K0p; shape[0] = Hp; shape[1] = Wp; }
+    else if (k == "fc") { src = F; rows = (int64_t)Hp * Wp; ld = width = Nfcp; shape[0] = Hp; shape[1] = Wp; }
     else throw std::runtime_error("fuxi: no debug map named " + k);
-    shape[2] = d.dim;
+    shape[2] = width;
     if (!host) return;
-    if (cap < rows * d.dim) throw std::runtime_error("fuxi: debug buffer too small");
+    if (cap < rows * width) throw std::runtime_error("fuxi: debug buffer too small");
     WX_HIP(hipDeviceSynchronize());
-    std::vector<T> h((size_t)((rows - 1) * ld + d.dim));   // "stage" starts `dim` channels into the concat buffer: stop at its last channel
+    std::vector<T> h((size_t)((rows - 1) * ld + width));   // "stage" starts `dim` channels into the concat buffer: stop at its last channel
     WX_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(T), hipMemcpyDeviceToHost));
     for (int64_t r = 0; r < rows; ++r)
-      for (int c = 0; c < d.dim; ++c) host[r * d.dim + c] = Elem<T>::to_f(h[(size_t)(r * ld + c)]);
+      for (int64_t c = 0; c < width; ++c) host[r * width + c] = Elem<T>::to_f(h[(size_t)(r * ld + c)]);
   }
 };
 

@@ -222,6 +222,28 @@ def named_fuxi_config(name: str) -> FuxiConfig:
         return FuxiConfig(image_height=32, patch_height=4, image_width=64, patch_width=4, levels=1, frames=1, frame_patch_size=1, dim=64,
                           num_groups=4, channels=4, surface_channels=3, input_only_channels=0, output_only_channels=1, num_heads=1,
                           depth=2, window_size=4, use_spectral_norm=False, meta_hidden=16, stage="cr")
+    # FT3 .. FT7: the patch reshapes away from patch width 4 and from widths that need no padding (tests/test_fuxi.py's path table)
+    if name == "FT3":    # the reference's default patch 16 x 16: generic gather (K0 1536); LDS scatter in 2 x-chunks of 16 patches, the last with 2
+        return FuxiConfig(image_height=32, patch_height=16, image_width=288, patch_width=16, levels=2, frames=2, frame_patch_size=2, dim=64,
+                          num_groups=(8, 16), channels=1, surface_channels=1, input_only_channels=0, output_only_channels=0, num_heads=2,
+                          depth=2, window_size=3, meta_hidden=24, stage="cr")
+    if name == "FT4":    # patch height 3: the row gather stops at column 24 of 32 in fp32 and does not apply in bf16; fc 36 -> 40 columns (the
+        # slow GEMM); LDS scatter in 2 x-chunks of 64 patches, the last with 6; 560 / 140 tokens: ragged 128-row GroupNorm tiles
+        return FuxiConfig(image_height=24, patch_height=3, image_width=280, patch_width=4, levels=1, frames=2, frame_patch_size=2, dim=64,
+                          num_groups=16, channels=1, surface_channels=0, input_only_channels=0, output_only_channels=2, num_heads=2,
+                          depth=2, window_size=7, meta_hidden=24, stage="cr")
+    if name == "FT5":    # patch height 6: the row gather in both types, stopping at column 48 of 64 in bf16; both stage axes padded
+        return FuxiConfig(image_height=24, patch_height=6, image_width=48, patch_width=4, levels=1, frames=1, frame_patch_size=1, dim=64,
+                          num_groups=8, channels=1, surface_channels=1, input_only_channels=0, output_only_channels=1, num_heads=1,
+                          depth=2, window_size=4, meta_hidden=24, stage="cr")
+    if name == "FT6":    # patch 5 x 3: generic gather AND generic scatter in both types; K0 = Nfc = 45, padded to 48 / 64 and to 48
+        return FuxiConfig(image_height=20, patch_height=5, image_width=36, patch_width=3, levels=1, frames=1, frame_patch_size=1, dim=64,
+                          num_groups=4, channels=2, surface_channels=1, input_only_channels=0, output_only_channels=0, num_heads=2,
+                          depth=2, window_size=3, meta_hidden=24, stage="cr")
+    if name == "FT7":    # FuXi's 67 channels in and out (fp32: more than the LDS scatter holds), dim 192 = 1.5 conv tiles, head width 96
+        return FuxiConfig(image_height=16, patch_height=4, image_width=32, patch_width=4, levels=15, frames=2, frame_patch_size=2, dim=192,
+                          num_groups=32, channels=4, surface_channels=7, input_only_channels=0, output_only_channels=0, num_heads=2,
+                          depth=2, window_size=4, meta_hidden=24, stage="cr")
     if name in ("FT0T", "FT1T", "FT2T"):   # the same three geometries with timm's block in the stage (the reference's own structure)
         import dataclasses
         return dataclasses.replace(named_fuxi_config(name[:-1]), stage="timm")
@@ -373,7 +395,16 @@ class FuxiHIP:
         _check(self.lib.wx_fuxi_flops(self._h, C.byref(f)))
         return float(f.value)
 
+    def query(self, key: str) -> int:
+        """One integer fact about the model / its last forward (include/wxengine.h wx_fuxi_query): which patch gather and scatter ran,
+        the padded GEMM widths."""
+        v = C.c_int64()
+        _check(self.lib.wx_fuxi_query(self._h, key.encode(), C.byref(v)))
+        return int(v.value)
+
     def debug_map(self, name: str) -> np.ndarray:
+        """An intermediate map of the last forward as float32: "embed" / "up" [Hp, Wp, dim], "down" / "stage" [Hp / 2, Wp / 2, dim],
+        "patches" [Hp, Wp, k0_padded] (the embed GEMM's input rows), "fc" [Hp, Wp, nfc_padded] (fc's output before the patch reshape)."""
         shape = (C.c_int64 * 3)()
         _check(self.lib.wx_fuxi_debug_map(self._h, name.encode(), None, C.c_int64(0), shape))
         out = np.empty(tuple(int(s) for s in shape), dtype=np.float32)

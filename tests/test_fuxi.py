@@ -1,6 +1,6 @@
 """BASELINE config 5 -- the FuXi forward (credit/models/fuxi.py:454-500) around a Swin V2 (Cr) stage.
 
-Golden: tests/golden/fuxi_{FT0,FT1,FT2}.npz = the output and four intermediate maps of the reference's own `Fuxi.forward`,
+Golden: tests/golden/fuxi_{FT0..FT7}.npz = the output and four intermediate maps of the reference's own `Fuxi.forward`,
 `UTransformer.forward`, `CubeEmbedding`, `DownBlock`, `UpBlock`, `apply_spectral_norm` run in the dev container with the reference's
 V2-Cr blocks as the stage (tools/make_goldens.py::fuxi_golden; timm's stage class is not vendored), on the keyed
 synthetic weights of wxengine.fuxi.synth_fuxi_state_dict (loaded there strict=True: the key names are pinned too).
@@ -9,7 +9,9 @@ spectral-norm fold against the oracle's, config / state-spec logic.
 GPU: the HIP model (`wx_fuxi_*`) against the goldens and the oracle:
     fp32 (exact-f32 MFMA)  max|y - ref| <= 2e-4 * max|ref| on y and every intermediate map
     bf16                   rel-L2 <= 2e-2 and max err <= 6e-2 * max|ref| on y; rel-L2 <= 2e-2 on the maps
-and, at BASELINE config 5's own size (F6H: 640 x 1280, patch 4, dim 1024, 16 blocks), size-independent properties."""
+and, at BASELINE config 5's own size (F6H: 640 x 1280, patch 4, dim 1024, 16 blocks), size-independent properties.
+The forward picks its patch gather / scatter and its GEMM paddings from the geometry: PATHS below is the table of what each case runs
+(asserted through wx_fuxi_query), and the two reshapes are compared bit for bit with a host gather / permutation."""
 import dataclasses
 import os
 
@@ -22,8 +24,29 @@ from wxengine.fuxi import FuxiConfig, fold_spectral_norm, named_fuxi_config, syn
 from wxengine.synth import keyed_normal
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-CASES = ["FT0", "FT1", "FT2"]
+CASES = ["FT0", "FT1", "FT2", "FT3", "FT4", "FT5", "FT6", "FT7"]
 MAPS = ["embed", "down", "stage", "up"]
+PRECS = ["fp32", "fp32s", "bf16"]
+QUERY_KEYS = ("patchify_rows", "unpatchify_lds", "unpatchify_chunks", "k0", "k0_padded", "nfc", "nfc_padded", "fc_dma")
+# What each case runs, per storage type (fp32s stores fp32), in QUERY_KEYS order -- worked out by hand from the geometry:
+#   patchify_rows      patch width 4 and G ph 4 elements a multiple of 16 bytes, G = max(1, 128 bytes // (ph 4 elements))
+#   unpatchify_lds     patch width divides 256 and 256 C_out elements fit 64 KiB; chunks = ceil(Wp / (256 / pw))
+#   k0_padded          K0 = C_in frames ph pw rounded up to 64 bytes;  nfc_padded: Nfc = C_out ph pw rounded up to 8
+#   fc_dma             nfc_padded >= 48
+PATHS = {
+    "FT0": {"fp32": (1, 1, 1, 112, 112, 56, 56, 1), "bf16": (1, 1, 1, 112, 128, 56, 56, 1)},
+    "FT1": {"fp32": (1, 1, 1, 288, 288, 128, 128, 1), "bf16": (1, 1, 1, 288, 288, 128, 128, 1)},
+    "FT2": {"fp32": (1, 1, 1, 112, 112, 128, 128, 1), "bf16": (1, 1, 1, 112, 128, 128, 128, 1)},
+    "FT3": {"fp32": (0, 1, 2, 1536, 1536, 768, 768, 1), "bf16": (0, 1, 2, 1536, 1536, 768, 768, 1)},     # chunks of 16 patches: 16 + 2
+    "FT4": {"fp32": (1, 1, 2, 24, 32, 36, 40, 0), "bf16": (0, 1, 2, 24, 32, 36, 40, 0)},                 # chunks of 64 patches: 64 + 6
+    "FT5": {"fp32": (1, 1, 1, 48, 48, 72, 72, 1), "bf16": (1, 1, 1, 48, 64, 72, 72, 1)},
+    "FT6": {"fp32": (0, 0, 0, 45, 48, 45, 48, 1), "bf16": (0, 0, 0, 45, 64, 45, 48, 1)},
+    "FT7": {"fp32": (1, 0, 0, 2144, 2144, 1072, 1072, 1), "bf16": (1, 1, 1, 2144, 2144, 1072, 1072, 1)},  # fp32: 256 x 67 floats > 64 KiB
+}
+
+
+def paths(name, prec):
+    return dict(zip(QUERY_KEYS, PATHS[name]["bf16" if prec == "bf16" else "fp32"]))
 
 
 def case(name):
@@ -207,7 +230,7 @@ def build(cfg, sd, prec):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("prec", ["fp32", "fp32s", "bf16"])
+@pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("name", CASES)
 def test_hip_fuxi_vs_reference_golden(name, prec):
     cfg, sd, x, g = case(name)
@@ -297,6 +320,117 @@ def test_hip_fuxi_with_the_timm_stage_vs_oracle(name, prec):
     else:
         l2 = ((y.double() - yo).norm() / yo.norm()).item()
         assert l2 <= 2e-2 and (y.double() - yo).abs().max() <= 6e-2 * yo.abs().max(), f"bf16 rel-L2 {l2:.3e}"
+
+
+def test_path_table_covers_every_reshape_path_in_both_types():
+    """The cases together reach, per storage type: both patch gathers, both scatters, an LDS scatter with more than one x-chunk, a padded
+    embed K, a padded fc width and the slow fc GEMM (the table itself is checked against the engine in the GPU test below)."""
+    assert sorted(PATHS) == sorted(CASES)
+    for prec in ("fp32", "bf16"):
+        rows = [paths(n, prec) for n in CASES]
+        for key in ("patchify_rows", "unpatchify_lds"):
+            assert {r[key] for r in rows} == {0, 1}, (prec, key)
+        assert any(r["unpatchify_chunks"] > 1 for r in rows), prec
+        assert any(r["k0_padded"] > r["k0"] for r in rows), prec
+        assert any(r["nfc_padded"] > r["nfc"] for r in rows), prec
+        assert any(r["fc_dma"] == 0 for r in rows), prec
+    for n in CASES:                                                     # the geometry columns against the config
+        cfg = named_fuxi_config(n)
+        for prec in ("fp32", "bf16"):
+            r = paths(n, prec)
+            assert r["k0"] == cfg.in_chans * cfg.frames * cfg.patch_height * cfg.patch_width
+            assert r["nfc"] == cfg.out_chans * cfg.patch_height * cfg.patch_width
+            kq = 16 if prec == "fp32" else 32
+            assert r["k0_padded"] == -(-r["k0"] // kq) * kq and r["nfc_padded"] == -(-r["nfc"] // 8) * 8
+        assert cfg.patches[0] * cfg.patches[1] <= 560                   # every GPU case stays a model of at most 560 patch tokens
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", CASES)
+def test_hip_fuxi_runs_the_paths_of_the_table(name, prec):
+    cfg, sd, x, _ = case(name)
+    m = build(cfg, sd, prec)
+    m(torch.from_numpy(x).cuda())
+    got = {k: m.query(k) for k in QUERY_KEYS}
+    print(f"\n{name} {prec}: {got}")
+    assert got == paths(name, prec)
+    from wxengine.engine import WXEngineError
+    with pytest.raises(WXEngineError):
+        m.query("no_such_key")
+
+
+def host_patches(x, cfg):
+    """x [C, T, H, W] -> [Hp, Wp, K0], column ((c T + t) ph + py) pw + px = x[c, t, y ph + py, x pw + px]: the Conv3d weight's flatten order."""
+    c, t, (hp, wp), ph, pw = cfg.in_chans, cfg.frames, cfg.patches, cfg.patch_height, cfg.patch_width
+    return x.reshape(c, t, hp, ph, wp, pw).permute(2, 4, 0, 1, 3, 5).reshape(hp, wp, c * t * ph * pw)
+
+
+def host_unpatchify(f, cfg):
+    """fc output [Hp, Wp, Nfc] -> [C_out, H, W] as fuxi.py:485-488: reshape(Lat, Lon, p_lat, p_lon, C), then the two permutes."""
+    (hp, wp), ph, pw = cfg.patches, cfg.patch_height, cfg.patch_width
+    return f.reshape(hp, wp, ph, pw, cfg.out_chans).permute(4, 0, 2, 1, 3).reshape(cfg.out_chans, hp * ph, wp * pw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", CASES)
+def test_hip_fuxi_patch_reshapes_bit_for_bit(name, prec):
+    """The patch gather in front of the embed GEMM and the scatter behind fc move values and compute nothing: "patches" is the host gather
+    of x (rounded to bf16 where the model stores bf16), its pad columns are 0.0, and y is the host permutation of "fc" -- exactly."""
+    cfg, sd, x, _ = case(name)
+    # Dirty the memory the model is about to allocate: a large NaN tensor, freed and handed back to the driver.  This only makes stale
+    # NaNs in the patch rows' pad columns likely, not certain -- the allocator owes nobody those pages -- so the engine clears the
+    # buffer at creation whether or not this assertion has ever tripped.
+    junk = torch.full((32 << 20,), float("nan"), device="cuda")
+    torch.cuda.synchronize()
+    del junk
+    torch.cuda.empty_cache()
+    m = build(cfg, sd, prec)
+    xd = torch.from_numpy(x).cuda()
+    y = m(xd)[0, :, 0].cpu()
+    r = paths(name, prec)
+    want = host_patches(torch.from_numpy(x[0]), cfg)
+    if prec == "bf16":
+        want = want.to(torch.bfloat16).float()
+    p = torch.from_numpy(m.debug_map("patches"))
+    assert p.shape == (*cfg.patches, r["k0_padded"])
+    assert torch.equal(p[..., :r["k0"]], want)
+    pad = p[..., r["k0"]:]
+    assert pad.numel() == 0 or (torch.equal(pad, torch.zeros_like(pad)) and not torch.signbit(pad).any()), "pad columns of the patch rows"
+    f = torch.from_numpy(m.debug_map("fc"))
+    assert f.shape == (*cfg.patches, r["nfc_padded"])
+    assert torch.isfinite(f).all()
+    assert torch.equal(y, host_unpatchify(f[..., :r["nfc"]], cfg))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", ["FT2", "FT4"])
+def test_hip_fuxi_misaligned_input_and_output(name, prec):
+    """x and out one float past a 16-byte boundary (contiguous views into larger buffers): the row gather's float4 loads do not apply, the
+    generic gather serves the call, and the result is the aligned call's bit for bit."""
+    cfg, sd, x, _ = case(name)
+    m = build(cfg, sd, prec)
+    xd = torch.from_numpy(x).cuda()
+    assert xd.data_ptr() % 16 == 0
+    y = m(xd)
+    assert m.query("patchify_rows") == paths(name, prec)["patchify_rows"]
+    p = m.debug_map("patches")
+    xbuf = torch.empty(xd.numel() + 1, dtype=torch.float32, device="cuda")
+    xm = xbuf[1:].view(xd.shape)
+    xm.copy_(xd)
+    obuf = torch.full((y.numel() + 2,), 7.0, dtype=torch.float32, device="cuda")
+    om = obuf[1:-1].view(y.shape)
+    assert xm.is_contiguous() and om.is_contiguous() and xm.data_ptr() % 16 == 4 and om.data_ptr() % 16 == 4
+    ym = m(xm, om)
+    assert ym.data_ptr() == om.data_ptr()
+    assert m.query("patchify_rows") == 0
+    assert torch.equal(ym, y)
+    assert np.array_equal(m.debug_map("patches"), p)
+    assert obuf[0].item() == 7.0 and obuf[-1].item() == 7.0               # nothing written outside the view
+    m(xd)                                                               # and the choice is per call
+    assert m.query("patchify_rows") == paths(name, prec)["patchify_rows"]
 
 
 @pytest.mark.gpu

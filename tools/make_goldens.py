@@ -425,8 +425,12 @@ def attend_golden():
     np.savez_compressed(os.path.join(GOLD, "attend.npz"), **out)
 
 
-def fuxi_golden():
-    """BASELINE config 5: the FuXi forward through the reference's own modules (credit/models/fuxi.py): `CubeEmbedding`, `DownBlock`,
+FUXI_CASES = ("FT0", "FT1", "FT2", "FT3", "FT4", "FT5", "FT6", "FT7")
+
+
+def fuxi_golden(names=FUXI_CASES):
+    """`--only fuxi` writes every case, `--only fuxi:FT3+FT4` only the named ones (the other golden files stay as they are).
+    BASELINE config 5: the FuXi forward through the reference's own modules (credit/models/fuxi.py): `CubeEmbedding`, `DownBlock`,
     `UpBlock`, `get_pad2d`, `UTransformer.forward`, `Fuxi.forward`, `apply_spectral_norm`, the two classes built without their
     constructors (which need timm) and populated with exactly the attributes those constructors set.  In the place of timm's
     `SwinTransformerV2Stage` (not vendored, not pinned: SURVEY.md 8(c)) sits a stage of the reference's OWN V2-Cr blocks
@@ -484,7 +488,9 @@ def fuxi_golden():
                 x = b(x)
             return x
 
-    for name in ("FT0", "FT1", "FT2"):
+    for name in names:
+        if name not in FUXI_CASES:
+            raise KeyError(f"fuxi golden: no case named {name}")
         cfg = named_fuxi_config(name)
         img = (cfg.frames, cfg.image_height, cfg.image_width)
         patch = (cfg.frame_patch_size, cfg.patch_height, cfg.patch_width)
@@ -1533,6 +1539,8 @@ def main():
             swin_block_golden()
         elif item == "fuxi":
             fuxi_golden()
+        elif item.startswith("fuxi:"):   # named cases only, joined with "+"
+            fuxi_golden(tuple(item[len("fuxi:"):].split("+")))
         elif item == "attend":
             attend_golden()
         elif item == "rollC1":      # BASELINE config 2: 24-step rollout on the 1-degree grid
