@@ -394,7 +394,7 @@ struct wx_metrics {
 int wx_metrics_create(int H, int W, const float* lat_w, int device, wx_metrics_handle* out) {
   return guarded([&] {
     if (!out) throw wx::ConfigError("wx_metrics_create: null argument");
-    const std::string why = wx::metrics_check_create(H, W, lat_w);   // needs no device to be told
+    const std::string why = wx::grid_check(H, W, lat_w);   // needs no device to be told
     if (!why.empty()) throw wx::ConfigError("wx_metrics_create: " + why);
     need_device(device, "wx_metrics_create");
     std::unique_ptr<wx_metrics> h(new wx_metrics);

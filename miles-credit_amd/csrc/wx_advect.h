@@ -276,13 +276,7 @@ class Advect {
     const std::string why = advect_build_tracers(t, n_tracers, src, bstride, dst, batch, lhw);
     if (!why.empty()) throw std::runtime_error("wx_advect_apply: " + why);
     WX_HIP(hipSetDevice(device));
-    const size_t want = (size_t)batch * lhw;
-    if (want > vel_records) {   // scratch sized by the batch seen so far (release waits for the kernels that still read the old one)
-      vel_records = 0;
-      mem.release(vel);
-      vel = (float4*)mem.alloc(want * sizeof(float4));
-      vel_records = want;
-    }
+    mem.grow(vel, vel_records, (size_t)batch * lhw);   // scratch sized by the batch seen so far
     const int64_t cols = (int64_t)batch * geom.H * geom.W;
     hipLaunchKernelGGL(advect_velocity_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, stream, u, u_bs, v, v_bs, sp, sp_bs,
                        omega, om_bs, vel, geom, tab, batch);

@@ -295,6 +295,17 @@ class DeviceArena {
     p = nullptr;
     WX_HIP(hipFree(old));
   }
+  // grow-only scratch of `have` elements: afterwards p holds at least `want` (the old contents are not kept).  `have` is cleared
+  // before the release: should hipFree or hipMalloc throw, the caller is left with (null, 0) and the next call allocates again,
+  // instead of a size that outlived its buffer.  release waits for the kernels that still read the old buffer.
+  template <typename T>
+  void grow(T*& p, size_t& have, size_t want) {
+    if (want <= have) return;
+    have = 0;
+    release(p);
+    p = (T*)alloc(want * sizeof(T));
+    have = want;
+  }
 
  private:
   int device_;

@@ -25,13 +25,12 @@
 // Optional maps [B][L][T][H][W] float32 from the same pass: ens_mean = y + mean_d, ens_std = sqrt(ss / (M - 1)), ens_abs_err = |err|,
 // crps = skill / M - pair / M^2, fair_crps = skill / M - pair / (M (M - 1)), afcrps = skill / M - (1 - (1 - alpha) / M) pair / (M (M - 1)).
 //
-// Reproducibility: the scheme of wx_metrics.h.  A workgroup owns one tile (variable, plane, block of rows), reduces it in a fixed
-// order and writes its six sums to its own slot of the handle's slab; the finish launch -- one wave per plane -- adds the plane's
-// slots in a fixed order.  No floating-point atomics; a plane's tiles depend on the grid alone, so repeated calls and any grouping
-// of variables into calls give identical bits, with maps or without -- as long as the variable takes the same load path: the
-// vector path gives a thread 4 (or 2) neighbouring points, the scalar path one, so the order of the in-tile sums differs between
-// them, and a layout or slice that changes the 16-byte alignment of a variable changes the last bits of its sums (not its maps).
-// Two launches per call.
+// Reproducibility.  Every sum is made in the fixed order of wx_reduce.h.  A workgroup owns one tile (variable, plane, block of rows)
+// and writes its six sums to its own slot of the handle's slab; the finish launch -- one wave per plane -- adds the plane's slots.
+// A plane's tiles depend on the grid alone, so repeated calls and any grouping of variables into calls give identical bits, with
+// maps or without -- as long as the variable takes the same load path: the vector path gives a thread 4 (or 2) neighbouring points,
+// the scalar path one, so the order of the in-tile sums differs between them, and a layout or slice that changes the 16-byte
+// alignment of a variable changes the last bits of its sums (not its maps).  Two launches per call.
 //
 // Layout.  Variable v, member m, batch item b at member[v * M + m] + b * member_bs[v], [L][T][H][W] contiguous, read in place (the
 // per-member buffers of ensemble_rollout, or the reference's [B * M, ...] tensor with pointer x[m] and batch stride M * stride(0)).
@@ -48,6 +47,7 @@
 #include <vector>
 
 #include "wx_common.h"
+#include "wx_reduce.h"
 
 namespace wx {
 
@@ -55,9 +55,6 @@ constexpr int kEnsMaxMembers = 64;
 constexpr int kEnsMaxVars = 32;
 constexpr int kEnsSums = 6;               // w skill, w pair, w err^2, w |err|, w ss, w sqrt(ss / (M - 1))
 constexpr int kEnsMaps = 6;               // ens_mean, ens_std, ens_abs_err, crps, fair_crps, afcrps
-constexpr int kEnsTileRows = 8;           // at most; fewer where rows * W would pass kEnsTileElems
-constexpr int kEnsTileElems = 8192;
-constexpr int kEnsThreads = 256;
 constexpr int kEnsRing = 4;               // pinned host slots of the pointer table
 
 struct EnsVar {
@@ -71,7 +68,8 @@ struct EnsVar {
 struct EnsArgs {
   EnsVar v[kEnsMaxVars];
   const float* w;          // device [H], or null
-  int n_vars, M, H, W, rows, row_blocks;
+  int n_vars, M;
+  RowTiles g;
   float alpha;
 };
 
@@ -79,13 +77,8 @@ struct EnsArgs {
 // "" or the reason wx_ensemble_create refuses
 inline std::string ensemble_check_create(int H, int W, const float* lat_w, int n_members) {
   if (n_members < 2 || n_members > kEnsMaxMembers) return "2.." + std::to_string(kEnsMaxMembers) + " members";
-  if (H < 1 || W < 1 || (int64_t)H * W > 2147483647LL) return "bad geometry";
-  if (lat_w)
-    for (int h = 0; h < H; ++h)
-      if (!std::isfinite(lat_w[h])) return "non-finite latitude weight at row " + std::to_string(h);
-  return "";
+  return grid_check(H, W, lat_w);
 }
-inline int ensemble_tile_rows(int H, int W) { return std::max(1, std::min(std::min(kEnsTileRows, H), kEnsTileElems / W)); }
 inline int ensemble_padded_members(int M) { return M <= 4 ? 4 : M <= 8 ? 8 : M <= 16 ? 16 : M <= 32 ? 32 : 64; }
 
 // ---- device side -------------------------------------------------------------------------------------------------------------------
@@ -141,7 +134,7 @@ __device__ __forceinline__ void ens_tile(const float* const* __restrict__ member
   const Acc inv_m = (Acc)1 / Mf, inv_m2 = (Acc)1 / (Mf * Mf), inv_mm1 = (Acc)1 / (Mf * (Mf - (Acc)1)), inv_dof = (Acc)1 / (Mf - (Acc)1);
   const Acc af = ((Acc)1 - ((Acc)1 - (Acc)alpha) / Mf) * inv_mm1;
   const float inf = __builtin_inff();
-  for (int i = threadIdx.x; i < n / NP; i += kEnsThreads) {
+  for (int i = threadIdx.x; i < n / NP; i += kTileThreads) {
     const int p0 = i * NP;
     float y[NP];
     ens_load<NP>(truth + p0, y);
@@ -212,75 +205,46 @@ __device__ __forceinline__ void ens_tile(const float* const* __restrict__ member
 
 // grid = total tiles.  table: per variable M member pointers, then kEnsMaps map pointers (null: not wanted).
 template <int MP>
-__global__ __launch_bounds__(kEnsThreads) void ens_tile_kernel(const EnsArgs a, const float* const* __restrict__ table,
-                                                               double* __restrict__ slab) {
-  __shared__ float s_w[kEnsTileRows];
-  __shared__ double s_red[kEnsThreads / 64][kEnsSums];
+__global__ __launch_bounds__(kTileThreads) void ens_tile_kernel(const EnsArgs a, const float* const* __restrict__ table,
+                                                                double* __restrict__ slab) {
+  __shared__ float s_w[kTileRows];
+  __shared__ double s_red[kTileThreads / 64][kEnsSums];
   const int tile = blockIdx.x;
   int vi = 0;
   while (vi + 1 < a.n_vars && tile >= a.v[vi + 1].tile0) ++vi;
   const EnsVar& v = a.v[vi];
-  const int local = tile - v.tile0;
-  const int plane = local / a.row_blocks, rb = local - plane * a.row_blocks;
-  const int h0 = rb * a.rows;
-  const int rows = min(a.rows, a.H - h0);
-  if (threadIdx.x < kEnsTileRows) s_w[threadIdx.x] = (a.w && (int)threadIdx.x < rows) ? a.w[h0 + threadIdx.x] : 1.f;
-  __syncthreads();
+  const RowTile rt = row_tile(tile - v.tile0, a.g);
+  stage_row_weights(s_w, a.w, rt.h0, rt.rows);
   const int lt = v.L * v.T;
-  const int b = plane / lt, r = plane - b * lt;        // r = l * T + t
-  const int64_t hw = (int64_t)a.H * a.W;
-  const int64_t in_plane = (int64_t)h0 * a.W;
+  const int b = rt.plane / lt, r = rt.plane - b * lt;  // r = l * T + t
+  const int64_t hw = (int64_t)a.g.H * a.g.W;
   const float* const* members = table + (size_t)vi * (a.M + kEnsMaps);
   float* const* maps = const_cast<float* const*>(reinterpret_cast<const float* const*>(members + a.M));
   bool any_map = false;
 #pragma unroll
   for (int k = 0; k < kEnsMaps; ++k) any_map = any_map || maps[k] != nullptr;
-  const float* truth = v.target + b * v.target_bs + r * hw + in_plane;
-  const int64_t member_off = b * v.member_bs + r * hw + in_plane;
-  const int64_t map_off = (int64_t)plane * hw + in_plane;
-  const int n = rows * a.W;
+  const float* truth = v.target + b * v.target_bs + r * hw + rt.offset;
+  const int64_t member_off = b * v.member_bs + r * hw + rt.offset;
+  const int64_t map_off = (int64_t)rt.plane * hw + rt.offset;
 
   double acc[kEnsSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   constexpr int NPV = MP <= 16 ? 4 : MP == 32 ? 2 : 1;
-  if (NPV > 1 && v.vec) ens_tile<MP, NPV>(members, maps, any_map, truth, member_off, map_off, n, a.M, a.W, a.alpha, s_w, acc);
-  else ens_tile<MP, 1>(members, maps, any_map, truth, member_off, map_off, n, a.M, a.W, a.alpha, s_w, acc);
-  // the tile's sums in a fixed order: a shuffle tree per wave, then the waves in order
-#pragma unroll
-  for (int k = 0; k < kEnsSums; ++k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kEnsSums; ++k) s_red[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kEnsSums) {
-    double s = s_red[0][threadIdx.x];
-    for (int wv = 1; wv < kEnsThreads / 64; ++wv) s += s_red[wv][threadIdx.x];
-    slab[(size_t)tile * kEnsSums + threadIdx.x] = s;
-  }
+  if (NPV > 1 && v.vec) ens_tile<MP, NPV>(members, maps, any_map, truth, member_off, map_off, rt.n, a.M, a.g.W, a.alpha, s_w, acc);
+  else ens_tile<MP, 1>(members, maps, any_map, truth, member_off, map_off, rt.n, a.M, a.g.W, a.alpha, s_w, acc);
+  const double s = block_sum_waves<kEnsSums, kTileThreads>(acc, s_red);
+  if (threadIdx.x < kEnsSums) slab[(size_t)tile * kEnsSums + threadIdx.x] = s;
 }
 
-// grid = total planes, one wave each: the plane's row blocks added in a fixed order (lane-strided, then a shuffle tree)
+// grid = total planes, one wave each: the plane's row blocks added lane-strided, then over the wave
 __global__ __launch_bounds__(64) void ens_finish_kernel(const EnsArgs a, const double* __restrict__ slab, double* __restrict__ planes) {
   const int plane = blockIdx.x;
   int vi = 0;
   while (vi + 1 < a.n_vars && plane >= a.v[vi + 1].plane0) ++vi;
   const EnsVar& v = a.v[vi];
-  const size_t tile0 = (size_t)v.tile0 + (size_t)(plane - v.plane0) * a.row_blocks;
+  const size_t tile0 = (size_t)v.tile0 + (size_t)(plane - v.plane0) * a.g.row_blocks;
   double acc[kEnsSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < a.row_blocks; i += 64) {
-    const double* s = slab + (tile0 + i) * kEnsSums;
-#pragma unroll
-    for (int k = 0; k < kEnsSums; ++k) acc[k] += s[k];
-  }
-#pragma unroll
-  for (int k = 0; k < kEnsSums; ++k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-  }
+  sum_slots<kEnsSums, 64>(slab + tile0 * kEnsSums, a.g.row_blocks, acc);
+  wave_sum<kEnsSums>(acc);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kEnsSums; ++k) planes[(size_t)plane * kEnsSums + k] = acc[k];
@@ -289,11 +253,9 @@ __global__ __launch_bounds__(64) void ens_finish_kernel(const EnsArgs a, const d
 
 class Ensemble {
  public:
-  Ensemble(int H_, int W_, const float* lat_w, int n_members, int dev) : H(H_), W(W_), M(n_members), device(dev), mem(dev) {
+  Ensemble(int H, int W, const float* lat_w, int n_members, int dev) : g(row_tiles(H, W)), M(n_members), device(dev), mem(dev) {
     WX_HIP(hipSetDevice(device));
     if (lat_w) w = mem.upload(lat_w, (size_t)H);
-    rows = ensemble_tile_rows(H, W);
-    row_blocks = (H + rows - 1) / rows;
     for (int i = 0; i < kEnsRing; ++i) WX_HIP(hipEventCreateWithFlags(&ring_done[i], hipEventDisableTiming));
   }
   Ensemble(const Ensemble&) = delete;
@@ -318,8 +280,8 @@ class Ensemble {
     EnsArgs a;
     std::memset(&a, 0, sizeof(a));
     int64_t tiles = 0, nplanes = 0;
-    const bool row_vec = W % 4 == 0;
-    const int64_t hw = (int64_t)H * W;
+    const bool row_vec = g.W % 4 == 0;
+    const int64_t hw = (int64_t)g.H * g.W;
     auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     struct Range { uintptr_t lo, hi; };
     std::vector<Range> inputs, outputs;
@@ -354,11 +316,11 @@ class Ensemble {
       }
       v.vec = vec ? 1 : 0;
       const int64_t np = (int64_t)batch * v.L * v.T;
-      if (tiles + np * row_blocks > 2147483647LL) throw std::runtime_error("wx_ensemble_apply: B * n_levels * n_time * row blocks exceeds 2^31 - 1 tiles");
+      if (tiles + np * g.row_blocks > 2147483647LL) throw std::runtime_error("wx_ensemble_apply: B * n_levels * n_time * row blocks exceeds 2^31 - 1 tiles");
       v.tile0 = (int)tiles;
       v.plane0 = (int)nplanes;
       v.nplanes = (int)np;
-      tiles += np * row_blocks;
+      tiles += np * g.row_blocks;
       nplanes += np;
     }
     for (size_t i = 0; i < outputs.size(); ++i) {
@@ -371,15 +333,10 @@ class Ensemble {
         throw std::runtime_error("wx_ensemble_apply: a map overlaps the plane table");
     }
     a.w = w;
-    a.n_vars = n_vars; a.M = M; a.H = H; a.W = W; a.rows = rows; a.row_blocks = row_blocks;
+    a.n_vars = n_vars; a.M = M; a.g = g;
     a.alpha = (float)alpha;
     WX_HIP(hipSetDevice(device));
-    if (tiles > slab_tiles) {      // grows only; hipFree waits for the launches that still read the old slab
-      slab_tiles = 0;
-      mem.release(slab);
-      slab = (double*)mem.alloc(sizeof(double) * kEnsSums * (size_t)tiles);
-      slab_tiles = tiles;
-    }
+    mem.grow(slab, slab_doubles, (size_t)tiles * kEnsSums);
     if (host.size() > table_cap) {  // grows only, to the full 32 variables at once: at most one growth per handle
       for (int i = 0; i < kEnsRing; ++i) WX_HIP(hipEventSynchronize(ring_done[i]));
       table_cap = 0;
@@ -397,7 +354,7 @@ class Ensemble {
     std::memcpy(staged, host.data(), sizeof(float*) * host.size());
     WX_HIP(hipMemcpyAsync(table, staged, sizeof(float*) * host.size(), hipMemcpyHostToDevice, stream));
     WX_HIP(hipEventRecord(ring_done[slot], stream));
-    const dim3 grid((unsigned)tiles), fin((unsigned)nplanes), block(kEnsThreads);
+    const dim3 grid((unsigned)tiles), fin((unsigned)nplanes), block(kTileThreads);
     switch (ensemble_padded_members(M)) {
       case 4: hipLaunchKernelGGL(ens_tile_kernel<4>, grid, block, 0, stream, a, table, slab); break;
       case 8: hipLaunchKernelGGL(ens_tile_kernel<8>, grid, block, 0, stream, a, table, slab); break;
@@ -411,12 +368,12 @@ class Ensemble {
   int members() const { return M; }
 
  private:
-  int H, W, M, device;
-  int rows = 1, row_blocks = 1;
+  RowTiles g;
+  int M, device;
   DeviceArena mem;
   float* w = nullptr;
   double* slab = nullptr;
-  int64_t slab_tiles = 0;
+  size_t slab_doubles = 0;
   const float** table = nullptr;     // device
   const float** ring = nullptr;      // pinned host, kEnsRing slots of table_cap pointers
   size_t table_cap = 0;

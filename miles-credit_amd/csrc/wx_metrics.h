@@ -15,12 +15,10 @@
 // appears at the eight outputs only.  About 10 fp64 FMAs per 12 loaded bytes is far below the vector fp64 rate of the chip, so
 // both passes stay HBM-bound.
 //
-// Reproducibility.  No floating-point atomics and no hand-off between workgroups inside a launch.  A workgroup owns one tile
-// (variable, plane (b, l, t), block of `rows` rows), reduces it in a fixed order (thread-strided sums, a shuffle tree per wave, the
-// waves in order) and writes its sums to its own slot of a scratch slab; the finish launch -- one workgroup per variable -- adds the
-// slots of that variable in a fixed order (thread-strided, then an LDS tree).  A variable's tiles and their order depend on its own
-// shape alone, so any grouping of variables into calls gives the same bits.  Four launches per call whatever n_vars is: partials 1,
-// finish 1, partials 2, finish 2; every slot read was written by the launch before, so nothing is cleared.
+// Reproducibility.  Every sum is made in the fixed order of wx_reduce.h.  A workgroup owns one tile (variable, plane (b, l, t), block
+// of `rows` rows) and writes its sums to its own slot of a scratch slab; the finish launch -- one workgroup per variable -- adds the
+// slots of that variable.  A variable's tiles and their order depend on its own shape alone, so any grouping of variables into calls
+// gives the same bits.  Four launches per call whatever n_vars is: partials 1, finish 1, partials 2, finish 2.
 //
 // Layout.  Variable v is [B][L_v][T_v][H][W] fp32 with contiguous batch items, read in place through (pointer, batch stride), channel
 // slices included; the climatology is [L_v or 1][T_v or 1][H][W] through (pointer, level stride, time stride), shared by the batch.
@@ -35,15 +33,13 @@
 #include <string>
 
 #include "wx_common.h"
+#include "wx_reduce.h"
 
 namespace wx {
 
 constexpr int kMetricsMaxVars = 32;
 constexpr int kMetricsScores = 8;         // rmse, mse, mae, bias, r2score, log_variance_ratio, acc, activity
-constexpr int kMetricsTileRows = 8;       // at most; fewer where rows * W would pass kMetricsTileElems
-constexpr int kMetricsTileElems = 8192;
 constexpr int kMetricsSums = 6;           // slots per tile (pass 1 uses 6, pass 2 uses 5) and per variable and pass in `sums`
-constexpr int kMetricsThreads = 256;
 
 struct MetricsVar {
   const float* pred;       // batch item b at pred + b * pred_bs: [L][T][H][W]
@@ -58,20 +54,10 @@ struct MetricsVar {
 struct MetricsArgs {
   MetricsVar v[kMetricsMaxVars];
   const float* w;          // device [H], or null
-  int n_vars, B, H, W, rows, row_blocks;
+  int n_vars, B;
+  RowTiles g;
   double eps;
 };
-
-// ---- host-only helpers (no HIP call) ---------------------------------------------------------------------------------------------
-// "" or the reason wx_metrics_create refuses
-inline std::string metrics_check_create(int H, int W, const float* lat_w) {
-  if (H < 1 || W < 1 || (int64_t)H * W > 2147483647LL) return "bad geometry";
-  if (lat_w)
-    for (int h = 0; h < H; ++h)
-      if (!std::isfinite(lat_w[h])) return "non-finite latitude weight at row " + std::to_string(h);
-  return "";
-}
-inline int metrics_tile_rows(int H, int W) { return std::max(1, std::min(std::min(kMetricsTileRows, H), kMetricsTileElems / W)); }
 
 // ---- device side -------------------------------------------------------------------------------------------------------------------
 // pass 1: acc = sum w p, sum w t, sum w c, sum w d, sum w |d|, sum w d^2
@@ -110,7 +96,7 @@ __device__ __forceinline__ void metrics_tile(const float* __restrict__ p, const 
     const float4* t4 = reinterpret_cast<const float4*>(t);
     const float4* c4 = reinterpret_cast<const float4*>(c);
     const int n4 = n >> 2;
-    for (int i = threadIdx.x; i < n4; i += kMetricsThreads) {
+    for (int i = threadIdx.x; i < n4; i += kTileThreads) {
       const float4 a = p4[i], b = t4[i];
       float4 k = make_float4(0.f, 0.f, 0.f, 0.f);
       if (CLIM) k = c4[i];
@@ -121,7 +107,7 @@ __device__ __forceinline__ void metrics_tile(const float* __restrict__ p, const 
       metrics_accumulate<PASS, CLIM>(w, a.w, b.w, k.w, mu, acc);
     }
   } else {
-    for (int i = threadIdx.x; i < n; i += kMetricsThreads) {
+    for (int i = threadIdx.x; i < n; i += kTileThreads) {
       const float a = p[i], b = t[i];
       float k = 0.f;
       if (CLIM) k = c[i];
@@ -132,29 +118,23 @@ __device__ __forceinline__ void metrics_tile(const float* __restrict__ p, const 
 
 // grid = total tiles.  PASS 2 reads the variable's pass-1 sums from `sums`.
 template <int PASS>
-__global__ __launch_bounds__(kMetricsThreads) void metrics_partial_kernel(const MetricsArgs a, const double* __restrict__ sums,
-                                                                          double* __restrict__ slab) {
-  __shared__ float s_w[kMetricsTileRows];
-  __shared__ double s_red[kMetricsThreads / 64][kMetricsSums];
+__global__ __launch_bounds__(kTileThreads) void metrics_partial_kernel(const MetricsArgs a, const double* __restrict__ sums,
+                                                                       double* __restrict__ slab) {
+  __shared__ float s_w[kTileRows];
+  __shared__ double s_red[kTileThreads / 64][kMetricsSums];
   const int tile = blockIdx.x;
   int vi = 0;
   while (vi + 1 < a.n_vars && tile >= a.v[vi + 1].tile0) ++vi;
   const MetricsVar& v = a.v[vi];
-  const int local = tile - v.tile0;
-  const int plane = local / a.row_blocks, rb = local - plane * a.row_blocks;
-  const int h0 = rb * a.rows;
-  const int rows = min(a.rows, a.H - h0);
-  if (threadIdx.x < kMetricsTileRows) s_w[threadIdx.x] = (a.w && (int)threadIdx.x < rows) ? a.w[h0 + threadIdx.x] : 1.f;
-  __syncthreads();
+  const RowTile rt = row_tile(tile - v.tile0, a.g);
+  stage_row_weights(s_w, a.w, rt.h0, rt.rows);
   const int lt = v.L * v.T;
-  const int b = plane / lt, r = plane - b * lt;        // r = l * T + t
+  const int b = rt.plane / lt, r = rt.plane - b * lt;  // r = l * T + t
   const int l = r / v.T, tt = r - l * v.T;
-  const int64_t hw = (int64_t)a.H * a.W;
-  const int64_t in_plane = (int64_t)h0 * a.W;
-  const float* p = v.pred + b * v.pred_bs + r * hw + in_plane;
-  const float* t = v.target + b * v.target_bs + r * hw + in_plane;
-  const float* c = v.clim ? v.clim + l * v.clim_ls + tt * v.clim_ts + in_plane : nullptr;
-  const int n = rows * a.W;
+  const int64_t hw = (int64_t)a.g.H * a.g.W;
+  const float* p = v.pred + b * v.pred_bs + r * hw + rt.offset;
+  const float* t = v.target + b * v.target_bs + r * hw + rt.offset;
+  const float* c = v.clim ? v.clim + l * v.clim_ls + tt * v.clim_ts + rt.offset : nullptr;
 
   double mu[4] = {0.0, 0.0, 0.0, 0.0};
   if (PASS == 2) {
@@ -167,67 +147,33 @@ __global__ __launch_bounds__(kMetricsThreads) void metrics_partial_kernel(const 
   }
   double acc[kMetricsSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (v.vec) {
-    if (c) metrics_tile<PASS, true, true>(p, t, c, n, a.W, s_w, mu, acc);
-    else metrics_tile<PASS, true, false>(p, t, c, n, a.W, s_w, mu, acc);
+    if (c) metrics_tile<PASS, true, true>(p, t, c, rt.n, a.g.W, s_w, mu, acc);
+    else metrics_tile<PASS, true, false>(p, t, c, rt.n, a.g.W, s_w, mu, acc);
   } else {
-    if (c) metrics_tile<PASS, false, true>(p, t, c, n, a.W, s_w, mu, acc);
-    else metrics_tile<PASS, false, false>(p, t, c, n, a.W, s_w, mu, acc);
+    if (c) metrics_tile<PASS, false, true>(p, t, c, rt.n, a.g.W, s_w, mu, acc);
+    else metrics_tile<PASS, false, false>(p, t, c, rt.n, a.g.W, s_w, mu, acc);
   }
-  // the tile's sums in a fixed order: a shuffle tree per wave, then the waves in order
-#pragma unroll
-  for (int k = 0; k < kMetricsSums; ++k) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kMetricsSums; ++k) s_red[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kMetricsSums) {
-    double s = s_red[0][threadIdx.x];
-    for (int wv = 1; wv < kMetricsThreads / 64; ++wv) s += s_red[wv][threadIdx.x];
-    slab[(size_t)tile * kMetricsSums + threadIdx.x] = s;
-  }
-}
-
-// the variable's tiles added in a fixed order: thread-strided, then a tree over the threads.  -> the K sums in s_red[k][0]
-__device__ __forceinline__ void metrics_sum_tiles(const double* __restrict__ slab, int tile0, int ntiles,
-                                                  double (*s_red)[kMetricsThreads]) {
-  double acc[kMetricsSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < ntiles; i += kMetricsThreads) {
-    const double* s = slab + (size_t)(tile0 + i) * kMetricsSums;
-#pragma unroll
-    for (int k = 0; k < kMetricsSums; ++k) acc[k] += s[k];
-  }
-#pragma unroll
-  for (int k = 0; k < kMetricsSums; ++k) s_red[k][threadIdx.x] = acc[k];
-  __syncthreads();
-  for (int half = kMetricsThreads / 2; half >= 1; half >>= 1) {
-    if ((int)threadIdx.x < half) {
-#pragma unroll
-      for (int k = 0; k < kMetricsSums; ++k) s_red[k][threadIdx.x] += s_red[k][threadIdx.x + half];
-    }
-    __syncthreads();
-  }
+  const double s = block_sum_waves<kMetricsSums, kTileThreads>(acc, s_red);
+  if (threadIdx.x < kMetricsSums) slab[(size_t)tile * kMetricsSums + threadIdx.x] = s;
 }
 
 // grid = n_vars.  PASS 1: sums[v][0..5] = the pass-1 sums.  PASS 2: the eight scores of variable v.
 template <int PASS>
-__global__ __launch_bounds__(kMetricsThreads) void metrics_finish_kernel(const MetricsArgs a, const double* __restrict__ slab,
-                                                                         double* __restrict__ sums, float* __restrict__ scores) {
-  __shared__ double s_red[kMetricsSums][kMetricsThreads];
+__global__ __launch_bounds__(kTileThreads) void metrics_finish_kernel(const MetricsArgs a, const double* __restrict__ slab,
+                                                                      double* __restrict__ sums, float* __restrict__ scores) {
+  __shared__ double s_red[kMetricsSums][kTileThreads];
   const int vi = blockIdx.x;
   const MetricsVar& v = a.v[vi];
-  metrics_sum_tiles(slab, v.tile0, v.ntiles, s_red);
+  double acc[kMetricsSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  sum_slots<kMetricsSums, kTileThreads>(slab + (size_t)v.tile0 * kMetricsSums, v.ntiles, acc);
+  block_sum_tree<kMetricsSums>(acc, s_red);
   if (PASS == 1) {
     if (threadIdx.x < kMetricsSums) sums[(size_t)vi * kMetricsSums + threadIdx.x] = s_red[threadIdx.x][0];
     return;
   }
   if (threadIdx.x != 0) return;
   const double* s1 = sums + (size_t)vi * kMetricsSums;
-  const double inv_n = 1.0 / ((double)a.B * (double)v.L * (double)v.T * (double)a.H * (double)a.W);
+  const double inv_n = 1.0 / ((double)a.B * (double)v.L * (double)v.T * (double)a.g.H * (double)a.g.W);
   const double mse = s1[5] * inv_n, mae = s1[4] * inv_n, bias = s1[3] * inv_n;
   const double var_p = s_red[0][0] * inv_n, var_t = s_red[1][0] * inv_n;
   float* out = scores + (size_t)vi * kMetricsScores;
@@ -250,12 +196,10 @@ __global__ __launch_bounds__(kMetricsThreads) void metrics_finish_kernel(const M
 
 class Metrics {
  public:
-  Metrics(int H_, int W_, const float* lat_w, int dev) : H(H_), W(W_), device(dev), mem(dev) {
+  Metrics(int H, int W, const float* lat_w, int dev) : g(row_tiles(H, W)), device(dev), mem(dev) {
     WX_HIP(hipSetDevice(device));
     if (lat_w) w = mem.upload(lat_w, (size_t)H);
     sums = (double*)mem.alloc(sizeof(double) * kMetricsMaxVars * kMetricsSums);
-    rows = metrics_tile_rows(H, W);
-    row_blocks = (H + rows - 1) / rows;
   }
   void apply(int n_vars, const float* const* pred, const int64_t* pred_bs, const float* const* target, const int64_t* target_bs,
              const float* const* clim, const int64_t* clim_ls, const int64_t* clim_ts, const int32_t* n_levels, const int32_t* n_time,
@@ -265,7 +209,7 @@ class Metrics {
     MetricsArgs a;
     std::memset(&a, 0, sizeof(a));
     int64_t tiles = 0;
-    const bool row_vec = W % 4 == 0;
+    const bool row_vec = g.W % 4 == 0;
     auto aligned = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     for (int i = 0; i < n_vars; ++i) {
       if (!pred[i] || !target[i]) throw std::runtime_error("wx_metrics_apply: null tensor pointer");
@@ -287,23 +231,18 @@ class Metrics {
       }
       v.vec = row_vec && aligned(v.pred) && aligned(v.target) && v.pred_bs % 4 == 0 && v.target_bs % 4 == 0 &&
               (!v.clim || (aligned(v.clim) && v.clim_ls % 4 == 0 && v.clim_ts % 4 == 0));
-      const int64_t nt = (int64_t)batch * v.L * v.T * row_blocks;
+      const int64_t nt = (int64_t)batch * v.L * v.T * g.row_blocks;
       if (tiles + nt > 2147483647LL) throw std::runtime_error("wx_metrics_apply: B * n_levels * n_time * row blocks exceeds 2^31 - 1 tiles");
       v.tile0 = (int)tiles;
       v.ntiles = (int)nt;
       tiles += nt;
     }
     a.w = w;
-    a.n_vars = n_vars; a.B = batch; a.H = H; a.W = W; a.rows = rows; a.row_blocks = row_blocks;
+    a.n_vars = n_vars; a.B = batch; a.g = g;
     a.eps = eps;
     WX_HIP(hipSetDevice(device));
-    if (tiles > slab_tiles) {      // grows only; hipFree waits for the launches that still read the old slab
-      slab_tiles = 0;
-      mem.release(slab);
-      slab =(double*)mem.alloc(sizeof(double) * kMetricsSums * (size_t)tiles);
-      slab_tiles = tiles;
-    }
-    const dim3 grid((unsigned)tiles), fin((unsigned)n_vars), block(kMetricsThreads);
+    mem.grow(slab, slab_doubles, (size_t)tiles * kMetricsSums);
+    const dim3 grid((unsigned)tiles), fin((unsigned)n_vars), block(kTileThreads);
     hipLaunchKernelGGL(metrics_partial_kernel<1>, grid, block, 0, stream, a, sums, slab);
     hipLaunchKernelGGL(metrics_finish_kernel<1>, fin, block, 0, stream, a, slab, sums, scores);
     hipLaunchKernelGGL(metrics_partial_kernel<2>, grid, block, 0, stream, a, sums, slab);
@@ -312,13 +251,13 @@ class Metrics {
   }
 
  private:
-  int H, W, device;
-  int rows = 1, row_blocks = 1;
+  RowTiles g;
+  int device;
   DeviceArena mem;
   float* w = nullptr;
   double* sums = nullptr;
   double* slab = nullptr;
-  int64_t slab_tiles = 0;
+  size_t slab_doubles = 0;
 };
 
 }  // namespace wx

@@ -6,13 +6,14 @@
 //
 // Every global fixer is "column integrals -> a few area-weighted global sums -> one scalar ratio -> elementwise
 // correction".  HBM-bound integer-free float work: one thread per grid cell walks its column (loads are coalesced
-// along longitude for every level), per-cell integrals in fp32 like the reference, the global sums in fp64 with a
-// fixed two-stage order (per-workgroup partials, then one workgroup) so results are bit-reproducible, then an
-// elementwise apply kernel.  Tensors are the caller's fp32 NCHW buffers (y [C_out][H][W], x [C_in][frames][H][W]).
+// along longitude for every level), per-cell integrals in fp32 like the reference, the global sums in fp64 in the
+// fixed order of wx_reduce.h (per-workgroup partials, then one workgroup), then an elementwise apply kernel.
+// Tensors are the caller's fp32 NCHW buffers (y [C_out][H][W], x [C_in][frames][H][W]).
 #pragma once
 #include <vector>
 
 #include "wx_common.h"
+#include "wx_reduce.h"
 
 namespace wx {
 
@@ -132,13 +133,7 @@ __global__ __launch_bounds__(256) void fix_reduce_kernel(const FixParams p) {
       s[0] = (double)rt * a; s[1] = (double)fs * a; s[2] = (double)te0 * a; s[3] = (double)te1 * a;
     }
   }
-  for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = s[k];
-  __syncthreads();
-  for (unsigned o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-      for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
-    __syncthreads();
-  }
+  block_sum_tree<4>(s, sh);
   if (threadIdx.x < 4) p.partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
@@ -146,15 +141,8 @@ __global__ __launch_bounds__(256) void fix_reduce_kernel(const FixParams p) {
 __global__ __launch_bounds__(256) void fix_sum_kernel(const FixParams p) {
   __shared__ double sh[4][256];
   double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int b = threadIdx.x; b < p.n_blocks; b += 256)
-    for (int k = 0; k < 4; ++k) s[k] += p.partial[(int64_t)b * 4 + k];
-  for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] = s[k];
-  __syncthreads();
-  for (unsigned o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-      for (int k = 0; k < 4; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + o];
-    __syncthreads();
-  }
+  sum_slots<4, 256>(p.partial, p.n_blocks, s);
+  block_sum_tree<4>(s, sh);
   if (threadIdx.x < 4) p.sums[threadIdx.x] = sh[threadIdx.x][0];
 }
 // p.sums[4] (of the whole globe: under lat-band sharding the engine has added every rank's sums by now) -> correction ratio

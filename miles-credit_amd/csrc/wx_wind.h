@@ -4,8 +4,8 @@
 //                          clamp(conv2d(flag, ones[dil_lat, dil_lon], zero pad), 0, 1) (wind_filter.py:40-47) -- an OR, exact in any order
 //   2 wind_falloff_kernel  the zero-padded Gaussian falloff of the dilated mask (:51-67) -> m [B][H][W] in [0, 1]
 //   3 wind_sums_kernel     only with preserve_amplitude (:115-121): per (batch item, target plane) the sums  m f^2  and  m fs^2  in
-//                          double, one partial per strip of tile rows, no atomics; the blend launch adds the partials in strip order,
-//                          so two calls on the same input give the same bits
+//                          double, one partial per strip of tile rows in the fixed order of wx_reduce.h; the blend launch adds the
+//                          partials in strip order, so two calls on the same input give the same bits
 //   4 wind_blend_kernel    every plane (variable, level, batch item) in one grid: target planes  fs = conv2d(f, G, zero pad),
 //                          fs *= alpha = min(sqrt(sum m f^2 / (sum m fs^2 + 1e-12)), 4),  out = m fs + (1 - m) f  (:113-123, rounded
 //                          products and a rounded sum: a point with m == 0 keeps its bits); every other plane is copied
@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "wx_common.h"
+#include "wx_reduce.h"
 
 namespace wx {
 
@@ -255,7 +256,7 @@ __device__ __forceinline__ bool wind_plane(const WindVars& t, int plane, int hw,
 }
 
 // launch 3 (preserve_amplitude only): grid = batch * levels * tiles_y; partial[(plane * tiles_y + strip) * 2 + {0, 1}] = the sums of
-// m f^2 and m fs^2 over one strip of tile rows, in double, tiles and lanes added in a fixed order
+// m f^2 and m fs^2 over one strip of tile rows, in double, tiles in order, then the workgroup (wx_reduce.h)
 __global__ __launch_bounds__(256) void wind_sums_kernel(const WindVars t, const float* __restrict__ mask, double* __restrict__ partial,
                                                         WindGrid g, const float* __restrict__ w_lat, const float* __restrict__ w_lon, int k_lat,
                                                         int k_lon) {
@@ -272,27 +273,18 @@ __global__ __launch_bounds__(256) void wind_sums_kernel(const WindVars t, const 
   const float* m_plane = mask + (int64_t)b * hw;
   const bool vec_m = wind_vec(m_plane, g.W);
   const int y = strip * kWindTH + threadIdx.x / 16;
-  double num = 0.0, den = 0.0;
+  double acc[2] = {0.0, 0.0};   // num, den
   for (int tx = 0; tx < g.tiles_x; ++tx) {
     float fs[4], f[4], m[4];
     wind_conv_tile<false>(src, vec, g.H, g.W, strip * kWindTH, tx * kWindTW, w_lat, w_lon, k_lat, k_lon, wind_lds, fs, f);
     wind_load4(m_plane, vec_m, g.H, g.W, y, tx * kWindTW + (threadIdx.x % 16) * 4, m);   // 0 outside the grid: no contribution
     for (int i = 0; i < 4; ++i) {
-      num += (double)m[i] * ((double)f[i] * (double)f[i]);
-      den += (double)m[i] * ((double)fs[i] * (double)fs[i]);
+      acc[0] += (double)m[i] * ((double)f[i] * (double)f[i]);
+      acc[1] += (double)m[i] * ((double)fs[i] * (double)fs[i]);
     }
   }
-  for (int off = 32; off >= 1; off >>= 1) {
-    num += __shfl_down(num, off);
-    den += __shfl_down(den, off);
-  }
-  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = num; red[threadIdx.x >> 6][1] = den; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double* p = partial + ((int64_t)plane * g.tiles_y + strip) * 2;
-    p[0] = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-    p[1] = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-  }
+  const double s = block_sum_waves<2, 256>(acc, red);
+  if (threadIdx.x < 2) partial[((int64_t)plane * g.tiles_y + strip) * 2 + threadIdx.x] = s;
 }
 
 // m fs + (1 - m) f as torch evaluates it: three rounded products / differences and a rounded sum; m == 0 returns f's bits
@@ -370,8 +362,8 @@ class Wind {
     WX_HIP(hipSetDevice(device));
     const int64_t planes = (int64_t)batch * t.lvl0[n_vars];
     const size_t hw = (size_t)H * W;
-    grow(dil, dil_floats, (size_t)batch * hw);
-    if (!mask_out) grow(mask, mask_floats, (size_t)batch * hw);
+    mem.grow(dil, dil_floats, (size_t)batch * hw);
+    if (!mask_out) mem.grow(mask, mask_floats, (size_t)batch * hw);
     float* m = mask_out ? mask_out : mask;
     const size_t lds_d = wind_lds_floats(dil_lat, dil_lon) * sizeof(float), lds_f = wind_lds_floats(k[2], k[3]) * sizeof(float),
                  lds_s = wind_lds_floats(k[0], k[1]) * sizeof(float);
@@ -379,7 +371,7 @@ class Wind {
                        grid, dil_lat, dil_lon);
     hipLaunchKernelGGL(wind_falloff_kernel, dim3((unsigned)(batch * tiles)), dim3(256), lds_f, stream, dil, m, grid, wdev[2], wdev[3], k[2], k[3]);
     if (preserve) {
-      grow(partial, partial_doubles, (size_t)planes * grid.tiles_y * 2);
+      mem.grow(partial, partial_doubles, (size_t)planes * grid.tiles_y * 2);
       hipLaunchKernelGGL(wind_sums_kernel, dim3((unsigned)(planes * grid.tiles_y)), dim3(256), lds_s, stream, t, m, partial, grid, wdev[0],
                          wdev[1], k[0], k[1]);
     }
@@ -399,16 +391,7 @@ class Wind {
   WindGrid grid;
   float *dil = nullptr, *mask = nullptr;
   double* partial = nullptr;
-  size_t dil_floats = 0, mask_floats = 0, partial_doubles = 0;
-  // scratch sized by the batch seen so far (release is a plain hipFree, which waits for the kernels that still read the old buffer)
-  template <typename T>
-  void grow(T*& p, size_t& have, size_t want) {
-    if (want <= have) return;
-    have = 0;
-    mem.release(p);
-    p = (T*)mem.alloc(want * sizeof(T));
-    have = want;
-  }
+  size_t dil_floats = 0, mask_floats = 0, partial_doubles = 0;   // scratch sized by the batch seen so far
 };
 
 }  // namespace wx

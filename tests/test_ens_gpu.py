@@ -227,6 +227,49 @@ def test_vector_loads_of_the_4_8_and_32_member_instantiations(M):
         print(f"[ens gpu] {M} members on 8 x 64, shift {shift}: worst distance / bound {worst:.3f}")
 
 
+def test_66_row_blocks_take_the_finish_kernel_round_its_loop_twice():
+    """The finish launch adds a plane's row blocks 64 at a time; no fixture has more than five.  521 x 4 with 3 members is 66 blocks
+    of 8 rows, the last of one row, and W % 4 == 0: an aligned view takes the 16-byte loads, a one-float-shifted one the scalar
+    loads.  Scalars and maps, with latitude weights, are held to the restatement on the same tensors under the gate, d_ref being the
+    restatement's own fp32-against-fp64 distance."""
+    from wxengine.ensemble_metrics import EnsembleVerification
+    M, H, W = 3, 521, 4
+    g = np.random.Generator(np.random.Philox(key=[2031, 66]))
+    key, shape = EC.KEYS["unit"], (1, 1, 1, H, W)
+    t, x = EC._field("unit", g, M, shape)
+    t, x = t.astype(np.float32), x.astype(np.float32)
+    w = EO.lat_weights(EC.latitude(H))
+    r32, m32 = EO.restate({key: torch.from_numpy(x)}, {key: torch.from_numpy(t)}, 0.9, w, torch.float32)
+    r64, m64 = EO.restate({key: torch.from_numpy(x)}, {key: torch.from_numpy(t)}, 0.9, w, torch.float64)
+    w32, w64 = EC.flat_scalars(r32), EC.flat_scalars(r64)
+    v = EnsembleVerification(M, alpha=0.9, maps=EC.MAPS, use_latitude_weights=True, latitude=EC.latitude(H))
+    for shift in (0, 1):
+        flat = torch.zeros((M + 1) * t.size + 8, device="cuda")
+        views = [flat[4 + shift + i * t.size:4 + shift + (i + 1) * t.size].view(shape) for i in range(M + 1)]
+        assert (views[0].data_ptr() % 16 == 0) == (shift == 0)
+        for dst, src in zip(views, [t] + list(x)):
+            dst.copy_(torch.from_numpy(src))
+        got = v([{key: m} for m in views[1:]], {key: views[0]})
+        flat_got = EC.flat_scalars(got)
+        assert list(flat_got) == list(w64)
+        worst = 0.0
+        for k in flat_got:
+            scale = abs(w64[k])
+            b32, b64 = EC.gate(EC.distance(w32[k], w64[k], scale))
+            d32, d64 = EC.distance(flat_got[k], w32[k], scale), EC.distance(flat_got[k], w64[k], scale)
+            worst = max(worst, d32 / b32, d64 / b64)
+            assert d32 <= b32 and d64 <= b64, (shift, k, flat_got[k], w32[k], w64[k])
+        for m in EC.MAPS:
+            dev = (got.reference_ens_std(key) if m == "ens_std" else got.maps[m][key]).cpu().numpy()
+            a32, a64 = m32[m][key].numpy(), m64[m][key].numpy()
+            scale = float(np.abs(m64["ens_abs_err"][key].numpy()).mean()) if m == "ens_mean" else float(np.abs(a64).mean())
+            b32, b64 = EC.gate(EC.map_distance(a32, a64, scale))
+            d32, d64 = EC.map_distance(dev, a32, scale), EC.map_distance(dev, a64, scale)
+            worst = max(worst, d32 / b32, d64 / b64)
+            assert d32 <= b32 and d64 <= b64, (shift, m, d32, b32, d64, b64)
+        print(f"[ens gpu] 66 row blocks on 521 x 4, shift {shift}: worst distance / bound {worst:.3f}")
+
+
 def test_rejections_at_call_carry_their_reason(runs):
     from wxengine.engine import WXEngineError
     r = runs["m2"]

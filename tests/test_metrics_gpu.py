@@ -173,6 +173,35 @@ def test_16_byte_and_scalar_loads_on_a_32_x_64_crop(runs, case, shift):
     print(f"[metrics gpu] {case} 32 x 64 crop, shift {shift}: worst distance / bound {worst:.3f}")
 
 
+def test_274_tiles_of_one_variable_take_the_finish_kernel_round_its_loop_twice():
+    """The finish launch adds a variable's tiles 256 at a time; the fixtures stop at 137 (`deep` in `many`).  137 levels x B = 2 on
+    7 x 19 is 274 tiles, one row block per plane.  All eight scores, with a per-level climatology and latitude weights, are held to
+    the restatement on the same tensors under the gate, d_ref being the restatement's own fp32-against-fp64 distance."""
+    from wxengine.metrics import CombinedMetric
+    H, W, L, B = 7, 19, 137, 2
+    g = np.random.Generator(np.random.Philox(key=[2029, 274]))
+    c, t, p = MC._field("T", g, (L, 1, H, W), (B, L, 1, H, W))
+    key = MC.KEYS["deep"]
+    clim = {key: np.ascontiguousarray(c.astype(np.float32).reshape(L, H, W))}
+    kw = dict(metrics={m: ({"climatology": clim} if m in ("acc", "activity") else {}) for m in MC.ALL8}, var_weighting="none",
+              use_latitude_weights=True, latitude=MC.latitude(H))
+    cpu = {"y_processed": {MC.SRC: {key: torch.from_numpy(p.astype(np.float32))}},
+           "y_target_processed": {MC.SRC: {key: torch.from_numpy(t.astype(np.float32))}}}
+    got = CombinedMetric(**kw)({s: {MC.SRC: {k: v.cuda() for k, v in cpu[s][MC.SRC].items()}} for s in cpu})
+    m32, m64 = MO.Restatement(dtype=torch.float32, **kw), MO.Restatement(dtype=torch.float64, **kw)
+    w32 = m32(cpu)
+    w64 = m64({s: {MC.SRC: {k: v.double() for k, v in cpu[s][MC.SRC].items()}} for s in cpu}, all_scores=True)
+    sc = MC.scales(m64.last_all_scores, m64.weights, m64.var_keys)
+    assert list(got) == list(w64) and {f"{m}/{key}" for m in MC.ALL8} <= set(got)
+    worst = 0.0
+    for k in got:
+        b32, b64 = MC.gate(MC.distance(w32[k], w64[k], sc[k]))
+        d32, d64 = MC.distance(got[k], w32[k], sc[k]), MC.distance(got[k], w64[k], sc[k])
+        worst = max(worst, d32 / b32, d64 / b64)
+        assert d32 <= b32 and d64 <= b64, (k, got[k], w32[k], w64[k], d32, b32, d64, b64)
+    print(f"[metrics gpu] 274 tiles of one variable: worst distance / bound {worst:.3f}")
+
+
 def test_rejections_at_call_carry_their_reason(runs):
     from wxengine.engine import WXEngineError
     r = runs["sp2d"]
