@@ -670,13 +670,21 @@ int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts);
  * wx_debug_read: copy an intermediate activation of the LAST forward (batch item 0) to host as
  *   float32 [C, H, W].  Names follow the reference module tree: "pad", "layers.S.0", "layers.S.1",
  *   "layers.S.1.layers.D.J", "up_block1".."up_block4".  Only valid after
- *   wx_set_debug(h, 1) and a forward.
+ *   wx_set_debug(h, level) and a forward.  level 1: every name above exists -- the engine leaves the routes whose intermediates
+ *   never reach memory (the FeedForward launches that take the attention's out-projection in front / the next to_qkv behind,
+ *   the k-blocked attention chain) for their unfused forms.  level 2: the engine runs exactly the kernels it runs with
+ *   captures off and captures what those leave in memory: a name whose tensor does not exist on the route taken (the attention
+ *   sub-block's output "...D.0" / "...D.2" in front of a FeedForward that took the out-projection) is reported missing;
+ *   "<attention>.attn" (the attention output in front of to_out) and "<attention>.qkv" (q|k|v, [3C, H, W]; bf16 engine: the q
+ *   channels carry dim_head^-0.5 * log2(e)) are captured wherever they are row-major in memory -- not in the k-blocked chain
+ *   nor inside the one-launch attention block.  Level 2 changes no arithmetic: the forward is bit-identical to level 0's.
+ *   level 0: off.  No forward is captured into a graph while a level is on.
  * wx_profile: when enabled, every kernel launch is bracketed by HIP events on the launch stream;
  *   wx_profile_read returns per-kernel-class totals since the last wx_profile_reset.  enable: 1 per class ("gemm_ff1"),
  *   2 per class and stage ("gemm_ff1.s2"), 3 additionally tags launches that took a non-default kernel family
  *   ("gemm_ff1.s2@stream": the persistent GEMM) -- what the parity tests use to prove which kernel they exercised.
  */
-int wx_set_debug(wx_handle h, int enable);
+int wx_set_debug(wx_handle h, int level);
 int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]);
 
 typedef struct wx_kernel_stat {

@@ -211,7 +211,7 @@ int wx_set_noise(wx_handle h, uint64_t seed, int member0, int step) {
 int wx_set_noise_tape(wx_handle h, const float* const* draws, int n) {
   return guarded([&] { need(h, "null engine handle"); h->impl->set_noise_tape(draws, n); });
 }
-int wx_set_debug(wx_handle h, int enable) { return guarded([&] { need(h, "null engine handle"); h->impl->set_debug(enable); }); }
+int wx_set_debug(wx_handle h, int level) { return guarded([&] { need(h, "null engine handle"); h->impl->set_debug(level); }); }
 int wx_debug_read(wx_handle h, const char* name, float* host_out, int64_t capacity, int64_t shape[3]) {
   return guarded([&] { need(h, "null engine handle"); if (!name || !shape) throw wx::ConfigError("wx_debug_read: null argument"); h->impl->debug_read(name, host_out, capacity, shape); });
 }

@@ -487,10 +487,17 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
                        have_denorm ? d_std : nullptr, y_phys, x_next, n_prog < 0 ? 0 : n_prog, d_xmap);
     WX_HIP(hipGetLastError());
   }
-  bool dbg_on = false;
+  // capture level (wx_set_debug): 1 = every activation the reference names, so the routes whose intermediates never reach memory
+  // (PRE / POST FeedForward forms, the k-blocked attention chain) step aside; 2 = whatever the default routes leave in memory, the
+  // routes themselves untouched
+  bool dbg_on = false, dbg_unfuse = false;   // any level; level 1
   struct DbgT { int64_t c, h, w; std::vector<float> data; };
   std::map<std::string, DbgT> dbg;
-  void set_debug(int on) override { dbg_on = on != 0; if (!dbg_on) dbg.clear(); }
+  void set_debug(int on) override {
+    const bool unfuse = on != 0 && on != 2;
+    if (on == 0 || unfuse != dbg_unfuse) dbg.clear();   // a level's forward must not answer with another level's captures
+    dbg_on = on != 0; dbg_unfuse = unfuse;
+  }
   void capture(const std::string& name, const T* base, int h, int w, int c, int64_t ld, int64_t row_pitch_px) {
     if (!dbg_on) return;
     WX_HIP(hipStreamSynchronize(cur_stream));
@@ -831,7 +838,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     } else {
       // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
       // k-blocked (see KBlk); outputs bitwise the row-major chain's
-      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_on && !band_on && cfg.dim_head == 32 &&
+      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_unfuse && !band_on && cfg.dim_head == 32 &&
           !qkv_ready && !defer_out && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
           m >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
         blk = KBlk::attn;
@@ -852,9 +859,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         if (cfg.dim_head == 32) launch_window_attn<T>(p, cur_stream, opt.attn_split, opt.attn_no_b2);
         else launch_window_attn_any<T>(p, cfg.dim_head, cur_stream);   // [NP][NP] bias table shared by the heads (bias_head_stride 0)
       });
-      capture(dbg_name + ".qkv", scratch, h, w, 3 * c, 3 * c, w);
+      if (blk != KBlk::attn) capture(dbg_name + ".qkv", scratch, h, w, 3 * c, 3 * c, w);   // (k-blocked: not a [tokens][3C] map)
     }
-    capture(dbg_name + ".attn", attn_o, h, w, c, c, w);
+    if (blk != KBlk::attn) capture(dbg_name + ".attn", attn_o, h, w, c, c, w);
     if (defer_out) return;
     stat_tiles_ready = gemm("gemm_out", a.out, {.in = attn_o, .in_h = h, .in_w = w, .in_ld = c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
                                                 .blk = blk, .want_stats = true}).stat_slots;
@@ -869,7 +876,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (cfg.dim[v.s] == 128 || cfg.dim[v.s] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
     return cdiv(m, 64) >= opt.ff_min_wgs;
   }
-  bool ff_takes_out(const FFL& f, const StageView& v) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_on && ff_big_enough(v) && cfg.dim_head == 32; }
+  bool ff_takes_out(const FFL& f, const StageView& v) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_unfuse && ff_big_enough(v) && cfg.dim_head == 32; }
   // split-bf16 precision: the one-launch FeedForward (wx_ff_split.h) of this layer ...
   bool ff_split_fused_ok(const FFL& f, int c) const {
     return sizeof(T) == 4 && split_mma && opt.ff_split_fused && !opt.dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || opt.ff_split_256) && f.w1.cin == c &&
@@ -879,7 +886,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // one kernel and its read by the next are gone)
   bool ff_split_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
     const int c = cfg.dim[v.s];
-    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_on && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
+    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_unfuse && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
   }
   bool ff_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
     if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a, v);
@@ -890,7 +897,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       if (!f.next) return false;
       const int c = cfg.dim[v.s];
       const ConvW& q = f.next->qkv;
-      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_on && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
+      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_unfuse && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
              q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
     }
     return ff_takes_out(f, v) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, v));

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256, OCC) void ff_fused_kernel(const FFParams p, co
 
   constexpr int NPRE = PRE ? C / 64 : 0;  // out-projection blocks ahead of the feed-forward chunks in the ring
   constexpr int NPOST = POST ? 3 * C / 64 : 0;  // to_qkv blocks behind them
-  // ---- x1 = x + Wout . o + bo (crossformer.py:314-316 to_out + the attention residual :352), kept in registers ----
+  // ---- x1 = x + Wout . o + bo (crossformer.py:314-316 to_out + the attention residual :352), kept in registers: bf16 operand + fp32 remainder ----
   uint4 ob[PRE ? KS : 1][PXF];
   if constexpr (PRE) {
 #pragma unroll
@@ -198,7 +198,10 @@ __global__ __launch_bounds__(256, OCC) void ff_fused_kernel(const FFParams p, co
       dma_wait_all();
       __syncthreads();
     }
-    // x1 -> bf16, into the x registers (accumulator layout == the permuted-k B layout); y back to zero
+    // x1 -> bf16, into the x registers (accumulator layout == the permuted-k B layout): the LayerNorm / GEMM1 operand.  What the
+    // rounding took off stays behind in y, so the epilogue's y + b2 + x adds the residual x1 UNROUNDED: x1 never reaches memory on this
+    // path, and rounding it would cost the sub-block a second 2^-9 |x1| next to the rounding of its stored output (teacher-forced
+    // out+ff link: d 0.032 - 0.043 against 0.013 for the unfused chain, whose x1 rounding belongs to the stored to_out result)
 #pragma unroll
     for (int m = 0; m < MF; ++m) {
       const float4 bb = *reinterpret_cast<const float4*>(s_b2 + C + m * 16 + 4 * g);
@@ -206,12 +209,12 @@ __global__ __launch_bounds__(256, OCC) void ff_fused_kernel(const FFParams p, co
       for (int f = 0; f < PXF; ++f) {
         uint4& xr = xb[m / 2][f];
         const uint32_t r01 = (m & 1) ? xr.z : xr.x, r23 = (m & 1) ? xr.w : xr.y;
-        const uint32_t n01 = pack_bf16x2(y[m][f][0] + bb.x + __builtin_bit_cast(float, r01 << 16),
-                                         y[m][f][1] + bb.y + __builtin_bit_cast(float, r01 & 0xffff0000u));
-        const uint32_t n23 = pack_bf16x2(y[m][f][2] + bb.z + __builtin_bit_cast(float, r23 << 16),
-                                         y[m][f][3] + bb.w + __builtin_bit_cast(float, r23 & 0xffff0000u));
+        const float t0 = y[m][f][0] + bb.x + __builtin_bit_cast(float, r01 << 16), t1 = y[m][f][1] + bb.y + __builtin_bit_cast(float, r01 & 0xffff0000u);
+        const float t2 = y[m][f][2] + bb.z + __builtin_bit_cast(float, r23 << 16), t3 = y[m][f][3] + bb.w + __builtin_bit_cast(float, r23 & 0xffff0000u);
+        const uint32_t n01 = pack_bf16x2(t0, t1), n23 = pack_bf16x2(t2, t3);
         if (m & 1) { xr.z = n01; xr.w = n23; } else { xr.x = n01; xr.y = n23; }
-        y[m][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        y[m][f] = f32x4_t{t0 - __builtin_bit_cast(float, n01 << 16), t1 - __builtin_bit_cast(float, n01 & 0xffff0000u),
+                          t2 - __builtin_bit_cast(float, n23 << 16), t3 - __builtin_bit_cast(float, n23 & 0xffff0000u)};
       }
     }
   }

@@ -486,8 +486,10 @@ class WXEngine:
         self._tape = draws   # the engine keeps the raw pointers: keep the tensors alive
 
     # ---- introspection -----------------------------------------------------------------
-    def set_debug(self, on: bool) -> None:
-        _check(self.lib.wx_set_debug(self._h, int(on)))
+    def set_debug(self, level) -> None:
+        """Capture level of wx_set_debug: 0 / False off, 1 / True every named activation (fused routes step aside), 2 what the
+        default routes leave in memory, with no change to which kernels run."""
+        _check(self.lib.wx_set_debug(self._h, int(level)))
 
     def debug_read(self, name: str) -> np.ndarray:
         shape = (C.c_int64 * 3)()
