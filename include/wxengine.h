@@ -536,6 +536,36 @@ int wx_hybrid_destroy(wx_hybrid_handle h);
 int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev,
                     int batch, int n_time, const float* sp_dev, int64_t sp_batch_stride, void* stream);
 
+/* ---- horizontal regridding on the device (csrc/wx_regrid.h) ----------------------------------------------------------------------
+ * credit/preblock/regrid.py::Regridder (registry names `regrid`, `Regridder`): an ESMF sparse weight matrix W [n_b x n_a] applied to
+ * every plane of a variable, y[p, r] = sum_j S[r, j] x[p, col[r, j]], float32 throughout.
+ *   wx_regrid_create / wx_regrid_destroy <-> Regridder.__init__ and _get_W (regrid.py:54-59, :118-132).  HOST arrays: the coalesced
+ *                         matrix as CSR, zero-based -- row_ptr [n_b + 1], col [nnz] and val [nnz] with nnz = row_ptr[n_b]
+ *                         (wxengine.regrid.coalesce_weights makes them from the file's 1-based `row`, `col`, `S`, as
+ *                         sparse_coo_tensor(...).coalesce() does; a source flip is folded into col by wxengine.regrid.fold_flips).
+ *                         The library builds its device format itself: sliced ELL, slice height 64, rows in their order, and
+ *                         a list of the rows with more than 64 entries, which one wave each sums.  A row's terms are added in
+ *                         their stored order.  WX_ERR_INVALID with the reason, before anything is uploaded: a null array; n_a
+ *                         or n_b outside 1 .. 2^31 - 1; row_ptr not starting at 0, decreasing somewhere, or ending at 2^31 or
+ *                         more; a col outside [0, n_a) (it would be an out-of-bounds read on the device).
+ *   wx_regrid_apply       <-> Regridder._regrid (:134-175) for n_vars variables (1 .. 32) in one launch (two when the matrix has
+ *                         long rows):
+ *       src_dev[v]        variable v: plane q of batch item b at src_dev[v] + b * batch_stride[v] + q * n_a floats
+ *                         (batch_stride is ignored when batch == 1), [planes_per_item[v]][n_a] contiguous per batch item, read
+ *                         where it lies -- channel slices of a wider tensor included -- and never written
+ *       dst_dev[v]        [batch * planes_per_item[v]][n_b] contiguous, distinct from every source; every element is written
+ *                         (0.0f for a destination point without entries), so the buffer may arrive uninitialised
+ *     WX_ERR_INVALID: a null handle or pointer, n_vars outside 1 .. 32, batch < 1, a planes_per_item < 1, a negative batch stride,
+ *     2^31 or more planes in one variable.  A plane's bits do not depend on the planes and variables it shares a call with; repeated
+ *     calls give identical bits.  A NaN in the source reaches exactly the destination points whose rows reference it.  Nothing is
+ *     allocated at apply. */
+typedef struct wx_regrid* wx_regrid_handle;
+int wx_regrid_create(int64_t n_a, int64_t n_b, const int64_t* row_ptr, const int32_t* col, const float* val, int device,
+                     wx_regrid_handle* out);
+int wx_regrid_destroy(wx_regrid_handle h);
+int wx_regrid_apply(wx_regrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, const int32_t* planes_per_item,
+                    int batch, float* const* dst_dev, void* stream);
+
 /* ---- verification metrics on the device (csrc/wx_metrics.h) ----------------------------------------------------------------------
  * credit/metrics/base.py, common.py, anomaly.py: the eight per-variable scores of the gen-2 metrics framework from ONE reduction
  * over prediction, target and climatology, in place of three to eight elementwise passes and a host sync per metric and variable.

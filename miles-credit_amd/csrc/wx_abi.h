@@ -387,6 +387,31 @@ int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev,
     });
   });
 }
+// ---- horizontal regridding (an ESMF sparse weight matrix on every plane, sliced-ELL SpMM; csrc/wx_regrid.h) -------------------------
+struct wx_regrid {
+  std::unique_ptr<wx::Regrid> impl;
+};
+int wx_regrid_create(int64_t n_a, int64_t n_b, const int64_t* row_ptr, const int32_t* col, const float* val, int device,
+                     wx_regrid_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_regrid_create: null argument");
+    const std::string why = wx::regrid_check_create(n_a, n_b, row_ptr, col, val);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_regrid_create: " + why);
+    need_device(device, "wx_regrid_create");
+    std::unique_ptr<wx_regrid> h(new wx_regrid);
+    h->impl.reset(new wx::Regrid(n_a, n_b, row_ptr, col, val, device));
+    *out = h.release();
+  });
+}
+int wx_regrid_destroy(wx_regrid_handle h) { return guarded([&] { delete h; }); }
+int wx_regrid_apply(wx_regrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, const int32_t* planes_per_item,
+                    int batch, float* const* dst_dev, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_regrid_apply: null regridding handle");
+    if (!src_dev || !batch_stride || !planes_per_item || !dst_dev) throw wx::ConfigError("wx_regrid_apply: null argument");
+    remap<wx::ConfigError>([&] { h->impl->apply(n_vars, src_dev, batch_stride, planes_per_item, batch, dst_dev, (hipStream_t)stream); });
+  });
+}
 // ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
 struct wx_metrics {
   std::unique_ptr<wx::Metrics> impl;

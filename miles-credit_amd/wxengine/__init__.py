@@ -7,6 +7,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   wind_filter       the wind artifact filter post block (WindArtifactFilter, exported here)
   advect            semi-Lagrangian tracer advection, post and pre block (SemiLagrangianAdvection, SemiLagrangianAdvectionPre, exported here)
   hybrid_interp     hybrid-level interpolation, post and pre block (HybridLevelInterp, HybridLevelInterpPre, midpoint_coefficients, exported here)
+  regrid            horizontal regridding pre block, an ESMF sparse weight matrix on every plane (Regridder, coalesce_weights, fold_flips, exported here)
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
@@ -24,6 +25,9 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name in ("HybridLevelInterp", "HybridLevelInterpPre", "midpoint_coefficients"):
         from . import hybrid_interp
         return getattr(hybrid_interp, name)
+    if name in ("Regridder", "coalesce_weights", "fold_flips"):
+        from . import regrid
+        return getattr(regrid, name)
     if name in ("CombinedMetric", "PendingScores"):
         from . import metrics
         return getattr(metrics, name)

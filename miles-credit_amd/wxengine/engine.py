@@ -143,6 +143,11 @@ _PROTOTYPES = {
     "wx_hybrid_destroy": ([C.c_void_p], C.c_int),
     "wx_hybrid_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int, C.c_int,
                          C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "wx_regrid_create": ([C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                          C.POINTER(C.c_void_p)], C.c_int),
+    "wx_regrid_destroy": ([C.c_void_p], C.c_int),
+    "wx_regrid_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int,
+                         C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
     "wx_metrics_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_metrics_destroy": ([C.c_void_p], C.c_int),
     "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),

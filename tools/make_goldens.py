@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,metrics,ensemble]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,regrid,metrics,ensemble]
 """
 import argparse
 import os
@@ -1022,6 +1022,88 @@ def hybrid_golden():
               + ", ".join(f"{k} {v:.2e}" for k, v in d_ref.items()), flush=True)
 
 
+def regrid_reference(standin_args, name, run, curvilinear=False):
+    """The reference's Regridder (credit/preblock/regrid.py) for a run of a case of tests/regrid_cases.py, reading the case's arrays
+    through the stand-in dataset."""
+    from regrid_cases import reference_args
+    import credit.preblock.regrid as RR
+    arrays, sizes = standin_args
+    kw, arr, sz = reference_args(name, run, curvilinear)
+    arrays.clear(), arrays.update(arr), sizes.clear(), sizes.update(sz)
+    return RR.Regridder(**kw)
+
+
+def regrid_golden():
+    """Horizontal regridding: the reference's Regridder run unmodified on every case, variable and run of tests/regrid_cases.py.  The
+    class reads its weights through xarray, which is absent: a stand-in module serves the case's arrays, sizes and `name in ds`.  The
+    float64 truth is the SAME instance with its `weights` buffer converted to double and its cached matrix cleared, on double inputs.
+    Written per case: regrid_<case>.npz (SHA-256 of every regenerated input, the fp32 outputs per run and variable, the destination
+    attributes) and regrid_<case>_f64.npz (the fp64 outputs).  The generator refuses to write a fixture that misses the condition its
+    case is there for (regrid_cases.check_conditions), whose fp32 output misses the gate of the device tests (regrid_cases.bound), or
+    whose fp64 output the restatement (tests/regrid_oracle.py) does not reproduce."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import regrid_oracle as RO
+    from regrid_cases import REGRID_CASES, SRC, bound, case_inputs, check_conditions, input_digest, key_of, out_shape, run_input, variables, weights
+    arrays, sizes = {}, {}
+    standin = oracle_stub.serve_xarray_dataset(arrays, sizes)
+    import credit.preblock.regrid as RR
+    RR.xr = standin
+
+    for name, c in REGRID_CASES.items():
+        inp = case_inputs(name)
+        summary = check_conditions(name, inp)
+        w = weights(name)
+        fix, f64 = {f"sha256:{v}": np.array(input_digest(inp[v])) for v in inp}, {}
+        worst = 0.0
+        for run in c["runs"]:
+            blk = regrid_reference((arrays, sizes), name, run)
+            res = {}
+            for dtype in (torch.float32, torch.float64):
+                if dtype == torch.float64:
+                    blk.weights = blk.weights.double()
+                    blk._W = None
+                batch = {"input": {SRC: {key_of(v): torch.from_numpy(run_input(name, run, inp[v])).to(dtype) for v in inp}}}
+                with torch.no_grad():
+                    y = blk(batch)["input"][SRC]
+                res[dtype] = {v: y[key_of(v)].contiguous().numpy() for v in inp}
+            shape = RO.dst_shape(w["dst_grid_dims"], w["xc_b"], w["yc_b"], c.get("reshape_to_xy", True))
+            assert (None if blk.dst_shape is None else tuple(int(s) for s in blk.dst_shape)) == shape, name
+            for v in variables(name):
+                a32, a64 = res[torch.float32][v], res[torch.float64][v]
+                assert a32.dtype == np.float32 and a64.dtype == np.float64 and a32.shape == a64.shape == out_shape(name, c["vars"][v]), (name, v)
+                mine, mag, k = RO.regrid(run_input(name, run, inp[v]), w["row"], w["col"], w["S"], w["n_a"], w["n_b"],
+                                         shape if c.get("reshape_to_xy", True) else None, c["runs"][run]["flip_axis"])
+                bad = np.isnan(a64)
+                assert np.array_equal(bad, np.isnan(mine)) and np.array_equal(bad, np.isnan(a32)) and bad.any() == bool(c.get("nan")), (name, v)
+                mag2 = mag.reshape(-1, w["n_b"])
+                scale = np.where(np.isnan(mag2), 0.0, mag2)
+                assert (np.abs(np.where(bad, 0.0, mine - a64)).reshape(-1, w["n_b"]) <= 1e-14 * scale).all(), (name, run, v)
+                err = np.abs(np.where(bad, 0.0, a32.astype(np.float64) - a64)).reshape(-1, w["n_b"])
+                gate = np.where(np.isnan(mag2), 0.0, bound(k, mag2))
+                assert (err <= gate).all(), (name, run, v, "the reference's own float32 output misses the gate")
+                worst = max(worst, float((err[gate > 0] / gate[gate > 0]).max()))
+                if name == "ragged":
+                    assert (a32.reshape(-1, w["n_b"])[:, k == 0] == 0).all() and (k == 0).sum() == 2
+                fix[f"f32:{run}:{v}"] = a32
+                f64[f"f64:{run}:{v}"] = a64
+        for tag, curv in (("rect", False), ("curv", True)) if name == "uniq" else (("rect", False),):
+            blk = regrid_reference((arrays, sizes), name, "plain", curv)
+            if curv:
+                batch = {"input": {SRC: {key_of(v): torch.from_numpy(inp[v]) for v in inp}}}
+                assert all(np.array_equal(blk(batch)["input"][SRC][key_of(v)].numpy(), fix[f"f32:plain:{v}"]) for v in inp)
+            fix[f"grid_type:{tag}"] = np.array(str(blk.dst_grid_type))
+            if blk.dst_grid_type is not None:
+                fix[f"dst_lat:{tag}"], fix[f"dst_lon:{tag}"] = np.asarray(blk.dst_lat), np.asarray(blk.dst_lon)
+        if name == "uniq":
+            assert str(fix["grid_type:rect"]) == "rectilinear" and str(fix["grid_type:curv"]) == "curvilinear"
+        np.savez_compressed(os.path.join(GOLD, f"regrid_{name}.npz"), **fix)
+        np.savez_compressed(os.path.join(GOLD, f"regrid_{name}_f64.npz"), **f64)
+        sizes_kb = [os.path.getsize(os.path.join(GOLD, f"regrid_{name}{s}.npz")) for s in ("", "_f64")]
+        assert max(sizes_kb) < 1000000, (name, sizes_kb)
+        print(f"[golden] regrid {name}: {summary}; files {sizes_kb[0] // 1024} + {sizes_kb[1] // 1024} KB; the reference's fp32 output "
+              f"at {worst:.2f} of the gate", flush=True)
+
+
 def metrics_reference(case, inp):
     """The reference's BaseCombinedMetric for a case of tests/metrics_cases.py: the class runs unmodified; the two loaders that read
     files (the scaler's variances, the grid's latitude) serve the case's arrays."""
@@ -1571,6 +1653,8 @@ def main():
             wind_golden()
         elif item == "advect":      # semi-Lagrangian tracer advection: omega, back-trajectory, trilinear gather
             advect_golden()
+        elif item == "regrid":      # horizontal regridding: an ESMF sparse weight matrix on every plane
+            regrid_golden()
         elif item == "hybrid":      # hybrid-level interpolation: one set of hybrid levels onto another, linear in log p
             hybrid_golden()
         elif item == "metrics":     # gen-2 verification metrics: rmse, mse, mae, bias, r2score, log_variance_ratio, acc, activity

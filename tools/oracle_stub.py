@@ -93,3 +93,29 @@ def serve_xarray(arrays):
     standin.open_dataset = lambda _path, **_kw: _Dataset()
     sys.modules["xarray"] = standin
     return standin
+
+
+def serve_xarray_dataset(arrays, sizes):
+    """`serve_xarray` for the reference classes that also ask the dataset for its dimension sizes and for the presence of a variable
+    (credit/preblock/regrid.py): `ds[name].values` serves `arrays[name]`, `ds.sizes[dim]` serves `sizes[dim]` and `name in ds` tells
+    whether `arrays` holds it.  Both dicts are read at access time.  Returns the module."""
+    class _Dataset:
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            return False
+
+        def __getitem__(self, name):
+            return types.SimpleNamespace(values=arrays[name])
+
+        def __contains__(self, name):
+            return name in arrays
+
+        @property
+        def sizes(self):
+            return sizes
+    standin = types.ModuleType("xarray")
+    standin.open_dataset = lambda _path, **_kw: _Dataset()
+    sys.modules["xarray"] = standin
+    return standin
