@@ -566,6 +566,34 @@ int wx_regrid_destroy(wx_regrid_handle h);
 int wx_regrid_apply(wx_regrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, const int32_t* planes_per_item,
                     int batch, float* const* dst_dev, void* stream);
 
+/* ---- TISR forcing on the device (csrc/wx_tisr.h) ------------------------------------------------------------------------------------
+ * credit/datasets/gen_2/tisr.py::TISRDataset / _compute_tisr: the top-of-atmosphere incident solar radiation accumulated over the
+ * window (t - period, t], J/m2, float32 -- a GraphCast / IFS orbital model, an annual TSI table, cos(zenith) floored at 0 at every grid
+ * point and sub-step, a trapezoid over n_steps + 1 sub-steps.  The reference's float32 quantisation of time (days since J2000, fractional
+ * year) is reproduced; everything else of a sub-step is evaluated in fp64, a point's sum is kept in fp64 and rounded once.
+ *   wx_tisr_create / wx_tisr_destroy <-> TISRDataset.__init__.  HOST arrays: lat_host, lon_host [ny][nx] in degrees (a rectangular grid
+ *                         as its meshgrid, a curvilinear one as it is) and the TSI table, tsi_times_host [n_tsi] in fractional years,
+ *                         ascending, with tsi_values_host [n_tsi] in W/m2 (`time` and `tsi` of total_solar_irradiance_CMIP6_49r1.nc).
+ *                         WX_ERR_INVALID with the reason: a null argument; ny or nx < 1 or ny * nx > 2^31 - 1; fewer than two table
+ *                         entries; a table that is not finite or does not ascend; a latitude or longitude that is not finite.
+ *   wx_tisr_compute       <-> _compute_tisr for n_times target times (any number; 64 go into one pair of launches):
+ *       t_end_ns_host     HOST array [n_times], the ends of the windows as Unix nanoseconds (UTC); they travel in the kernel arguments
+ *       period_ns         the length of the window; n_steps: num_integration_steps.  The sub-steps are those of pandas' date_range(end =
+ *                         t, periods = n_steps + 1, freq = period / n_steps): the step is period_ns / n_steps truncated to whole ns
+ *       dst_dev           the plane of target time i is written at dst_dev + i * plane_stride floats, [ny][nx] contiguous; nothing else
+ *                         is written, so a plane may be a channel slot of a wider forcing tensor
+ *     WX_ERR_INVALID, decided on the host before any launch: a null handle or argument, n_times < 1, n_steps outside 1 .. 2^22 - 1,
+ *     period_ns < 1 or < n_steps, plane_stride < ny * nx, a window that leaves the int64 range, a sub-step whose YEAR lies outside
+ *     int(tsi_times[0]) .. int(tsi_times[n_tsi - 1]) (the reference's ValueError).  A plane's bits do not depend on the target times it
+ *     shares a call with.  The coefficient table is the handle's own and grows with n_steps (at most 64 MB): calls on one handle must
+ *     be ordered by one stream. */
+typedef struct wx_tisr* wx_tisr_handle;
+int wx_tisr_create(int ny, int nx, const float* lat_host, const float* lon_host, int n_tsi, const float* tsi_times_host,
+                   const float* tsi_values_host, int device, wx_tisr_handle* out);
+int wx_tisr_destroy(wx_tisr_handle h);
+int wx_tisr_compute(wx_tisr_handle h, int n_times, const int64_t* t_end_ns_host, int64_t period_ns, int n_steps, float* dst_dev,
+                    int64_t plane_stride, void* stream);
+
 /* ---- verification metrics on the device (csrc/wx_metrics.h) ----------------------------------------------------------------------
  * credit/metrics/base.py, common.py, anomaly.py: the eight per-variable scores of the gen-2 metrics framework from ONE reduction
  * over prediction, target and climatology, in place of three to eight elementwise passes and a host sync per metric and variable.

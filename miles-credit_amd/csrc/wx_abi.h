@@ -412,6 +412,30 @@ int wx_regrid_apply(wx_regrid_handle h, int n_vars, const float* const* src_dev,
     remap<wx::ConfigError>([&] { h->impl->apply(n_vars, src_dev, batch_stride, planes_per_item, batch, dst_dev, (hipStream_t)stream); });
   });
 }
+// ---- TISR forcing (top-of-atmosphere incident solar radiation per step, a coefficient table and one sum per point; csrc/wx_tisr.h) ----
+struct wx_tisr {
+  std::unique_ptr<wx::Tisr> impl;
+};
+int wx_tisr_create(int ny, int nx, const float* lat_host, const float* lon_host, int n_tsi, const float* tsi_times_host,
+                   const float* tsi_values_host, int device, wx_tisr_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_tisr_create: null argument");
+    const std::string why = wx::tisr_check_create(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_tisr_create: " + why);
+    need_device(device, "wx_tisr_create");
+    std::unique_ptr<wx_tisr> h(new wx_tisr);
+    h->impl.reset(new wx::Tisr(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host, device));
+    *out = h.release();
+  });
+}
+int wx_tisr_destroy(wx_tisr_handle h) { return guarded([&] { delete h; }); }
+int wx_tisr_compute(wx_tisr_handle h, int n_times, const int64_t* t_end_ns_host, int64_t period_ns, int n_steps, float* dst_dev,
+                    int64_t plane_stride, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_tisr_compute: null TISR handle");
+    remap<wx::ConfigError>([&] { h->impl->compute(n_times, t_end_ns_host, period_ns, n_steps, dst_dev, plane_stride, (hipStream_t)stream); });
+  });
+}
 // ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
 struct wx_metrics {
   std::unique_ptr<wx::Metrics> impl;

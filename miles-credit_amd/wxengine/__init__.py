@@ -8,6 +8,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   advect            semi-Lagrangian tracer advection, post and pre block (SemiLagrangianAdvection, SemiLagrangianAdvectionPre, exported here)
   hybrid_interp     hybrid-level interpolation, post and pre block (HybridLevelInterp, HybridLevelInterpPre, midpoint_coefficients, exported here)
   regrid            horizontal regridding pre block, an ESMF sparse weight matrix on every plane (Regridder, coalesce_weights, fold_flips, exported here)
+  tisr              the TISR dynamic forcing per step from a clock, top-of-atmosphere incident solar radiation (TISRForcing, exported here)
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
@@ -28,6 +29,9 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name in ("Regridder", "coalesce_weights", "fold_flips"):
         from . import regrid
         return getattr(regrid, name)
+    if name == "TISRForcing":
+        from .tisr import TISRForcing
+        return TISRForcing
     if name in ("CombinedMetric", "PendingScores"):
         from . import metrics
         return getattr(metrics, name)

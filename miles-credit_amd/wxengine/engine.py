@@ -148,6 +148,10 @@ _PROTOTYPES = {
     "wx_regrid_destroy": ([C.c_void_p], C.c_int),
     "wx_regrid_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int,
                          C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
+    "wx_tisr_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                        C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_tisr_destroy": ([C.c_void_p], C.c_int),
+    "wx_tisr_compute": ([C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "wx_metrics_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_metrics_destroy": ([C.c_void_p], C.c_int),
     "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),

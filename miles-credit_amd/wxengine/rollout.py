@@ -2,7 +2,8 @@
 
     for step in 1..n: y = model(x) [+tracer fixer]; y_phys = y*std+mean; x = update_x(x, frc_t, y)
 
-All tensors stay in HBM: forcing for every step is pre-staged on the device, y_phys is written into a
+All tensors stay in HBM: forcing for every step is pre-staged on the device (the `tisr` plane of a step is made there from the
+step's valid time alone: `wxengine.tisr.TISRForcing.compute_into(t, frc, channel=k)`), y_phys is written into a
 caller-provided ring so the host can drain it asynchronously (the reference does `.cpu().numpy()` every
 step, rollout_to_netcdf.py:292), and the next input is assembled by the engine's tail kernel.
 """
