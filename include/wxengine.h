@@ -594,6 +594,42 @@ int wx_tisr_destroy(wx_tisr_handle h);
 int wx_tisr_compute(wx_tisr_handle h, int n_times, const int64_t* t_end_ns_host, int64_t period_ns, int n_steps, float* dst_dev,
                     int64_t plane_stride, void* stream);
 
+/* ---- perturbed initial conditions on the device (csrc/wx_perturb.h) ------------------------------------------------------------------
+ * credit/ensemble/gaussian.py::GaussianNoise, color.py::ColorNoise, temporal.py::TemporalNoise and utils.hemispheric_rescale: the
+ * ensemble route of applications/rollout_metrics_noisy_ic.py, which works with every deterministic checkpoint.  One handle per grid; one
+ * call per member and step on the n_planes = C * T planes of a [1, C, T, H, W] float32 tensor (a plane is H * W contiguous floats).
+ *   wx_perturb_create / wx_perturb_destroy: kind 0 white (delta = amplitude * r), kind 1 colour (r filtered per plane:
+ *                         irfft2(rfft2(r) * S, s = (H, W)) by dense fp64 DFTs on the matrix cores).  S_host: HOST array [H][W / 2 + 1],
+ *                         ColorNoise's float32 `scaling_weights`; ignored (may be NULL) for kind 0.  WX_ERR_INVALID with the reason: an
+ *                         unknown kind; H < 1 or W < 2; H * W beyond the generator's counter (2^34); for kind 1 a null or non-finite S,
+ *                         or a side above 4096 points (a pass keeps its twiddle table in LDS).
+ *   wx_perturb_batch      the number of planes the colour filter takes through its scratch at a time: min(64, 256 MiB / (32 H (W / 2 + 1))).
+ *   wx_perturb_apply      r: tape_dev (DEVICE, float32, [n_planes][H][W] contiguous: the reference's torch.randn draws replayed) or, when
+ *                         NULL, the engine's generator (Philox4x32-10 / Box-Muller as for wx_set_noise) with the counter (e >> 2, slot 16,
+ *                         member, step), e = (p * H + h) * W + x.  A draw depends on (seed, member, step, e) alone.  Then per element, every
+ *                         operation rounded once in float32 in the reference's order:
+ *                             eps = amplitude * n;  eps *= chan_scale[p];  d = rho * prev + eps;  d *= lat_weight[h];
+ *                             delta_out = d;  x_out = x + d
+ *       chan_scale_host   HOST array [n_planes] or NULL (TemporalNoise: perturbation_std[c] / amplitude, repeated over the T planes of c)
+ *       prev_dev, rho     the member's previous delta (DEVICE) or NULL: no AR(1) term
+ *       lat_weight_host   HOST array [H] or NULL (hemispheric_rescale's weights)
+ *       x_dev, delta_out_dev, x_out_dev   DEVICE; either output may be NULL, not both; x_out needs x.  Plane p of each lies at
+ *                         pointer + p * its stride (in floats, >= H * W): a channel range of a wider tensor is perturbed where it lies and
+ *                         nothing outside the planes is written.  x_out may be x and delta_out may be prev (same pointer, same stride).
+ *     WX_ERR_INVALID with the reason, nothing launched, copied or written: a null handle; n_planes < 1 or H * W * n_planes > 2^34; no
+ *     output; x_out without x; a stride below H * W or one that takes the planes beyond
+ *     2^44 floats; a tape that overlaps an output; an input that overlaps an output otherwise than
+ *     as the same view.  A plane's bits do not depend on n_planes, the batch split or the other planes.  The scratch is the handle's own:
+ *     calls on one handle must be ordered by one stream. */
+typedef struct wx_perturb* wx_perturb_handle;
+int wx_perturb_create(int H, int W, int kind, const float* S_host, int device, wx_perturb_handle* out);
+int wx_perturb_destroy(wx_perturb_handle h);
+int wx_perturb_batch(wx_perturb_handle h, int* planes_out);
+int wx_perturb_apply(wx_perturb_handle h, int n_planes, const float* tape_dev, uint64_t seed, int member, int step, float amplitude,
+                     const float* chan_scale_host, float rho, const float* prev_dev, int64_t prev_stride, const float* lat_weight_host,
+                     const float* x_dev, int64_t x_stride, float* delta_out_dev, int64_t delta_stride, float* x_out_dev, int64_t x_out_stride,
+                     void* stream);
+
 /* ---- verification metrics on the device (csrc/wx_metrics.h) ----------------------------------------------------------------------
  * credit/metrics/base.py, common.py, anomaly.py: the eight per-variable scores of the gen-2 metrics framework from ONE reduction
  * over prediction, target and climatology, in place of three to eight elementwise passes and a host sync per metric and variable.

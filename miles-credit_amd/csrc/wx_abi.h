@@ -436,6 +436,41 @@ int wx_tisr_compute(wx_tisr_handle h, int n_times, const int64_t* t_end_ns_host,
     remap<wx::ConfigError>([&] { h->impl->compute(n_times, t_end_ns_host, period_ns, n_steps, dst_dev, plane_stride, (hipStream_t)stream); });
   });
 }
+// ---- perturbed initial conditions (white, colour-filtered and AR(1) noise on the planes of one member; csrc/wx_perturb.h) ----------
+struct wx_perturb {
+  std::unique_ptr<wx::Perturb> impl;
+};
+int wx_perturb_create(int H, int W, int kind, const float* S_host, int device, wx_perturb_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_perturb_create: null argument");
+    const std::string why = wx::perturb_check_create(H, W, kind, S_host);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_perturb_create: " + why);
+    need_device(device, "wx_perturb_create");
+    std::unique_ptr<wx_perturb> h(new wx_perturb);
+    h->impl.reset(new wx::Perturb(H, W, kind, S_host, device));
+    *out = h.release();
+  });
+}
+int wx_perturb_destroy(wx_perturb_handle h) { return guarded([&] { delete h; }); }
+int wx_perturb_batch(wx_perturb_handle h, int* planes_out) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_perturb_batch: null perturbation handle");
+    if (!planes_out) throw wx::ConfigError("wx_perturb_batch: null argument");
+    *planes_out = h->impl->batch_planes();
+  });
+}
+int wx_perturb_apply(wx_perturb_handle h, int n_planes, const float* tape_dev, uint64_t seed, int member, int step, float amplitude,
+                     const float* chan_scale_host, float rho, const float* prev_dev, int64_t prev_stride, const float* lat_weight_host,
+                     const float* x_dev, int64_t x_stride, float* delta_out_dev, int64_t delta_stride, float* x_out_dev, int64_t x_out_stride,
+                     void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_perturb_apply: null perturbation handle");
+    remap<wx::ConfigError>([&] {
+      h->impl->apply(n_planes, tape_dev, seed, member, step, amplitude, chan_scale_host, rho, prev_dev, prev_stride, lat_weight_host, x_dev, x_stride,
+                     delta_out_dev, delta_stride, x_out_dev, x_out_stride, (hipStream_t)stream);
+    });
+  });
+}
 // ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
 struct wx_metrics {
   std::unique_ptr<wx::Metrics> impl;

@@ -11,6 +11,8 @@
 //             launch geometry, precision and kernel variant); latent z [Dn]: e = j
 //     slot    0 - 2 the encoder layers encoder_noise_layers.{0,1,2}, 3 - 5 the decoder layers noise_inject{1,2,3} (pixel noise);
 //             6 + l the latent of layer slot l; with `correlated` one latent per forward, slot 6
+//             16 (SLOT_PERTURB, csrc/wx_perturb.h) the white source of the perturbed-initial-condition noise: e = (p * H + h) * W + x
+//             over the P = C * T planes of one member's [1, C, T, H, W] tensor; step = the forecast step
 //     member  ensemble member (wx_set_noise member0 + batch row)
 //     step    the forward / step coordinate (wx_set_noise step, advanced by one after every forward, wx_step and rollout step)
 //   Box-Muller on the four output words (w0, w1, w2, w3) -> normals (n0, n1, n2, n3) of elements 4q .. 4q + 3:

@@ -9,6 +9,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   hybrid_interp     hybrid-level interpolation, post and pre block (HybridLevelInterp, HybridLevelInterpPre, midpoint_coefficients, exported here)
   regrid            horizontal regridding pre block, an ESMF sparse weight matrix on every plane (Regridder, coalesce_weights, fold_flips, exported here)
   tisr              the TISR dynamic forcing per step from a clock, top-of-atmosphere incident solar radiation (TISRForcing, exported here)
+  perturb           perturbed-initial-condition ensembles: white, colour-filtered and AR(1) noise on a member's planes (GaussianNoise, ColorNoise, TemporalNoise, hemispheric_weights, exported here)
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
@@ -32,6 +33,9 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name == "TISRForcing":
         from .tisr import TISRForcing
         return TISRForcing
+    if name in ("GaussianNoise", "ColorNoise", "TemporalNoise", "hemispheric_weights"):
+        from . import perturb
+        return getattr(perturb, name)
     if name in ("CombinedMetric", "PendingScores"):
         from . import metrics
         return getattr(metrics, name)

@@ -152,6 +152,11 @@ _PROTOTYPES = {
                         C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_tisr_destroy": ([C.c_void_p], C.c_int),
     "wx_tisr_compute": ([C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "wx_perturb_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_perturb_destroy": ([C.c_void_p], C.c_int),
+    "wx_perturb_batch": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
+    "wx_perturb_apply": ([C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_float, C.c_void_p,
+                          C.c_int64, C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
     "wx_metrics_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_metrics_destroy": ([C.c_void_p], C.c_int),
     "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),

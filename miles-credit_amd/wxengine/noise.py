@@ -19,6 +19,9 @@ from .synth import keyed_normal
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 W0, W1 = 0x9E3779B9, 0xBB67AE85
 SLOT_LATENT = 6   # latent of layer slot l: slot 6 + l (6 alone when correlated)
+SLOT_PERTURB = 16  # the white source of the perturbed-initial-condition noise (csrc/wx_perturb.h, wxengine.perturb): element index
+#                    e = (p * H + h) * W + x over the P = C * T planes of one member's [1, C, T, H, W] tensor, step = the forecast step;
+#                    normals(seed, SLOT_PERTURB, member, step, n) are the first n draws of a call.  Slots 0 - 11 are the noise layers'.
 
 
 def philox4x32_10(ctr, key) -> np.ndarray:

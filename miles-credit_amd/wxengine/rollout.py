@@ -119,6 +119,68 @@ def ensemble_rollout(engine: WXEngine, x0: torch.Tensor, forcings: Sequence[Opti
     return out
 
 
+def perturbed_ensemble_rollout(engine: WXEngine, x0: torch.Tensor, forcings: Sequence[Optional[torch.Tensor]], n_members: int, noise, *,
+                               seed: int = 0, member0: int = 0, n_perturbed: Optional[int] = None, temporal=None, deltas=None):
+    """A perturbed-initial-condition ensemble of a deterministic engine (applications/rollout_metrics_noisy_ic.py:384-415): member m
+    starts from x0 + noise(x0) on the first `n_perturbed` input channels (default: all of them, as the reference perturbs the whole
+    assembled input) with the generator's coordinates (seed, member0 + m, step 1), and runs one wx_rollout.
+
+    noise: a wxengine.perturb GaussianNoise or ColorNoise.  temporal: a wxengine.perturb.TemporalNoise (its own generator is used and
+    `noise` is ignored): the member is run step by step, and before every later step t = 2, 3, ... the prognostic channels of the next
+    input are perturbed in place with delta_t = rho * delta_{t-1} + eps_t (generator step t), the member's delta being carried on the
+    device.  The prognostic channels are the first channels * levels + surface_channels of the input (the single-source layout).
+    deltas: an optional list that receives, per member, the list of its carried perturbations [delta_1, delta_2, ...].
+
+    Returns [member][step] de-normalised outputs in the shape `ensemble_rollout` returns (engine.set_denorm must have been called):
+    `score_ensemble_rollout` takes them unchanged."""
+    from .perturb import TemporalNoise, _Noise
+    cfg = engine.cfg
+    if isinstance(n_members, bool) or not isinstance(n_members, int) or n_members < 1:
+        raise ValueError(f"perturbed_ensemble_rollout: n_members must be a positive integer, got {n_members!r}")
+    if len(forcings) < 1:
+        raise ValueError("perturbed_ensemble_rollout: forcings must have one entry per step, got none")
+    if temporal is not None and not isinstance(temporal, TemporalNoise):
+        raise TypeError("perturbed_ensemble_rollout: temporal must be a wxengine.perturb.TemporalNoise or None")
+    if temporal is None and not isinstance(noise, _Noise):
+        raise TypeError("perturbed_ensemble_rollout: noise must be a wxengine.perturb GaussianNoise or ColorNoise")
+    want = (1, cfg.base_input_channels, cfg.frames, cfg.image_height, cfg.image_width)
+    if not isinstance(x0, torch.Tensor) or tuple(x0.shape) != want:
+        raise ValueError(f"perturbed_ensemble_rollout: x0 must be a tensor of shape {want}, got "
+                         f"{tuple(x0.shape) if isinstance(x0, torch.Tensor) else type(x0).__name__}")
+    n_in = cfg.base_input_channels
+    n_pert = n_in if n_perturbed is None else n_perturbed
+    if isinstance(n_pert, bool) or not isinstance(n_pert, int) or not 1 <= n_pert <= n_in:
+        raise ValueError(f"perturbed_ensemble_rollout: n_perturbed must be 1 .. {n_in}, got {n_perturbed!r}")
+    n_carry = min(n_pert, cfg.channels * cfg.levels + cfg.surface_channels)
+    oh, ow = cfg.out_hw
+    n = len(forcings)
+    out = []
+    for m in range(n_members):
+        member = member0 + m
+        x = x0.clone()
+        head = x[:, :n_pert]
+        phys = [torch.empty((1, cfg.base_output_channels, oh, ow), dtype=torch.float32, device=x0.device) for _ in forcings]
+        if temporal is None:
+            noise.apply(head, seed=seed, member=member, step=1, x_out=head)
+            engine.rollout(x, forcings, phys_out=phys)
+        else:
+            _, delta = temporal(head, None, 1, seed=seed, member=member, out=head)
+            delta = delta[:, :n_carry]
+            carried = [delta]
+            for t in range(n):
+                last = t == n - 1
+                _, _, xn = engine.step(x, forcings[t], want_y=False, phys_out=phys[t], want_next=not last)
+                if not last:
+                    prog = xn[:, :n_carry]
+                    _, delta = temporal(prog, delta, t + 2, seed=seed, member=member, out=prog)
+                    carried.append(delta)
+                    x = xn
+            if deltas is not None:
+                deltas.append(carried)
+        out.append(phys)
+    return out
+
+
 def score_ensemble_rollout(out, targets, verifier, channel_map):
     """Score the [member][step] output of `ensemble_rollout` where it lies: every step is submitted to `verifier` (an
     ensemble_metrics.EnsembleVerification) without a host sync, the members read as channel slices of their own buffers.
