@@ -772,6 +772,9 @@ int wx_band_plan_partition(wx_band_plan p, int which, int32_t* starts);
  *   "<attention>.attn" (the attention output in front of to_out) and "<attention>.qkv" (q|k|v, [3C, H, W]; bf16 engine: the q
  *   channels carry dim_head^-0.5 * log2(e)) are captured wherever they are row-major in memory -- not in the k-blocked chain
  *   nor inside the one-launch attention block.  Level 2 changes no arithmetic: the forward is bit-identical to level 0's.
+ *   At either level the decoder's stored intermediates are captured too (not in lat-band mode): "up_blockN.up" (the shortcut),
+ *   "up_blockN.c1" / ".n1" / ".c2" (first 3x3 conv, GroupNorm + SiLU, second 3x3 conv), "up_blockN.ps" / "up_block4.ps" (wxformer:
+ *   the pixel-shuffled map) and "up_blockN.us" / "up_block4.us" (upsample_v_conv: the upsampled input), N = 1..3.
  *   level 0: off.  No forward is captured into a graph while a level is on.
  * wx_profile: when enabled, every kernel launch is bracketed by HIP events on the launch stream;
  *   wx_profile_read returns per-kernel-class totals since the last wx_profile_reset.  enable: 1 per class ("gemm_ff1"),
@@ -792,6 +795,8 @@ typedef struct wx_kernel_stat {
  * parity test needs to prove it exercised the path it names; the reference has no counterpart: its "schedule" is ATen's).  Keys:
  *   "launches"           kernel launches of the last forward
  *   "gemm8p_launches"    ... of which ran on the eight-phase kernel (wx_gemm8p.h: the decoder's deep-K convolutions, round 6)
+ *   "splitk_gemms"       ... of which were plain convolutions split over K ranges with a fixed-order finish kernel (CrossEmbed GEMMs of
+ *                        small maps)
  *   "attn_blk"           attention sub-blocks of the last forward whose q|k|v and attention output travelled k-blocked (round 6)
  *   "attn_nkf_mask"      bit n set: the last forward launched window_attn_kernel with NKF == n key fragments of 16 tokens (n in 1, 2, 4,
  *                        7, 8, 10, 12, 14, 16: windows of <= 16, 32, 64, 112, 128, 160, 192, 224, 256 tokens)

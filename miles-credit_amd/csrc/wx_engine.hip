@@ -202,6 +202,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   float* embed_partial = nullptr;
   size_t embed_partial_bytes = 0;
   int64_t n_gemm8p = 0;              // launches of the last forward that took it
+  int64_t n_splitk = 0;              // plain split-K launches (K ranges + finish kernel) of the last forward
   char* stream_sink = nullptr;
   float2* statpart = nullptr;   // [rows][slots] LayerNorm partials written by the producing GEMM epilogue (slots <= 8, or C / 32)
   int64_t statpart_elems = 0;
@@ -410,6 +411,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (key == "precision") { *v = sizeof(T) == 2 ? WX_PREC_BF16 : (split_mma ? WX_PREC_FP32_SPLIT : WX_PREC_FP32); return true; }
     if (key == "split_gemms") { *v = n_split_gemms; return true; }
     if (key == "gemm8p_launches") { *v = n_gemm8p; return true; }
+    if (key == "splitk_gemms") { *v = n_splitk; return true; }
     if (key == "attn_blk") { *v = n_attn_blk; return true; }
     if (key == "attn_nkf_mask") { *v = attn_nkf_mask; return true; }
     if (key == "attn_block_nkf_mask") { *v = attn_block_nkf_mask; return true; }
@@ -733,6 +735,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       if (S >= 2) {
         p.partial = splitk_scratch((size_t)S * rows * w.n * sizeof(float));
         p.k_splits = S;
+        ++n_splitk;
       }
     }
     // ... and for the deep-K 1 x 1 layers of the transformer blocks on maps of a few hundred pixels (1-degree grid, stages 2 - 3:
@@ -1299,6 +1302,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   }
   void core(const float* x_item) {
     n_gemm8p = 0;
+    n_splitk = 0;
     n_attn_blk = 0;
     n_split_gemms = 0;
     n_ff_split_fused = 0;
@@ -1338,23 +1342,32 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       const int64_t in_ld = (i == 0) ? cfg.dim[3] : 2 * cfg.dim[si];
       const int64_t mo = (int64_t)sh[so] * sw[so];
       T *scut = dtmp[0], *ta = dtmp[1], *tb = dtmp[2];
+      // the block's stored intermediates, captured behind the launch that wrote them (ta is written twice); no route depends on them
+      const std::string up = "up_block" + std::to_string(i + 1);
+      auto cap_mid = [&](const char* what, const T* buf, int c) { capture(up + what, buf, sh[so], sw[so], c, c, sw[so]); };
       if (cfg.arch == WX_ARCH_WXFORMER) {
         // x = PixelShuffle(conv3x3(x)); x = x + sharp(x)   (wxformer/crossformer.py:157-158)
         gemm("gemm_convPS", u.convps, {.in = in, .in_h = sh[si], .in_w = sw[si], .in_ld = in_ld, .out = dtmp[3], .out_ld = u.cout, .out_mode = 1,
                                        .cout = u.cout});
+        cap_mid(".ps", dtmp[3], u.cout);
         gemm("gemm_conv3", u.sharp, {.in = dtmp[3], .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = scut, .out_ld = u.cout, .res = dtmp[3],
                                      .res_ld = u.cout});
       } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
         upsample2x(in, sh[si], sw[si], in_ld, u.cin);
+        cap_mid(".us", upbuf, u.cin);
         gemm("gemm_conv3", u.upc, {.in = upbuf, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cin, .out = scut, .out_ld = u.cout});
       } else {
         gemm("gemm_convT2", u.convt, {.in = in, .in_h = sh[si], .in_w = sw[si], .in_ld = in_ld, .out = scut, .out_ld = u.cout, .out_mode = 1, .cout = u.cout});
       }
+      cap_mid(".up", scut, u.cout);
       int tiles = gemm("gemm_conv3", u.c1, {.in = scut, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = ta, .out_ld = u.cout, .want_gn = true}).gn_tiles;
+      cap_mid(".c1", ta, u.cout);
       group_norm_silu(ta, u.cout, mo, u.g1, u.b1, nullptr, 0, tb, u.cout, tiles);
+      cap_mid(".n1", tb, u.cout);
       tiles = gemm("gemm_conv3", u.c2, {.in = tb, .in_h = sh[so], .in_w = sw[so], .in_ld = u.cout, .out = ta, .out_ld = u.cout, .want_gn = true}).gn_tiles;
+      cap_mid(".c2", ta, u.cout);
       group_norm_silu(ta, u.cout, mo, u.g2, u.b2, scut, u.cout, cat[so], 2 * cfg.dim[so], tiles);
-      capture("up_block" + std::to_string(i + 1), cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
+      capture(up, cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
       if (noise_slot_on(3 + i)) {       // before the concat: the up block's half of cat[so]
         noise_inject(3 + i, cat[so], 2 * cfg.dim[so], sh[so], sw[so]);
         capture(noise_prefix(3 + i), cat[so], sh[so], sw[so], u.cout, 2 * cfg.dim[so], sw[so]);
@@ -1364,9 +1377,11 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     if (cfg.arch == WX_ARCH_WXFORMER) {
       gemm("gemm_convPS", ps4, {.in = cat[0], .in_h = sh[0], .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = ps4_buf, .out_ld = cpad4, .out_mode = 1,
                                 .cout = cpad4});
+      capture("up_block4.ps", ps4_buf, Hd, Wd, C_out, cpad4, Wd);
       gemm("gemm_conv3", fin4, {.in = ps4_buf, .in_h = Hd, .in_w = Wd, .in_ld = cpad4, .out = dec, .out_ld = ld_dec});
     } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {
       upsample2x(cat[0], sh[0], sw[0], 2 * cfg.dim[0], 2 * cfg.dim[0]);
+      capture("up_block4.us", upbuf, Hd, Wd, 2 * cfg.dim[0], 2 * cfg.dim[0], Wd);
       gemm("gemm_conv3", up4c, {.in = upbuf, .in_h = Hd, .in_w = Wd, .in_ld = 2 * cfg.dim[0], .out = dec, .out_ld = ld_dec});
     } else {
       // pads (1 - py, 1 - px), output pixel (2 oy + py, 2 ox + px): gemm() runs the four parities (merged when it can)

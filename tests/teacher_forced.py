@@ -25,12 +25,37 @@ Links, from the captures of ONE forward (wx_set_debug level 1 or 2; a link exist
                                                           computed in fp64 and never rounded -- it is never stored on that path
 
 x_in is the previous sub-block's capture, or "layers.S.0" for a stage's first sub-block.
+
+The convolutional rest of the forward -- the four CrossEmbeds, the three UpBlocks, the up_block4 head and the tail -- has links of
+the same kind (build_conv_links), over the captures the engine makes of an UpBlock's stored intermediates at any capture level:
+
+  embed    "pad" (s = 0) / "layers.(s-1).1" -> "layers.s.0"                      O.cross_embed
+  up       x = "layers.3.1" (N = 1) / cat("up_block(N-1)", "layers.(4-N).1") -> "up_blockN.up": ConvTranspose k2 s2 of x; upconv
+           decoder: conv3 of the CAPTURED "up_blockN.us"; wxformer: -> "up_blockN.ps" = PixelShuffle(conv3(x))
+  us       x -> "up_blockN.us" = O.upsample2x(x)                                  (upconv decoder)
+  sharp    "up_blockN.ps" -> "up_blockN.up" = ps + conv3(ps)                      (wxformer; base ps)
+  c1       "up_blockN.up" -> "up_blockN.c1"                                       conv3
+  n1       "up_blockN.c1" -> "up_blockN.n1"                                       GroupNorm(dim[0] groups) + SiLU
+  c2       "up_blockN.n1" -> "up_blockN.c2"                                       conv3
+  n2       "up_blockN.c2", "up_blockN.up" -> "up_blockN"                          GroupNorm + SiLU + shortcut (base the shortcut)
+  head     cat("up_block3", "layers.0.1") -> "up_block4"                          ConvTranspose k4 s2 p1 / conv3(PixelShuffle(conv3)) /
+                                                                                  conv3(upsample2x) -- the three forms of O.forward
+  head_ps, head_us, head_fin   the same head through its captured intermediate "up_block4.ps" / "up_block4.us": cat -> intermediate,
+           intermediate -> "up_block4" (what `head` alone cannot tell apart)
+  tail     "up_block4" -> y (forward's batch row 0)                               earth_unpad + bilinear_resize, i0 / i1 / lambda from the
+                                                                                  oracle's fp32 index rule, the blend in fp64
+
+The denominator of a link without a base is rms_row(ref) over the channels of that pixel.  GroupNorm: the engine's statistics come
+from the fp32 accumulators of the producing GEMM's epilogue (per-tile partials) BEFORE the store, the reference computes them from the
+stored, rounded map; the two differ by O(2^-9 / sqrt(n)) of a standard deviation, n the elements of a group -- this is not a finding.
+Ensemble (noise) configurations are not covered: the noisy maps are not a function of the captures alone.
 """
 import math
 from collections import namedtuple
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from oracle import wxformer_oracle as O
 
@@ -42,6 +67,10 @@ F64 = torch.float64
 # chain, MEASURED on MI355X per weight family; the plain chain is held to 1.25 x, every other route to 2 x; 2 x B_PLAIN <= B_CEIL is
 # a condition, not a measurement.
 B_PLAIN = {"base": 0.0126, "stress": 0.0135}
+# ... and of the convolutional links: b_conv = the worst d over all links of the conv_plain engines (128 x 128 implicit GEMM only, no
+# merged / split-K / ride-along CrossEmbed forms, GroupNorm partials folded by their own launch), measured the same way (the per-case
+# figures: test_teacher_forced_gpu.test_bf16_conv_links_teacher_forced).  conv_plain is held to 1.25 x, every other route to 2 x.
+B_PLAIN_CONV = {"base": 0.0141}
 B_CEIL = 0.1
 PLAIN_FACTOR, ROUTE_FACTOR = 1.25, 2.0
 
@@ -69,11 +98,11 @@ def capture_names(cfg):
     return names
 
 
-def read_captures(eng, cfg):
+def read_captures(eng, cfg, names=None):
     """name -> float32 [C, H, W] of the engine's last forward; names the route did not leave in memory are absent."""
     from wxengine.engine import WXEngineError
     caps = {}
-    for k in capture_names(cfg):
+    for k in capture_names(cfg) if names is None else names:
         try:
             caps[k] = eng.debug_read(k)
         except WXEngineError as e:
@@ -204,4 +233,134 @@ def encoder_captures(cfg, sd, x, dtype=torch.float32):
         z = O.cross_embed(z, sd, f"layers.{s}.0", list(cfg.cross_embed_kernel_sizes[s]), cfg.cross_embed_strides[s], getattr(cfg, "arch", "crossformer"))
         cap[f"layers.{s}.0"] = z
         z = O.transformer(z, sd, f"layers.{s}.1", cfg.depth[s], cfg.local_window_size[s], cfg.global_window_size[s], cfg.dim_head, cap)
+    return cap
+
+
+# --------------------------------------------------------------------------- #
+# CrossEmbed, decoder, tail
+# --------------------------------------------------------------------------- #
+UP_PARTS = ("ps", "up", "us", "c1", "n1", "c2")
+
+
+def decoder_form(cfg):
+    """"ps" (wxformer: conv3 + PixelShuffle + sharp), "upconv" (upsample + conv3) or "convt" (ConvTranspose)."""
+    if getattr(cfg, "arch", "crossformer") == "wxformer":
+        return "ps"
+    return "upconv" if getattr(cfg, "upsample_v_conv", False) else "convt"
+
+
+def conv_capture_names(cfg):
+    """Every capture a convolutional link can use."""
+    names = ["pad"] + [f"layers.{s}.{j}" for s in range(4) for j in (0, 1)]
+    for n in (1, 2, 3):
+        names += [f"up_block{n}"] + [f"up_block{n}.{k}" for k in UP_PARTS]
+    return names + ["up_block4", "up_block4.ps", "up_block4.us"]
+
+
+def conv_nd(x, sd, p, **kw):
+    """Conv2d of layer `p` in x's dtype."""
+    return F.conv2d(x, O.folded_weight(sd, p, x.dtype), O._bias(sd, p, x.dtype), **kw)
+
+
+def conv3(x, sd, p):
+    return conv_nd(x, sd, p, padding=1)
+
+
+def conv_t(x, sd, p, **kw):
+    return F.conv_transpose2d(x, O.folded_weight(sd, p, x.dtype), O._bias(sd, p, x.dtype), stride=2, **kw)
+
+
+Spec = namedtuple("Spec", "kind out ins base")     # ins: capture names; the kinds that read a concatenation list its parts in order
+
+
+def ref_gn(cfg, sd, p, x):
+    return O.group_norm_silu(x, O._as_t(sd[p + ".weight"], x.dtype), O._as_t(sd[p + ".bias"], x.dtype), cfg.dim[0])
+
+
+def ref_tail(cfg, z):
+    if cfg.pad_activate:
+        z = O.earth_unpad(z, cfg.pad_lat, cfg.pad_lon)
+    return O.bilinear_resize(z, cfg.image_height, cfg.image_width) if cfg.interp else z   # (fp32 index rule; the blend in z's dtype)
+
+
+def conv_link_specs(cfg, skip_embed0=False):
+    """The convolutional links of `cfg` in execution order."""
+    form = decoder_form(cfg)
+    specs = [Spec("embed", f"layers.{s}.0", ("pad" if s == 0 else f"layers.{s - 1}.1",), None) for s in range(0 + bool(skip_embed0), 4)]
+    for n in (1, 2, 3):
+        ub = f"up_block{n}"
+        x = ("layers.3.1",) if n == 1 else (f"up_block{n - 1}", f"layers.{4 - n}.1")
+        if form == "upconv":
+            specs += [Spec("us", ub + ".us", x, None), Spec("up", ub + ".up", (ub + ".us",), None)]
+        elif form == "ps":
+            specs += [Spec("up", ub + ".ps", x, None), Spec("sharp", ub + ".up", (ub + ".ps",), ub + ".ps")]
+        else:
+            specs.append(Spec("up", ub + ".up", x, None))
+        specs += [Spec("c1", ub + ".c1", (ub + ".up",), None), Spec("n1", ub + ".n1", (ub + ".c1",), None),
+                  Spec("c2", ub + ".c2", (ub + ".n1",), None), Spec("n2", ub, (ub + ".c2", ub + ".up"), ub + ".up")]
+    x = ("up_block3", "layers.0.1")
+    if form != "convt":
+        mid = "up_block4.ps" if form == "ps" else "up_block4.us"
+        specs += [Spec("head_ps" if form == "ps" else "head_us", mid, x, None), Spec("head_fin", "up_block4", (mid,), None)]
+    return specs + [Spec("head", "up_block4", x, None), Spec("tail", "y", ("up_block4",), None)]
+
+
+def conv_link_fn(cfg, sd, spec, ins):
+    """The oracle's function of one link on the tensors `ins` ([1, C, H, W], in their dtype)."""
+    form = decoder_form(cfg)
+    kind, ub = spec.kind, spec.out.split(".")[0]
+    if kind == "embed":
+        s = int(spec.out.split(".")[1])
+        return O.cross_embed(ins[0], sd, f"layers.{s}.0", list(cfg.cross_embed_kernel_sizes[s]), cfg.cross_embed_strides[s], getattr(cfg, "arch", "crossformer"))
+    if kind == "n1":
+        return ref_gn(cfg, sd, ub + ".b.1", ins[0])
+    if kind == "n2":
+        return ref_gn(cfg, sd, ub + ".b.4", ins[0]) + ins[1]
+    if kind == "tail":
+        return ref_tail(cfg, ins[0])
+    x = ins[0] if len(ins) == 1 else torch.cat(list(ins), dim=1)
+    if kind in ("us", "head_us"):
+        return O.upsample2x(x)
+    if kind == "up":
+        y = conv_t(x, sd, ub + ".conv") if form == "convt" else conv3(x, sd, ub + ".conv")
+        return O.pixel_shuffle2(y) if form == "ps" else y
+    if kind == "sharp":
+        return x + conv3(x, sd, ub + ".sharp")
+    if kind in ("c1", "c2"):
+        return conv3(x, sd, ub + (".b.0" if kind == "c1" else ".b.3"))
+    if kind == "head_ps":
+        return O.pixel_shuffle2(conv3(x, sd, "up_block4.0"))
+    if kind == "head_fin":
+        return conv3(x, sd, "up_block4.2" if form == "ps" else "up_block4.1")
+    assert kind == "head", kind
+    if form == "ps":
+        return conv3(O.pixel_shuffle2(conv3(x, sd, "up_block4.0")), sd, "up_block4.2")
+    return conv3(O.upsample2x(x), sd, "up_block4.1") if form == "upconv" else conv_t(x, sd, "up_block4", padding=1)
+
+
+def build_conv_links(cfg, sd, caps, prec, skip_embed0=False):
+    """Every convolutional link whose input(s) and output are in `caps` (name -> [C, H, W]; "y": forward's batch row 0 as
+    [C_out, H, W]), with its fp64 reference.  The references do not depend on `prec` (no scale is folded into a stored map here).
+    skip_embed0 leaves the stage-0 CrossEmbed out: on the 1-degree grid its k = 32 branch costs 3e10 fp64 MACs on the CPU, and the
+    small-map form of the patch kernel that it runs there is the one T1 and T0X run.  It is the only link ever left out."""
+    assert getattr(cfg, "noise_latent_dim", 0) <= 0, "ensemble (noise) configurations are not covered"
+    t = {}
+    links = []
+    for sp in conv_link_specs(cfg, skip_embed0):
+        if sp.out not in caps or any(k not in caps for k in sp.ins):
+            continue
+        for k in sp.ins + (sp.out,):
+            if k not in t:
+                t[k] = _t(caps[k])
+        links.append(Link(sp.kind, sp.out, t[sp.out], conv_link_fn(cfg, sd, sp, [t[k] for k in sp.ins]), None if sp.base is None else t[sp.base]))
+    return links
+
+
+def decoder_captures(cfg, sd, enc, dtype=torch.float32):
+    """The captures the oracle's functions make of the decoder, every stored intermediate and "y" included, from the encoder captures
+    `enc` ("layers.S.1" as [1, C, H, W]); returned together with those."""
+    cap = {k: v.to(dtype) for k, v in enc.items()}
+    for sp in conv_link_specs(cfg):
+        if sp.kind != "embed" and sp.out not in cap:     # ("head" after "head_fin": the same map)
+            cap[sp.out] = conv_link_fn(cfg, sd, sp, [cap[k] for k in sp.ins])
     return cap

@@ -11,7 +11,27 @@ bf16 gate the GPU test holds the fused routes to, and three faults of the kind a
 
 Each mutant's rel-L2 over the sub-block's output is printed next to its d: with base weights most of them sit under the 2e-2 the
 per-block norm gates allow for the sub-block's own output (that is the record of why this gate exists, not an assertion about the
-older tests)."""
+older tests).
+
+The convolutional links (CrossEmbed, UpBlocks, head, tail: teacher_forced.build_conv_links) get the same treatment on T0, T1 and
+the two other decoder forms of T0's geometry (T0W PixelShuffle, T0U upsample + conv).  Stand-in: the oracle's function of the link
+with bf16-rounded operand, weights and output in fp32 arithmetic, GroupNorm statistics in fp64; the tail in fp32 from the bf16 map,
+not rounded.  Every link is judged on its own: inputs = the oracle's own stream rounded to bf16.  Faults:
+
+  border   3x3 conv (c1, c2): the bottom tap row of the LAST output row reads the map's last row where it should read the zero
+           padding below the edge (a halo origin off by one row at the map border)
+  chunk    3x3 conv: the last 8 pixels lose 32 input channels of the centre tap (a ragged tile that skips a K step)
+  gn_tail  GroupNorm (n1, n2): the statistics leave out the pixels beyond the last full 128-row tile (partials of a ragged tile
+           dropped); applied where the map is no multiple of 128 pixels and has at least one full tile.  It moves every pixel, so
+           there are no faulty pixels to name
+  scatter  ConvTranspose-k2 / PixelShuffle `up` link: dy and dx swapped in the 2 x 2 scatter of the last input column
+  lerp     tail: i1 = i0 on the last output row THAT INTERPOLATES.  (On the very last output row the index rule already clamps i1 to
+           i0 whenever the map is enlarged -- every configuration here -- so there the fault named in the first place changes nothing.)
+
+The tail is held to FP32_TOL per pixel row (fp32_row_excess), everything else to ROUTE_FACTOR x B_PLAIN_CONV = 0.0282.  Figures: the
+stand-in needs d = 0.0089 on T0 and T1, 0.0144 / 0.0117 on T0W / T0U (their `head` link: two launches with a stored map between them),
+1.2e-7 on the tail; the weakest mutants reach scatter 3.7, border 1.55, chunk 0.52, gn_tail 0.079 (T1, up_block2: 32 of 800 pixels left
+out), lerp 3.8e-2 of max_row|ref| -- at a rel-L2 of the link's output of 1e-2 - 4e-2 for chunk, gn_tail and lerp."""
 import math
 
 import pytest
@@ -140,6 +160,199 @@ def test_links_of_the_oracles_own_stream_are_exact(prec):
     links += TF.build_links(cfg, sd, as_np({k: v for k, v in full.items() if k not in attn_outs}), prec)
     kinds = [k.kind for k in links]
     assert kinds.count("attn") == n_pairs and kinds.count("out+ff") == n_pairs, kinds
+    for k in links:
+        assert TF.link_distance(k, 0.0).d <= 1e-10, (k.kind, k.out)
+        assert TF.fp32_row_excess(k)[0] <= 1e-12, (k.kind, k.out)
+
+
+# --------------------------------------------------------------------------- #
+# CrossEmbed, decoder, tail
+# --------------------------------------------------------------------------- #
+F32 = torch.float32
+CONV_MUTANTS = {"border": ("c1", "c2"), "chunk": ("c1", "c2"), "gn_tail": ("n1", "n2"), "scatter": ("up",), "lerp": ("tail",)}
+
+
+def _sd_bf16(sd):
+    """The state dict a bf16 engine computes with: every convolution's folded weight rounded to bf16 (biases, GroupNorm affines fp32)."""
+    out = {}
+    for k, v in sd.items():
+        if k.endswith(".weight_orig"):
+            out[k[:-5]] = _bf(O.folded_weight(sd, k[:-12])).numpy()
+        elif not k.endswith((".weight_u", ".weight_v")):
+            t = O._as_t(v, F32)
+            out[k] = (_bf(t) if t.dim() == 4 else t).numpy()
+    return out
+
+
+def _axis32(n_in, n_out):
+    d = torch.arange(n_out, dtype=F32)
+    scale = torch.tensor(n_in, dtype=F32) / torch.tensor(n_out, dtype=F32)
+    src = (scale.double() * (d + 0.5).double() - 0.5).float().clamp(min=0.0)     # the oracle's index rule (bilinear_resize)
+    i0 = torch.floor(src).long().clamp(max=n_in - 1)
+    return i0, (i0 + 1).clamp(max=n_in - 1), src - i0.float()
+
+
+def _lerp_row(cfg, z):
+    """The last output row whose i1 differs from i0 under the correct rule."""
+    i0, i1, _ = _axis32(z.shape[-2] - sum(cfg.pad_lat), cfg.image_height)
+    return int((i1 != i0).nonzero().max())
+
+
+def _tail32(cfg, z, mutant=None):
+    z = O.earth_unpad(z, cfg.pad_lat, cfg.pad_lon)
+    r0, r1, lr = _axis32(z.shape[-2], cfg.image_height)
+    c0, c1, lc = _axis32(z.shape[-1], cfg.image_width)
+    if mutant == "lerp":
+        r1 = r1.clone()
+        row = int((r1 != r0).nonzero().max())
+        r1[row] = r0[row]
+    rows = z[..., r0, :] * (1 - lr).view(-1, 1) + z[..., r1, :] * lr.view(-1, 1)
+    return rows[..., c0] * (1 - lc) + rows[..., c1] * lc
+
+
+def _gn32(x, g, b, groups, res, mutant=None):
+    """GroupNorm + SiLU (+ shortcut) on the fp32 map x: statistics in fp64, the rest in fp32."""
+    _, c, h, w = x.shape
+    m = h * w
+    xs = x.double().reshape(1, groups, c // groups, m)
+    if mutant == "gn_tail":
+        xs = xs[..., : m // 128 * 128]
+    mean = xs.mean(dim=(2, 3))
+    var = (xs ** 2).mean(dim=(2, 3)) - mean ** 2
+    a = (1.0 / torch.sqrt(var + 1e-5)).repeat_interleave(c // groups, dim=1).view(1, c, 1, 1)
+    mu = mean.repeat_interleave(c // groups, dim=1).view(1, c, 1, 1)
+    y = (x - mu.float()) * a.float() * g.view(1, c, 1, 1) + b.view(1, c, 1, 1)
+    y = y * torch.sigmoid(y)
+    return y if res is None else y + res
+
+
+def _conv_standin(cfg, sdb, sp, ins, mutant=None):
+    """One link in a bf16 kernel's arithmetic: ins = fp32 tensors holding bf16 values -> the stored output as fp64."""
+    form = TF.decoder_form(cfg)
+    ub = sp.out.split(".")[0]
+    if sp.kind == "tail":
+        return _tail32(cfg, ins[0], mutant).double()       # fp32 out of a stored map: not rounded
+    if sp.kind in ("n1", "n2"):
+        q = ub + (".b.1" if sp.kind == "n1" else ".b.4")
+        return _bf(_gn32(ins[0], O._as_t(sdb[q + ".weight"], F32), O._as_t(sdb[q + ".bias"], F32), cfg.dim[0],
+                         ins[1] if sp.kind == "n2" else None, mutant)).double()
+    if sp.kind == "head" and form != "convt":              # two launches: the shuffled / upsampled map is stored in between
+        specs = {k.kind: k for k in TF.conv_link_specs(cfg)}
+        mid = _bf(TF.conv_link_fn(cfg, sdb, specs["head_ps" if form == "ps" else "head_us"], ins))
+        return _bf(TF.conv_link_fn(cfg, sdb, specs["head_fin"], [mid])).double()
+    y = TF.conv_link_fn(cfg, sdb, sp, ins).clone()
+    if mutant in ("border", "chunk"):
+        x = ins[0]
+        wgt = O.folded_weight(sdb, ub + (".b.0" if sp.kind == "c1" else ".b.3"), F32)
+        if mutant == "border":
+            y[:, :, -1:, :] += F.conv2d(x[:, :, -1:, :], wgt[:, :, 2:3, :], padding=(0, 1))
+        else:
+            y[0, :, -1, -8:] -= wgt[:, :32, 1, 1] @ x[0, :32, -1, -8:]
+    if mutant == "scatter":
+        _, c, h2, _ = y.shape
+        y[..., -2:] = y[..., -2:].reshape(1, c, h2 // 2, 2, 2).transpose(-1, -2).reshape(1, c, h2, 2)
+    return _bf(y).double()
+
+
+@pytest.fixture(scope="module", params=["T0", "T1", "T0W", "T0U"])
+def conv_stream(request):
+    """(config, weights, bf16 weights, the oracle's fp32 captures of the whole forward rounded to bf16 -- "y" fp32)."""
+    cfg = named_config(request.param)
+    sd = synth_state_dict(cfg)
+    cap = {}
+    O.forward(cfg, sd, synth_input(cfg), capture=cap)
+    cap = TF.decoder_captures(cfg, sd, {k: v[:1] for k, v in cap.items()})
+    return request.param, cfg, sd, _sd_bf16(sd), {k: _bf(v) for k, v in cap.items()}
+
+
+def _conv_gate():
+    b = TF.B_PLAIN_CONV["base"]
+    assert b is not None and 0 < TF.ROUTE_FACTOR * b <= TF.B_CEIL, b
+    return TF.ROUTE_FACTOR * b
+
+
+def _one_link(cfg, sd, sp, ins, got):
+    """The link `sp` through build_conv_links, from captures that hold nothing but its inputs and its output."""
+    caps = {k: v[0].numpy() for k, v in zip(sp.ins, ins)}
+    caps[sp.out] = got[0].numpy()
+    links = [k for k in TF.build_conv_links(cfg, sd, caps, "bf16") if k.kind == sp.kind]
+    assert len(links) == 1 and links[0].out == sp.out, (sp, [k.kind for k in links])
+    return links[0]
+
+
+def test_conv_gate_is_recorded_and_under_its_ceiling():
+    _conv_gate()
+
+
+def test_conv_standin_passes_and_every_mutant_fails(conv_stream):
+    name, cfg, sd, sdb, cap = conv_stream
+    gate = _conv_gate()
+    worst_ok, worst_tail, weakest, applied = 0.0, 0.0, {}, set()
+    for sp in TF.conv_link_specs(cfg):
+        ins = [cap[k] for k in sp.ins]
+        link = _one_link(cfg, sd, sp, ins, _conv_standin(cfg, sdb, sp, ins))
+        _, _, h, w = link.ref.shape
+        if sp.kind == "tail":
+            e, tok = TF.fp32_row_excess(link)
+            worst_tail = max(worst_tail, e)
+            assert e <= TF.FP32_TOL, f"{name} tail: the stand-in needs {e:.3e} at pixel {tok}"
+        else:
+            d_ok = TF.link_distance(link, TF.A_BF16)
+            worst_ok = max(worst_ok, d_ok.d)
+            assert d_ok.d <= gate, f"{name} {sp.kind} -> {sp.out}: the unmutated stand-in needs d = {d_ok.d:.4f} > {gate:.4f} (channel {d_ok.channel}, pixel {d_ok.token})"
+        for mut, kinds in CONV_MUTANTS.items():
+            if sp.kind not in kinds:
+                continue
+            if mut == "gn_tail" and (h * w < 128 or h * w % 128 == 0):
+                continue    # no full tile / no ragged one: the fault does not exist on this map
+            if mut == "scatter" and TF.decoder_form(cfg) == "upconv":
+                continue    # no scatter: its `up` is a 3x3 conv
+            bad = _one_link(cfg, sd, sp, ins, _conv_standin(cfg, sdb, sp, ins, mut))
+            l2 = TF.rel_l2(bad.got, bad.ref)
+            applied.add(mut)
+            if mut == "lerp":
+                e, tok = TF.fp32_row_excess(bad)
+                print(f"[teacher-forced cpu] {name} tail {h}x{w}: stand-in {worst_tail:.2e} | mutant lerp: row error {e:.3e} at pixel {tok} (row {tok // w}), rel-L2 {l2:.2e}")
+                assert e > TF.FP32_TOL, f"{name}: mutant 'lerp' passes the tail's tolerance ({e:.3e})"
+                assert tok // w == _lerp_row(cfg, ins[0]), (tok, w)
+                weakest[mut] = min(weakest.get(mut, math.inf), e)
+                continue
+            r = TF.link_distance(bad, TF.A_BF16)
+            print(f"[teacher-forced cpu] {name} {sp.kind} -> {sp.out} C={bad.ref.shape[1]} {h}x{w}: stand-in d {d_ok.d:.4f} | "
+                  f"mutant {mut}: d {r.d:.3f} at pixel {r.token}, rel-L2 of the link's output {l2:.2e}")
+            assert r.d > gate, f"{name} {sp.kind} -> {sp.out}: mutant '{mut}' passes the gate (d = {r.d:.4f} <= {gate:.4f})"
+            if mut == "border":
+                assert r.token >= (h - 1) * w, (mut, r.token)
+            elif mut == "chunk":
+                assert r.token >= h * w - 8, (mut, r.token)
+            elif mut == "scatter":
+                assert r.token % w >= w - 2, (mut, r.token)
+            weakest[mut] = min(weakest.get(mut, math.inf), r.d)
+    want = set(CONV_MUTANTS) - ({"scatter"} if TF.decoder_form(cfg) == "upconv" else set())
+    assert applied == want, (applied, want)
+    print(f"[teacher-forced cpu] {name} conv links: stand-in worst d {worst_ok:.4f} (gate {gate:.4f}), tail {worst_tail:.2e}; weakest mutants " +
+          ", ".join(f"{m} {v:.3g}" for m, v in weakest.items()))
+
+
+@pytest.mark.parametrize("name", ["T0", "T1", "T0W", "T0U"])
+def test_conv_links_of_the_oracles_own_stream_are_exact(name):
+    """The references themselves: the decoder rebuilt link by link from the oracle's fp64 functions must (a) compose to the oracle's
+    own up_block / up_block_ps, head and forward, and (b) come back from build_conv_links with d = 0 on every link."""
+    cfg = named_config(name)
+    sd = synth_state_dict(cfg)
+    cap = {}
+    y = O.forward(cfg, sd, synth_input(cfg), torch.float64, capture=cap)
+    cap = {k: v[:1] for k, v in cap.items()}
+    dec = TF.decoder_captures(cfg, sd, cap, torch.float64)
+    for k in ("up_block1", "up_block2", "up_block3", "up_block4"):
+        assert float((dec[k] - cap[k]).abs().max()) <= 1e-12 * float(cap[k].abs().max()), k
+    y0 = y[0].reshape(1, -1, y.shape[-2], y.shape[-1])
+    assert dec["y"].shape == y0.shape and float((dec["y"] - y0).abs().max()) <= 1e-12 * float(y0.abs().max())
+    specs = TF.conv_link_specs(cfg)
+    assert set(TF.conv_capture_names(cfg)) >= {k for sp in specs for k in sp.ins + (sp.out,)} - {"y"}
+    links = TF.build_conv_links(cfg, sd, {k: v[0].numpy() for k, v in dec.items()}, "bf16")
+    assert [k.kind for k in links] == [sp.kind for sp in specs] and len(links) >= 4 + 3 * 5 + 2
+    assert len(TF.build_conv_links(cfg, sd, {k: v[0].numpy() for k, v in dec.items()}, "bf16", skip_embed0=True)) == len(links) - 1
     for k in links:
         assert TF.link_distance(k, 0.0).d <= 1e-10, (k.kind, k.out)
         assert TF.fp32_row_excess(k)[0] <= 1e-12, (k.kind, k.out)
