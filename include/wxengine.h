@@ -630,6 +630,36 @@ int wx_perturb_apply(wx_perturb_handle h, int n_planes, const float* tape_dev, u
                      const float* x_dev, int64_t x_stride, float* delta_out_dev, int64_t delta_stride, float* x_out_dev, int64_t x_out_stride,
                      void* stream);
 
+/* ---- zonal power spectra on the device (csrc/wx_spectrum.h) ---------------------------------------------------------------------------
+ * credit/losses/gen_1/power.py::PSDLoss (get_psd and forward) and spectral.py::SpectralLoss2D: the per-latitude DFT along longitude of
+ * P planes of a float32 field a and, optionally, of a second field b of the same shape, by a dense fp64 DFT on the matrix cores with the
+ * real input folded (half the products), in place of a copy of the fields to the host and torch.fft in float32 there.  Wh = W / 2 + 1,
+ * X_k = sum_x r[x] e^{-2 pi i k x / W}, mult_k = 1 for k = 0 and 2 for every other bin (the Nyquist bin of an even W too: the reference's).
+ *   wx_spectrum_create / wx_spectrum_destroy: the grid and the latitude weights.  lat_w_host: HOST array [H] or NULL (w = 1).
+ *                         WX_ERR_INVALID with the reason: H or W < 2; W > 4096 (the twiddle table lies in LDS); a weight that is not
+ *                         finite or is negative; weights that sum to zero.
+ *   wx_spectrum_apply     plane p of a (of b) at a_dev + p * a_stride floats (stride >= H * W), [H][W] contiguous, read where it lies
+ *                         and never modified; b_dev may be NULL.  Every output is DEVICE memory, written completely, or NULL (not wanted):
+ *       psd_a_dev, psd_b_dev             [n_planes][H][Wh] float32: mult_k |X_k|^2 / W^2 (PSDLoss.get_psd), rounded once from fp64
+ *       mean_psd_a_dev, mean_psd_b_dev   [n_planes][Wh] float64: sum_h what_h psd[h][k], what = w / sum(w) (1 / H without weights)
+ *       mean_amp_a_dev, mean_amp_b_dev   [n_planes][Wh] float64: (sum_h w_h |X_k|) / H -- SpectralLoss2D divides by H, not by sum(w)
+ *       scores_dev                       [n_planes][2] float64, over the bins k_init <= k < Wh:
+ *                                          [0] mean_k sum_h what_h (log(psd_a + 1e-8) - log(psd_b + 1e-8))^2     (PSDLoss per plane)
+ *                                          [1] mean_k (mean_amp_a[k] - mean_amp_b[k])^2                           (SpectralLoss2D per plane)
+ *                                        the reference's two scalar losses are the means of these over the planes
+ *     WX_ERR_INVALID with the reason, nothing launched or written: a null handle or a null a; n_planes < 1; a stride below H * W or
+ *     one that takes the planes beyond 2^44 floats; k_init < 0 or >= Wh; a scores pointer, or any output of b, without b; no output at
+ *     all; an output that overlaps an input or another output.
+ *     Two launches per call, every sum in fp64 in one fixed order, no atomics: a plane's outputs are bit-identical whatever n_planes, the
+ *     split of the planes into calls and the plane's position, and the outputs of a are the same with and without b.  The scratch is
+ *     the handle's own and grows only in a call with more tiles than any before: calls on one handle must be ordered by one stream. */
+typedef struct wx_spectrum* wx_spectrum_handle;
+int wx_spectrum_create(int H, int W, const float* lat_w_host, int device, wx_spectrum_handle* out);
+int wx_spectrum_destroy(wx_spectrum_handle h);
+int wx_spectrum_apply(wx_spectrum_handle h, int n_planes, const float* a_dev, int64_t a_stride, const float* b_dev, int64_t b_stride, int k_init,
+                      float* psd_a_dev, float* psd_b_dev, double* mean_psd_a_dev, double* mean_psd_b_dev, double* mean_amp_a_dev,
+                      double* mean_amp_b_dev, double* scores_dev, void* stream);
+
 /* ---- verification metrics on the device (csrc/wx_metrics.h) ----------------------------------------------------------------------
  * credit/metrics/base.py, common.py, anomaly.py: the eight per-variable scores of the gen-2 metrics framework from ONE reduction
  * over prediction, target and climatology, in place of three to eight elementwise passes and a host sync per metric and variable.

@@ -471,6 +471,33 @@ int wx_perturb_apply(wx_perturb_handle h, int n_planes, const float* tape_dev, u
     });
   });
 }
+// ---- zonal power spectra (PSD, latitude-mean spectra and the two spectral scores from a folded fp64 DFT; csrc/wx_spectrum.h) -------
+struct wx_spectrum {
+  std::unique_ptr<wx::Spectrum> impl;
+};
+int wx_spectrum_create(int H, int W, const float* lat_w_host, int device, wx_spectrum_handle* out) {
+  return guarded([&] {
+    if (!out) throw wx::ConfigError("wx_spectrum_create: null argument");
+    const std::string why = wx::spectrum_check_create(H, W, lat_w_host);   // needs no device to be told
+    if (!why.empty()) throw wx::ConfigError("wx_spectrum_create: " + why);
+    need_device(device, "wx_spectrum_create");
+    std::unique_ptr<wx_spectrum> h(new wx_spectrum);
+    h->impl.reset(new wx::Spectrum(H, W, lat_w_host, device));
+    *out = h.release();
+  });
+}
+int wx_spectrum_destroy(wx_spectrum_handle h) { return guarded([&] { delete h; }); }
+int wx_spectrum_apply(wx_spectrum_handle h, int n_planes, const float* a_dev, int64_t a_stride, const float* b_dev, int64_t b_stride, int k_init,
+                      float* psd_a_dev, float* psd_b_dev, double* mean_psd_a_dev, double* mean_psd_b_dev, double* mean_amp_a_dev,
+                      double* mean_amp_b_dev, double* scores_dev, void* stream) {
+  return guarded([&] {
+    if (!h || !h->impl) throw wx::ConfigError("wx_spectrum_apply: null spectrum handle");
+    remap<wx::ConfigError>([&] {
+      h->impl->apply(n_planes, a_dev, a_stride, b_dev, b_stride, k_init, psd_a_dev, psd_b_dev, mean_psd_a_dev, mean_psd_b_dev, mean_amp_a_dev,
+                     mean_amp_b_dev, scores_dev, (hipStream_t)stream);
+    });
+  });
+}
 // ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
 struct wx_metrics {
   std::unique_ptr<wx::Metrics> impl;

@@ -45,6 +45,7 @@
 #include "wx_regrid.h"
 #include "wx_tisr.h"
 #include "wx_perturb.h"
+#include "wx_spectrum.h"
 #include "wx_metrics.h"
 #include "wx_ensemble.h"
 #include "wx_noise.h"

@@ -6,6 +6,7 @@
 // shapes alone decide:
 //   in a thread    whatever the caller's loop does (thread-strided over the tile, or over the slots of an earlier launch: sum_slots)
 //   in a wave      wave_sum: a shuffle-down tree 32, 16, .. 1 -- lane i adds lane i + off -- the result in lane 0
+//                  (wave_sum_groups: its steps 32 and 16 alone, one result per lane position 0 .. 15)
 //   in a workgroup either block_sum_waves: wave_sum, then the waves added 0, 1, 2, .. by one thread per sum
 //                  or     block_sum_tree:  a halving tree 128, 64, .. 1 over 256 threads in LDS -- thread i adds thread i + half
 //   across workgroups  each writes its sums to a slot of its own; a LATER launch adds the slots with the pieces above.  No hand-off
@@ -88,6 +89,17 @@ __device__ __forceinline__ void wave_sum(double (&acc)[K]) {
   for (int k = 0; k < K; ++k) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
+  }
+}
+
+// the K sums over the four 16-lane groups of the wave, per lane position: lane c < 16 ends with lanes c, c + 16, c + 32, c + 48 --
+// the first two steps of wave_sum's tree (the rows of an MFMA accumulator column; wx_spectrum.h)
+template <int K>
+__device__ __forceinline__ void wave_sum_groups(double (&acc)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int off = 32; off >= 16; off >>= 1) acc[k] += __shfl_down(acc[k], off, 64);
   }
 }
 

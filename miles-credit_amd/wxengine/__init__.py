@@ -12,6 +12,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   perturb           perturbed-initial-condition ensembles: white, colour-filtered and AR(1) noise on a member's planes (GaussianNoise, ColorNoise, TemporalNoise, hemispheric_weights, exported here)
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
+  spectrum          zonal power spectra, PSD / latitude-mean spectra / spectral scores from a folded fp64 DFT (ZonalSpectrum, PendingSpectra, SpectrumResult, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
 There is no CPU fallback: without the HIP library or a GPU, construction raises.
 """
@@ -42,4 +43,7 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name in ("EnsembleVerification", "PendingEnsembleScores", "EnsembleScores"):
         from . import ensemble_metrics
         return getattr(ensemble_metrics, name)
+    if name in ("ZonalSpectrum", "PendingSpectra", "SpectrumResult"):
+        from . import spectrum
+        return getattr(spectrum, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

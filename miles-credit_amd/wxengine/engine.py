@@ -157,6 +157,10 @@ _PROTOTYPES = {
     "wx_perturb_batch": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
     "wx_perturb_apply": ([C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_float, C.c_void_p,
                           C.c_int64, C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "wx_spectrum_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_spectrum_destroy": ([C.c_void_p], C.c_int),
+    "wx_spectrum_apply": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p],
+                          C.c_int),
     "wx_metrics_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
     "wx_metrics_destroy": ([C.c_void_p], C.c_int),
     "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),

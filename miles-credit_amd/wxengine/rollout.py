@@ -200,3 +200,20 @@ def score_ensemble_rollout(out, targets, verifier, channel_map):
         target = targets[step]
         pending.append(verifier.submit([split(member[step]) for member in out], target if isinstance(target, dict) else split(target)))
     return pending
+
+
+def spectra_of_rollout(out, targets, spectrum, channel_map, wavenum_init=20):
+    """The zonal spectra of the per-step output of a rollout against the truth, where the output lies: every step is submitted to
+    `spectrum` (a spectrum.ZonalSpectrum) without a host sync, the variables read as channel slices of the step's buffer.
+
+    out[step]: a [1, C, H, W] tensor; channel_map as for score_ensemble_rollout (a variable of n channels is n planes);
+    targets[step]: a [1, C, H, W] tensor in the output's channel layout, or {var_key: [1, L, 1, H, W]}.
+    Returns the list of PendingSpectra, one per step; call result() on them after the loop: {var_key: SpectrumResult}."""
+    if len(targets) != len(out):
+        raise ValueError("spectra_of_rollout: the output and the targets must have one entry per step")
+    slices = {k: (v["slice"] if isinstance(v, dict) else v) for k, v in channel_map.items()}
+    split = lambda y: {k: y[:, sl].unsqueeze(2) for k, sl in slices.items()}      # noqa: E731  [1, L, H, W] -> [1, L, 1, H, W] views
+    pending = []
+    for y, target in zip(out, targets):
+        pending.append(spectrum.submit(split(y), target if isinstance(target, dict) else split(target), wavenum_init))
+    return pending
