@@ -798,31 +798,97 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     ln_stats(x, ld, c, m);
     return rowstat;
   }
-  // defer_out: leave the attention output in attn_o; the fused feed-forward kernel applies to_out + residual itself
-  // qkv_ready: the previous fused feed-forward kernel already wrote this attention's q|k|v into `scratch`
-  // the whole attention sub-block in one launch?  (bf16 engine, C = 128 / 256, unsharded maps; q|k|v and the attention output never
-  // exist in memory on this path: a debug run captures the sub-block's output only)
-  bool attn_block_ok(const AttnL& a, const StageView& v) const {
-    const int s = v.s;
-    if (sizeof(T) != 2 || !opt.attn_block || band_on || a.bias_tb < 0 || cfg.dim_head != 32) return false;
-    if (opt.attn_block == 2) {
-      const bool big_s0 = cfg.dim[s] == 128 && attn_nkf(a.wsz) == 7 && (int64_t)(v.h / a.wsz) * (v.w / a.wsz) >= 2048;
-      const bool small_map = small_map_tokens(s);   // launch-bound maps (1-degree model): one launch instead of three
-      if (!big_s0 && !small_map) return false;
-    }
-    // 2 x 2 windows: one 16-token fragment per window loses even on launch-bound maps (37 us against 26 for the three launches); four
-    // windows per fragment (AttnBlockParams::pack) win there
-    if (a.wsz == 2 && !(opt.attn_pack2 && small_map_tokens(s) && ((v.h / 2) * (v.w / 2)) % 4 == 0)) return false;
-    return a.wsz > 1 && attn_block_supported(cfg.dim[s], a.wsz, true) &&
-           (a.kind == 0 || a.kind == 1) && a.qkv.cin == cfg.dim[s] && a.out.cin == cfg.dim[s];
+  // ------------------------------------------------------------------ the route of one (attention, FeedForward) pair
+  // The fused feed-forward kernel gives every workgroup 128 (C = 128) or 64 (C = 256) pixels: below one workgroup per CU the
+  // plain GEMM chain fills the chip better (1-degree model: 45 and 22 workgroups; 507 -> 527 steps/s without the fusion)
+  bool ff_big_enough(const StageView& v) const {
+    const int64_t m = (int64_t)v.h * v.w;
+    // C = 128 on a launch-bound map (1-degree grid stage 1: 45 workgroups): one launch instead of two wins from 40 workgroups on
+    // (724 -> 729 steps/s); C = 256 at 23 workgroups loses (710)
+    if (cfg.dim[v.s] == 128 || cfg.dim[v.s] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
+    return cdiv(m, 64) >= opt.ff_min_wgs;
   }
-  void attention(const AttnL& a, const StageView& v, const std::string& dbg_name, bool defer_out = false, bool qkv_ready = false) {
+  // split-bf16 precision: the one-launch FeedForward (wx_ff_split.h) of this layer
+  bool ff_split_fused_ok(const FFL& f, int c) const {
+    return sizeof(T) == 4 && split_mma && opt.ff_split_fused && !opt.dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || opt.ff_split_256) && f.w1.cin == c &&
+           f.w2.cin == 4 * c && f.w1.kh == 1 && f.w2.kh == 1 && f.w1.bias >= 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
+  }
+  // the form of a FeedForward (feedforward() below):
+  //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
+  //               attention's LayerNorm + to_qkv behind) form
+  //   split       bf16, launch-bound maps: the fused block with its hidden dimension split, and the split-K finish kernel
+  //   split_bf16  split-bf16 precision, C = 128 / 256: both layers in one launch (wx_ff_split.h), plain / PRE / POST
+  //   chain       ff1 + ff2 on gemm()
+  enum class FFForm { fused, split, split_bf16, chain };
+  // what attention() and feedforward() run for one pair; plan_pair() is the only place that decides it
+  struct PairPlan {
+    enum class Attn { vonly, block, chain } attn = Attn::chain;   // wsz == 1: V-only GEMM; wx_attn_block.h; to_qkv -> window_attn -> to_out
+    bool qkv_ready = false;     // q|k|v already lie in `scratch` (the previous pair's POST form wrote them)
+    bool attn_kblk = false;     // chain on the k-blocked layouts (KBlk::attn)
+    FFForm ff = FFForm::chain;
+    bool pre = false;           // the attention leaves its output in attn_o; the FeedForward applies to_out + residual itself ...
+    bool post = false;          // ... and the next attention's LayerNorm + to_qkv (the next pair's qkv_ready)
+    bool hidden_kblk = false;   // chain: hidden tensor k-blocked (KBlk::hidden)
+  };
+  // A pure function of the layer tables, the view, opt / cfg / precision, band_on and the capture level -- of nothing a launch changes
+  // (stat_tiles_ready: the decisions that need it stay where they execute).  Resolved in the order block, pre, form, post, attn_kblk,
+  // hidden_kblk: each may use the ones before it (the bf16 `split` form needs `pre` known).
+  PairPlan plan_pair(const AttnL& a, const FFL& f, const StageView& v, bool qkv_ready) const {
+    const int s = v.s, c = cfg.dim[s];
+    const int64_t m = (int64_t)v.h * v.w;
+    // the whole attention sub-block in one launch?  (bf16 engine, C = 128 / 256, unsharded maps; q|k|v and the attention output never
+    // exist in memory on this path: a debug run captures the sub-block's output only)
+    auto block = [&](const AttnL& a) {   // (also asked of the NEXT attention, f.next, by `post`)
+      if (sizeof(T) != 2 || !opt.attn_block || band_on || a.bias_tb < 0 || cfg.dim_head != 32) return false;
+      if (opt.attn_block == 2) {
+        const bool big_s0 = cfg.dim[s] == 128 && attn_nkf(a.wsz) == 7 && (int64_t)(v.h / a.wsz) * (v.w / a.wsz) >= 2048;
+        const bool small_map = small_map_tokens(s);   // launch-bound maps (1-degree model): one launch instead of three
+        if (!big_s0 && !small_map) return false;
+      }
+      // 2 x 2 windows: one 16-token fragment per window loses even on launch-bound maps (37 us against 26 for the three launches); four
+      // windows per fragment (AttnBlockParams::pack) win there
+      if (a.wsz == 2 && !(opt.attn_pack2 && small_map_tokens(s) && ((v.h / 2) * (v.w / 2)) % 4 == 0)) return false;
+      return a.wsz > 1 && attn_block_supported(cfg.dim[s], a.wsz, true) &&
+             (a.kind == 0 || a.kind == 1) && a.qkv.cin == cfg.dim[s] && a.out.cin == cfg.dim[s];
+    };
+    PairPlan p;
+    p.qkv_ready = qkv_ready;
+    p.attn = block(a) ? PairPlan::Attn::block : a.wsz == 1 ? PairPlan::Attn::vonly : PairPlan::Attn::chain;
+    if constexpr (sizeof(T) == 2) {
+      p.pre = opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_unfuse && ff_big_enough(v) && cfg.dim_head == 32 && p.attn != PairPlan::Attn::block;
+      if (opt.ff_split_max >= 2 && !p.pre && f.pack >= 0 && opt.fuse_ff && opt.fuse_ln && !band_on && !opt.dbg_flags &&
+          ff_fused_supported(c, 4 * c) && small_map_tokens(s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= opt.ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0)
+        p.ff = FFForm::split;
+      else if (f.pack >= 0 && opt.fuse_ff && ff_big_enough(v)) p.ff = FFForm::fused;
+      p.post = p.pre && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && block(*f.next));
+    } else {
+      // split-bf16 precision: the one-launch form, whether it also applies the attention's out-projection + residual in front (its PRE
+      // form: to_out's launch, the write of x1 by one kernel and its read by the next are gone), and the to_qkv tail (its POST form)
+      const bool one = ff_split_fused_ok(f, c);
+      if (one) p.ff = FFForm::split_bf16;
+      p.pre = one && opt.ff_split_pre && opt.fuse_ln && !dbg_unfuse && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
+      if (p.pre && f.next) {
+        const ConvW& q = f.next->qkv;
+        p.post = one && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_unfuse && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
+                 q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
+      }
+    }
+    // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
+    // k-blocked (see KBlk); outputs bitwise the row-major chain's
+    p.attn_kblk = p.attn == PairPlan::Attn::chain && sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_unfuse &&
+                  !band_on && cfg.dim_head == 32 && !p.qkv_ready && !p.pre && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) &&
+                  m >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0;
+    // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
+    p.hidden_kblk = p.ff == FFForm::chain && sizeof(T) == 2 && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 &&
+                    c == 512 && m >= opt.stream_min_rows && f.w2.bias >= 0;
+    return p;
+  }
+  void attention(const AttnL& a, const StageView& v, const std::string& dbg_name, const PairPlan& pl) {
     const int c = cfg.dim[v.s], h = v.h, w = v.w, m = h * w;
     const int64_t ld = v.ld;
     T* x = v.x;
     if constexpr (sizeof(T) == 2) {
-      if (attn_block_ok(a, v)) {
-        if (defer_out || qkv_ready) throw StateError("attention block: the fused feed-forward variants must be off for this layer");
+      if (pl.attn == PairPlan::Attn::block) {
         AttnBlockParams bp;
         bp.x = reinterpret_cast<bf16_t*>(x); bp.ld = ld;
         bp.wqkv = reinterpret_cast<const bf16_t*>(wt_dev + a.qkv.wt); bp.csq = f_dev + a.qkv.colsum; bp.bq = f_dev + a.qkv.bias;
@@ -838,20 +904,13 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         return;
       }
     }
-    const float2* rs = qkv_ready ? nullptr : stream_stats(x, ld, c, m);
-    KBlk blk = KBlk::none;
-    if (a.wsz == 1) {
+    const float2* rs = pl.qkv_ready ? nullptr : stream_stats(x, ld, c, m);
+    const KBlk blk = pl.attn_kblk ? KBlk::attn : KBlk::none;
+    if (pl.attn == PairPlan::Attn::vonly) {
       gemm("gemm_qkv", a.vonly, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = attn_o, .out_ld = c, .rs = rs});
     } else {
-      // C >= 512 on large maps (stages 2 - 3 of the 0.25-degree model): the three launches exchange q|k|v and the attention output
-      // k-blocked (see KBlk); outputs bitwise the row-major chain's
-      if (sizeof(T) == 2 && opt.attn_blk_on && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && !dbg_unfuse && !band_on && cfg.dim_head == 32 &&
-          !qkv_ready && !defer_out && a.qkv.wt_kb >= 0 && a.out.wt_kb >= 0 && (c == 512 || c == 1024) && rs &&
-          m >= opt.stream_min_rows && a.out.bias >= 0 && a.qkv.colsum >= 0 && a.qkv.n % 256 == 0) {
-        blk = KBlk::attn;
-        ++n_attn_blk;
-      }
-      if (!qkv_ready) gemm("gemm_qkv", a.qkv, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 3 * c, .rs = rs, .blk = blk});
+      if (pl.attn_kblk) ++n_attn_blk;
+      if (!pl.qkv_ready) gemm("gemm_qkv", a.qkv, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 3 * c, .rs = rs, .blk = blk});
       AttnParams p;
       p.trace = nullptr;
       p.qkv = scratch; p.ld_qkv = 3 * c; p.out = attn_o; p.ld_out = c; p.bias = f_dev + a.bias_tab; p.tb = a.bias_tb >= 0 ? f_dev + a.bias_tb : nullptr;
@@ -869,74 +928,17 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       if (blk != KBlk::attn) capture(dbg_name + ".qkv", scratch, h, w, 3 * c, 3 * c, w);   // (k-blocked: not a [tokens][3C] map)
     }
     if (blk != KBlk::attn) capture(dbg_name + ".attn", attn_o, h, w, c, c, w);
-    if (defer_out) return;
+    if (pl.pre) return;   // attn_o stays for the FeedForward
     stat_tiles_ready = gemm("gemm_out", a.out, {.in = attn_o, .in_h = h, .in_w = w, .in_ld = c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
                                                 .blk = blk, .want_stats = true}).stat_slots;
     capture(dbg_name, x, h, w, c, ld, w);
   }
-  // The fused feed-forward kernel gives every workgroup 128 (C = 128) or 64 (C = 256) pixels: below one workgroup per CU the
-  // plain GEMM chain fills the chip better (1-degree model: 45 and 22 workgroups; 507 -> 527 steps/s without the fusion)
-  bool ff_big_enough(const StageView& v) const {
-    const int64_t m = (int64_t)v.h * v.w;
-    // C = 128 on a launch-bound map (1-degree grid stage 1: 45 workgroups): one launch instead of two wins from 40 workgroups on
-    // (724 -> 729 steps/s); C = 256 at 23 workgroups loses (710)
-    if (cfg.dim[v.s] == 128 || cfg.dim[v.s] == 64) return cdiv(m, 128) >= std::min(opt.ff_min_wgs, 40);
-    return cdiv(m, 64) >= opt.ff_min_wgs;
-  }
-  bool ff_takes_out(const FFL& f, const StageView& v) const { return sizeof(T) == 2 && opt.fuse_ff && opt.fuse_out && f.pack_pre >= 0 && !dbg_unfuse && ff_big_enough(v) && cfg.dim_head == 32; }
-  // split-bf16 precision: the one-launch FeedForward (wx_ff_split.h) of this layer ...
-  bool ff_split_fused_ok(const FFL& f, int c) const {
-    return sizeof(T) == 4 && split_mma && opt.ff_split_fused && !opt.dbg_flags && ws_dev && ff_split_supported(c, f.w1.n) && (c == 128 || opt.ff_split_256) && f.w1.cin == c &&
-           f.w2.cin == 4 * c && f.w1.kh == 1 && f.w2.kh == 1 && f.w1.bias >= 0 && f.w2.bias >= 0 && f.w1.colsum >= 0;
-  }
-  // ... and whether it also applies the attention's out-projection + residual in front (its PRE form: to_out's launch, the write of x1 by
-  // one kernel and its read by the next are gone)
-  bool ff_split_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
-    const int c = cfg.dim[v.s];
-    return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.fuse_ln && !dbg_unfuse && !band_on && a.out.cin == c && a.out.n == c && a.out.kh == 1 && a.out.kw == 1 && a.out.bias >= 0;
-  }
-  bool ff_takes_out(const FFL& f, const AttnL& a, const StageView& v) const {
-    if constexpr (sizeof(T) == 4) return ff_split_takes_out(f, a, v);
-    return ff_takes_out(f, v) && !attn_block_ok(a, v);
-  }
-  bool ff_makes_qkv(const FFL& f, const StageView& v) const {
-    if constexpr (sizeof(T) == 4) {   // split-bf16 precision: the to_qkv tail of the one-launch FeedForward (its POST form; rides on the PRE form)
-      if (!f.next) return false;
-      const int c = cfg.dim[v.s];
-      const ConvW& q = f.next->qkv;
-      return ff_split_fused_ok(f, c) && opt.ff_split_pre && opt.ff_split_post && opt.fuse_ln && !dbg_unfuse && !band_on && f.next->wsz > 1 && q.wt >= 0 && q.cin == c &&
-             q.n == 3 * c && q.kh == 1 && q.kw == 1 && q.bias >= 0 && q.colsum >= 0;
-    }
-    return ff_takes_out(f, v) && opt.fuse_qkv && f.pack_pp >= 0 && !band_on && !(f.next && attn_block_ok(*f.next, v));
-  }
-  bool ff_split_ok(const FFL& f, const StageView& v, const AttnL* pre) const {
-    const int c = cfg.dim[v.s];
-    const int64_t m = (int64_t)v.h * v.w;
-    return sizeof(T) == 2 && opt.ff_split_max >= 2 && !pre && f.pack >= 0 && opt.fuse_ff && opt.fuse_ln && !band_on && !opt.dbg_flags &&
-           ff_fused_supported(c, 4 * c) && small_map_tokens(v.s) && cdiv(m, (int64_t)(c == 128 ? 128 : 64)) <= opt.ff_split_tiles && f.w2.bias >= 0 && f.w1.colsum >= 0;
-  }
-  // the form of a FeedForward (feedforward() below):
-  //   fused       bf16: the one-launch block (wx_ff.h), in its plain, PRE (with the attention's to_out in front) or POST (and the next
-  //               attention's LayerNorm + to_qkv behind) form
-  //   split       bf16, launch-bound maps: the fused block with its hidden dimension split, and the split-K finish kernel
-  //   split_bf16  split-bf16 precision, C = 128 / 256: both layers in one launch (wx_ff_split.h), plain / PRE / POST
-  //   chain       ff1 + ff2 on gemm()
-  enum class FFForm { fused, split, split_bf16, chain };
-  FFForm ff_form(const FFL& f, const StageView& v, const AttnL* pre) const {
-    if (sizeof(T) == 2) {
-      if (ff_split_ok(f, v, pre)) return FFForm::split;
-      if (f.pack >= 0 && opt.fuse_ff && ff_big_enough(v)) return FFForm::fused;
-    } else if (ff_split_fused_ok(f, cfg.dim[v.s])) {
-      return FFForm::split_bf16;
-    }
-    return FFForm::chain;
-  }
-  void feedforward(const FFL& f, const StageView& v, const std::string& dbg_name, const AttnL* pre = nullptr) {
+  void feedforward(const AttnL& a, const FFL& f, const StageView& v, const std::string& dbg_name, const PairPlan& pl) {   // a: the pair's attention (PRE form: its to_out)
     const int c = cfg.dim[v.s], h = v.h, w = v.w, m = h * w;
     const int64_t ld = v.ld;
     T* x = v.x;
-    const FFForm form = ff_form(f, v, pre);
-    if (pre && form != FFForm::fused && form != FFForm::split_bf16) throw StateError("feedforward: out-projection deferred to a layer that cannot take it");
+    const FFForm form = pl.ff;
+    const bool pre = pl.pre, post = pl.post;
     if constexpr (sizeof(T) == 2) {
       auto block_params = [&](int64_t pack) {   // the one-launch block's operands
         FFParams fp{};
@@ -966,11 +968,10 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         stat_tiles_ready = conv_gemm_finish_slots(c);
       };
       if (form == FFForm::fused) {
-        const bool post = pre && ff_makes_qkv(f, v);
         FFParams fp = block_params(post ? f.pack_pp : pre ? f.pack_pre : f.pack);
         fp.qkv = post ? reinterpret_cast<bf16_t*>(scratch) : nullptr; fp.ld_qkv = 3 * c;
         fp.csq = post ? f_dev + f.next->qkv.colsum : nullptr; fp.bq = post ? f_dev + f.next->qkv.bias : nullptr;
-        fp.o = pre ? reinterpret_cast<const bf16_t*>(attn_o) : nullptr; fp.ld_o = c; fp.bo = pre ? f_dev + pre->out.bias : nullptr;
+        fp.o = pre ? reinterpret_cast<const bf16_t*>(attn_o) : nullptr; fp.ld_o = c; fp.bo = pre ? f_dev + a.out.bias : nullptr;
         fp.stat_out = opt.fuse_ln ? statpart : nullptr; fp.dbg = 0;
         timed(post ? "out_ff_qkv_fused" : pre ? "out_ff_fused" : "ff_fused", (post ? 24.0 : pre ? 18.0 : 16.0) * m * c * c, 2.0 * m * c * sizeof(T) + 16.0 * c * c, [&] { launch_ff_fused(c, fp, zero_page, cur_stream, /*px64=*/c == 128 && !pre && opt.ff_small_px64 && cdiv(m, 128) < 128); });
         stat_tiles_ready = opt.fuse_ln ? 1 : 0;
@@ -996,11 +997,10 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
         }
         if (pre) {
           q.o = reinterpret_cast<const float*>(attn_o); q.ld_o = c;
-          q.wos = reinterpret_cast<const float*>(ws_dev + pre->out.wt); q.bo = f_dev + pre->out.bias;
+          q.wos = reinterpret_cast<const float*>(ws_dev + a.out.wt); q.bo = f_dev + a.out.bias;
           ++n_split_gemms;
           ++n_ff_split_pre;
         }
-        const bool post = pre && ff_makes_qkv(f, v);
         if (post) {
           q.qkv = reinterpret_cast<float*>(scratch); q.ld_qkv = 3 * c;
           q.wqs = reinterpret_cast<const float*>(ws_dev + f.next->qkv.wt); q.bq = f_dev + f.next->qkv.bias;
@@ -1016,9 +1016,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     }
     if (form == FFForm::chain) {
       const float2* rs = stream_stats(x, ld, c, m);
-      // both layers on the persistent GEMM (stage 2 of the 0.25-degree model): the hidden tensor between them goes k-blocked
-      const KBlk blk = sizeof(T) == 2 && opt.use_stream && opt.use_dma && opt.fuse_ln && !opt.dbg_flags && f.w1.wt_kb >= 0 && f.w2.wt_kb >= 0 && c == 512 &&
-                       m >= opt.stream_min_rows && f.w2.bias >= 0 ? KBlk::hidden : KBlk::none;
+      const KBlk blk = pl.hidden_kblk ? KBlk::hidden : KBlk::none;
       gemm("gemm_ff1", f.w1, {.in = x, .in_h = h, .in_w = w, .in_ld = ld, .out = scratch, .out_ld = 4 * c, .rs = rs, .act = 1, .blk = blk});
       stat_tiles_ready = gemm("gemm_ff2", f.w2, {.in = scratch, .in_h = h, .in_w = w, .in_ld = 4 * c, .out = x, .out_ld = ld, .res = x, .res_ld = ld,
                                                  .blk = blk, .want_stats = true}).stat_slots;
@@ -1211,12 +1209,13 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     for (size_t d = 0; d < st.blocks.size(); ++d) {
       const std::string bp = sp + ".1.layers." + std::to_string(d);
       const BlockL& bl = st.blocks[d];
-      const bool ds = ff_takes_out(bl.sf, bl.sa, v), dl = ff_takes_out(bl.lf, bl.la, v);
-      attention(bl.sa, v, bp + ".0", ds, qkv_made);
-      feedforward(bl.sf, v, bp + ".1", ds ? &bl.sa : nullptr);
-      attention(bl.la, v, bp + ".2", dl, ds && ff_makes_qkv(bl.sf, v));
-      feedforward(bl.lf, v, bp + ".3", dl ? &bl.la : nullptr);
-      qkv_made = dl && ff_makes_qkv(bl.lf, v);
+      const PairPlan p = plan_pair(bl.sa, bl.sf, v, qkv_made);
+      attention(bl.sa, v, bp + ".0", p);
+      feedforward(bl.sa, bl.sf, v, bp + ".1", p);
+      const PairPlan q = plan_pair(bl.la, bl.lf, v, p.post);
+      attention(bl.la, v, bp + ".2", q);
+      feedforward(bl.la, bl.lf, v, bp + ".3", q);
+      qkv_made = q.post;
     }
   }
   void block_half(const StageView& v, int d, bool long_half) {   // lat-band mode: one (attention, feed-forward) pair
@@ -1224,9 +1223,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     const BlockL& bl = stages[v.s].blocks[d];
     const AttnL& a = long_half ? bl.la : bl.sa;
     const FFL& f = long_half ? bl.lf : bl.sf;
-    const bool df = ff_takes_out(f, a, v);
-    attention(a, v, "", df, false);
-    feedforward(f, v, "", df ? &a : nullptr);
+    const PairPlan p = plan_pair(a, f, v, false);
+    attention(a, v, "", p);
+    feedforward(a, f, v, "", p);
   }
   // ------------------------------------------------------------------ ensemble noise (wx_noise.h)
   // tape entries of slot l in the reference's draw order: per active layer (latent, pixel), or one latent first when correlated
