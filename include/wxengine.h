@@ -41,8 +41,12 @@ enum wx_arch {
   WX_ARCH_CROSSFORMER = 0, /* credit/models/crossformer.py (model.type: crossformer): ConvTranspose decoder */
   WX_ARCH_WXFORMER = 1,    /* credit/models/wxformer/crossformer.py (model.type: wxformer / wxformer_base): sub-pixel conv
                               + PixelShuffle decoder, ZeroPad2d-wrapped CrossEmbed branches (keys convs.<i>.1.*) */
-  WX_ARCH_CROSSFORMER_UPCONV = 2 /* credit/models/crossformer.py with upsample_v_conv=True (:87-92, :560-570): every decoder
+  WX_ARCH_CROSSFORMER_UPCONV = 2, /* credit/models/crossformer.py with upsample_v_conv=True (:87-92, :560-570): every decoder
                               up-sampling is nn.Upsample(2x bilinear, align_corners=False) + Conv3x3 instead of ConvTranspose */
+  WX_ARCH_CAMULATOR = 3    /* credit/models/camulator.py (model.type: camulator): the legacy CrossEmbed (bare Conv2d, keys convs.<i>.*)
+                              in front of the wxformer decoder, whose `sharp` convs carry no spectral norm here; frames == 2 enters as
+                              the mean of the two frames (F.avg_pool3d), so the first conv takes channels * levels + surface +
+                              input_only channels whatever `frames` is.  frames <= 2, no noise layers, not in lat-band mode */
 };
 
 enum wx_precision {

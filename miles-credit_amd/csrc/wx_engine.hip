@@ -249,7 +249,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     int64_t max_dt = 0;
     for (int i = 0; i < 3; ++i) max_dt = std::max(max_dt, (int64_t)sh[2 - i] * sw[2 - i] * ups[i].cout);
     for (int i = 0; i < 4; ++i) dtmp[i] = (T*)mem.alloc(max_dt * sizeof(T));
-    if (cfg.arch == WX_ARCH_WXFORMER) ps4_buf = (T*)mem.alloc((int64_t)Hd * Wd * cpad4 * sizeof(T));
+    if (ps_decoder()) ps4_buf = (T*)mem.alloc((int64_t)Hd * Wd * cpad4 * sizeof(T));
     if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // bilinearly up-sampled conv input: largest is up_block4's (Hd x Wd x 2 dim0)
       int64_t m = (int64_t)Hd * Wd * 2 * cfg.dim[0];
       for (int i = 0; i < 3; ++i) m = std::max(m, (int64_t)sh[2 - i] * sw[2 - i] * ups[i].cin);
@@ -1071,7 +1071,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
   // `x` holds input rows [src_row0, src_row0 + src_rows) of every channel (the whole grid outside lat-band mode)
   void pack_input(const float* x, T* dst, T* dst_planar, int Hb, int row0, int nrows, int dst_row, int src_row0, int src_rows) {
     PackParams p;
-    p.x = x; p.dst = dst; p.C = C_in; p.H = cfg.image_height; p.W = cfg.image_width;
+    p.x = x; p.dst = dst; p.C = C_in_model; p.H = cfg.image_height; p.W = cfg.image_width;
     p.p0 = cfg.pad_activate ? cfg.pad_lat[0] : 0; p.p1 = cfg.pad_activate ? cfg.pad_lat[1] : 0;
     p.pl = cfg.pad_activate ? cfg.pad_lon[0] : 0; p.pr = cfg.pad_activate ? cfg.pad_lon[1] : 0;
     p.halo = halo; p.cpad = cpad0; p.dst_planar = dst_planar; p.Hb = Hb;
@@ -1084,7 +1084,9 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     const int cg = std::min(cpad0, 224);
     const int xshift = opt.pack_align ? (64 - p.pl % 64) % 64 : 0;
     timed("pack_input", 0.0, (double)C_in * nrows * cfg.image_width * 4.0 + (double)nrows * Wp * cpad0 * sizeof(T), [&] {
-      hipLaunchKernelGGL(pack_input_kernel<T>, dim3(cdiv(Wp + xshift, 64), nrows), dim3(256), (size_t)cg * 65 * sizeof(float), cur_stream, p, cg, xshift);
+      // camulator at frames == 2: the same launch reads both frames of x [C_in_model][2][H][W] and packs their mean
+      if (avg_frames()) hipLaunchKernelGGL((pack_input_kernel<T, true>), dim3(cdiv(Wp + xshift, 64), nrows), dim3(256), (size_t)cg * 65 * sizeof(float), cur_stream, p, cg, xshift);
+      else hipLaunchKernelGGL(pack_input_kernel<T>, dim3(cdiv(Wp + xshift, 64), nrows), dim3(256), (size_t)cg * 65 * sizeof(float), cur_stream, p, cg, xshift);
       WX_HIP(hipGetLastError());
     });
   }
@@ -1134,12 +1136,12 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
           const PatchW& pw = st.patch[j];
           const int kj = st.embed_k[j];
           if (pw.wt >= 0) {
-            fl += 2.0 * v.h * v.w * pw.n * kj * kj * C_in;
+            fl += 2.0 * v.h * v.w * pw.n * kj * kj * C_in_model;
             if (kj == 32) ep.wt32 = wt_dev + pw.wt;
             if (kj == 16) ep.wt16 = wt_dev + pw.wt;
             if (kj == 8) ep.wt8 = wt_dev + pw.wt;
           } else if (kj == 4 && st.ride4) {
-            fl += 2.0 * v.h * v.w * st.embed[j].n * kj * kj * C_in;
+            fl += 2.0 * v.h * v.w * st.embed[j].n * kj * kj * C_in_model;
           }
           off += st.embed[j].n;
         }
@@ -1313,7 +1315,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
     attn_block_nkf_mask = 0;
     // a1: pack + earth halo
     pack_input(x_item, xin, xin_planar, Hp + 2 * halo, 0, Hp, halo, 0, cfg.image_height);
-    capture("pad", xin + ((int64_t)halo * (Wp + 2 * halo) + halo) * cpad0, Hp, Wp, C_in, cpad0, Wp + 2 * halo);
+    capture("pad", xin + ((int64_t)halo * (Wp + 2 * halo) + halo) * cpad0, Hp, Wp, C_in_model, cpad0, Wp + 2 * halo);
     if (cfg.noise_latent_dim > 0) noise_styles();
     // encoder
     for (int s = 0; s < 4; ++s) {
@@ -1345,7 +1347,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       // the block's stored intermediates, captured behind the launch that wrote them (ta is written twice); no route depends on them
       const std::string up = "up_block" + std::to_string(i + 1);
       auto cap_mid = [&](const char* what, const T* buf, int c) { capture(up + what, buf, sh[so], sw[so], c, c, sw[so]); };
-      if (cfg.arch == WX_ARCH_WXFORMER) {
+      if (ps_decoder()) {
         // x = PixelShuffle(conv3x3(x)); x = x + sharp(x)   (wxformer/crossformer.py:157-158)
         gemm("gemm_convPS", u.convps, {.in = in, .in_h = sh[si], .in_w = sw[si], .in_ld = in_ld, .out = dtmp[3], .out_ld = u.cout, .out_mode = 1,
                                        .cout = u.cout});
@@ -1374,7 +1376,7 @@ class Engine : public EngineBase, public ModelSpec, public LayerTables {
       }
     }
     cur_stage = 7;
-    if (cfg.arch == WX_ARCH_WXFORMER) {
+    if (ps_decoder()) {
       gemm("gemm_convPS", ps4, {.in = cat[0], .in_h = sh[0], .in_w = sw[0], .in_ld = 2 * cfg.dim[0], .out = ps4_buf, .out_ld = cpad4, .out_mode = 1,
                                 .cout = cpad4});
       capture("up_block4.ps", ps4_buf, Hd, Wd, C_out, cpad4, Wd);

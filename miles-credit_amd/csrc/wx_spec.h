@@ -52,6 +52,13 @@ struct ModelSpec {
   // ------------------------------------------------------------------ config
   wx_config cfg;
   int C_in = 0, C_out = 0, Hp = 0, Wp = 0, halo = 0, cpad0 = 0;
+  // C_in: planes of the caller's input tensor (and of the PostBlock's x), frames included.  C_in_model: channels of the first conv =
+  // of the packed stage-0 input (cpad0 pads it).  They differ for WX_ARCH_CAMULATOR at frames == 2 only, whose entry averages the frames
+  int C_in_model = 0;
+  // the two halves an arch pairs: the CrossEmbed form (ZeroPad2d-wrapped branches or bare convs) and the decoder
+  bool ps_decoder() const { return cfg.arch == WX_ARCH_WXFORMER || cfg.arch == WX_ARCH_CAMULATOR; }
+  bool zeropad_embed() const { return cfg.arch == WX_ARCH_WXFORMER; }
+  bool avg_frames() const { return cfg.arch == WX_ARCH_CAMULATOR && cfg.frames == 2; }
   int sh[4], sw[4];           // stage maps
   int Hd = 0, Wd = 0, Hu = 0, Wu = 0, Ho = 0, Wo = 0, ld_dec = 0;
 
@@ -71,12 +78,21 @@ struct ModelSpec {
       for (int s = 0; s < 4; ++s)
         if (cfg.local_window_size[s] * cfg.local_window_size[s] > 128 || cfg.global_window_size[s] * cfg.global_window_size[s] > 128)
           throw ConfigError("dim_head != 32 needs windows of at most 128 tokens (the general attention kernel's limit)");
-    if (cfg.arch != WX_ARCH_CROSSFORMER && cfg.arch != WX_ARCH_WXFORMER && cfg.arch != WX_ARCH_CROSSFORMER_UPCONV)
+    if (cfg.arch != WX_ARCH_CROSSFORMER && cfg.arch != WX_ARCH_WXFORMER && cfg.arch != WX_ARCH_CROSSFORMER_UPCONV &&
+        cfg.arch != WX_ARCH_CAMULATOR)
       throw ConfigError("unknown wx_config.arch");
     if (cfg.noise_latent_dim < 0 || cfg.noise_latent_dim > 4096) throw ConfigError("noise_latent_dim must be in 0 .. 4096");
     if (cfg.noise_latent_dim > 0 && cfg.arch == WX_ARCH_WXFORMER)
       throw ConfigError("noise layers belong to crossformer-ensemble (a legacy CrossFormer subclass): not with the wxformer decoder");
-    C_in = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.input_only_channels) * cfg.frames;
+    if (cfg.arch == WX_ARCH_CAMULATOR) {
+      if (cfg.noise_latent_dim > 0) throw ConfigError("camulator: noise layers belong to crossformer-ensemble, the Camulator class has none");
+      // camulator.py:587-588 F.avg_pool3d(x, (2, 1, 1)).squeeze(2): frames 0 and 1 are averaged, a third is dropped without a word, four fail
+      if (cfg.frames > 2) throw ConfigError("camulator: frames must be 1 or 2 (the entry averages frames 0 and 1; the reference drops a third and fails on four)");
+      if (cfg.output_frames != 1) throw ConfigError("camulator: output_frames must be 1 (the class has no such argument)");
+    }
+    C_in_model = cfg.channels * cfg.levels + cfg.surface_channels + cfg.input_only_channels;
+    C_in = C_in_model * cfg.frames;
+    if (cfg.arch != WX_ARCH_CAMULATOR) C_in_model = C_in;   // every other class reshapes the frames into channels (c * t)
     C_out = (cfg.channels * cfg.levels + cfg.surface_channels + cfg.output_only_channels) * cfg.output_frames;
     Hp = cfg.image_height + (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);
     Wp = cfg.image_width + (cfg.pad_activate ? cfg.pad_lon[0] + cfg.pad_lon[1] : 0);
@@ -96,7 +112,7 @@ struct ModelSpec {
         if (k < st) throw ConfigError("cross-embed kernel smaller than stride");
         const int pd = (k - st) / 2;
         // legacy: symmetric padding pd; wxformer: ZeroPad2d(lo = (k-s)/2, hi = (k-s) - lo) then an un-padded conv
-        const int pad_total = cfg.arch == WX_ARCH_WXFORMER ? (k - st) : 2 * pd;
+        const int pad_total = zeropad_embed() ? (k - st) : 2 * pd;
         const int h2 = (h + pad_total - k) / st + 1, w2 = (w + pad_total - k) / st + 1;
         if (oh >= 0 && (h2 != oh || w2 != ow)) throw ConfigError("cross-embed branches disagree on output size");
         oh = h2; ow = w2;
@@ -127,7 +143,7 @@ struct ModelSpec {
       for (int wsz : {cfg.local_window_size[s], cfg.global_window_size[s]})
         if (wsz > 1 && !window_attn_lds_ok(elem, attn_nkf(wsz), cfg.dim_head, false))
           throw ConfigError("window attention: dim_head x window size exceeds the kernel's 160 KB of LDS (fp32 storage: dim_head 128 takes windows of at most 64 tokens)");
-    cpad0 = ((C_in + 31) / 32) * 32;
+    cpad0 = ((C_in_model + 31) / 32) * 32;
     Hd = sh[3] * 16; Wd = sw[3] * 16;
     Hu = Hd - (cfg.pad_activate ? cfg.pad_lat[0] + cfg.pad_lat[1] : 0);
     Wu = Wd - (cfg.pad_activate ? cfg.pad_lon[0] + cfg.pad_lon[1] : 0);
@@ -148,9 +164,10 @@ struct ModelSpec {
     t.shape = std::move(shape);
     tensors[k] = std::move(t);
   }
-  void add_conv(const std::string& p, std::vector<int64_t> shape, bool bias, bool transposed = false) {
+  // sn = false: a conv the class leaves out of apply_spectral_norm (camulator.py:22-28 skips every module named "sharp")
+  void add_conv(const std::string& p, std::vector<int64_t> shape, bool bias, bool transposed = false, bool sn = true) {
     const int64_t nb = transposed ? shape[1] : shape[0];
-    if (cfg.use_spectral_norm) {
+    if (cfg.use_spectral_norm && sn) {
       if (bias) add_key(p + ".bias", {nb});
       add_key(p + ".weight_orig", shape);
       int64_t rest = 1;
@@ -169,7 +186,7 @@ struct ModelSpec {
     }
   }
   void build_spec() {
-    int dims[5] = {C_in, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
+    int dims[5] = {C_in_model, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
     for (int s = 0; s < 4; ++s) {
       const int cin = dims[s], cout = dims[s + 1];
       std::vector<int> ks(cfg.embed_kernels[s], cfg.embed_kernels[s] + cfg.n_embed_kernels[s]);
@@ -212,9 +229,9 @@ struct ModelSpec {
     const int ups[3][2] = {{last, last / 2}, {2 * (last / 2), last / 4}, {2 * (last / 4), last / 8}};
     for (int i = 0; i < 3; ++i) {
       const std::string p = "up_block" + std::to_string(i + 1);
-      if (cfg.arch == WX_ARCH_WXFORMER) {  // UpBlockPS (wxformer/crossformer.py:137-162)
+      if (ps_decoder()) {  // UpBlockPS (wxformer/crossformer.py:137-162, camulator.py:102-127)
         add_conv(p + ".conv", {4 * ups[i][1], ups[i][0], 3, 3}, true);
-        add_conv(p + ".sharp", {ups[i][1], ups[i][1], 3, 3}, true);
+        add_conv(p + ".sharp", {ups[i][1], ups[i][1], 3, 3}, true, false, cfg.arch != WX_ARCH_CAMULATOR);
       } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // nn.Upsample + Conv2d 3x3 (crossformer.py:87-89)
         add_conv(p + ".conv", {ups[i][1], ups[i][0], 3, 3}, true);
       } else {
@@ -226,7 +243,7 @@ struct ModelSpec {
         add_key(p + ".b." + std::to_string(j + 1) + ".bias", {ups[i][1]});
       }
     }
-    if (cfg.arch == WX_ARCH_WXFORMER) {  // Sequential(conv3x3 -> PixelShuffle -> conv3x3) (wxformer/crossformer.py:817-830)
+    if (ps_decoder()) {  // Sequential(conv3x3 -> PixelShuffle -> conv3x3) (wxformer/crossformer.py:817-830, camulator.py:546-557)
       add_conv("up_block4.0", {4 * C_out, 2 * (last / 8), 3, 3}, true);
       add_conv("up_block4.2", {C_out, C_out, 3, 3}, true);
     } else if (cfg.arch == WX_ARCH_CROSSFORMER_UPCONV) {  // Sequential(Upsample, Conv2d) (crossformer.py:560-570)
@@ -252,7 +269,7 @@ struct ModelSpec {
   }
   int noise_channels(int l) const { return l < 3 ? cfg.dim[l] : cfg.dim[5 - l]; }
   std::string embed_key(int s, int b) const {
-    return "layers." + std::to_string(s) + ".0.convs." + std::to_string(b) + (cfg.arch == WX_ARCH_WXFORMER ? ".1" : "");
+    return "layers." + std::to_string(s) + ".0.convs." + std::to_string(b) + (zeropad_embed() ? ".1" : "");
   }
 
   void load_tensor(const char* key, const float* data, int ndim, const int64_t* shape) {
@@ -304,7 +321,7 @@ struct ModelSpec {
 
   // eval-mode spectral norm: W / (u . (W_mat v)); W_mat rows = dim 0 (dim 1 for ConvTranspose2d)
   std::vector<double> folded(const std::string& p, bool transposed) const {
-    if (!cfg.use_spectral_norm) {
+    if (!cfg.use_spectral_norm || !tensors.count(p + ".weight_orig")) {   // the spec lists `weight` for a conv without spectral norm
       const HostTensor& w = need(p + ".weight");
       return std::vector<double>(w.data.begin(), w.data.end());
     }
@@ -369,6 +386,8 @@ inline BandModel band_model(const ModelSpec& e, int n, int elem, int n_fix) {
   return m;
 }
 inline void band_check_supported(const ModelSpec& e) {
+  if (e.cfg.arch == WX_ARCH_CAMULATOR)
+    throw ConfigError("lat-band mode: the camulator arch is not wired (crossformer and wxformer are)");
   if (e.cfg.arch != WX_ARCH_CROSSFORMER && e.cfg.arch != WX_ARCH_WXFORMER)
     throw ConfigError("lat-band mode: the upsample_v_conv decoder variant is not wired (crossformer and wxformer are)");
   if (e.cfg.frames != 1 || e.cfg.output_frames != 1) throw ConfigError("lat-band mode needs frames == output_frames == 1");

@@ -400,7 +400,7 @@ struct WeightPacker {
   }
 
   void run() {
-    int dims[5] = {spec.C_in, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
+    int dims[5] = {spec.C_in_model, cfg.dim[0], cfg.dim[1], cfg.dim[2], cfg.dim[3]};
     for (int s = 0; s < 4; ++s) {
       StageL st;
       std::vector<int> ks(cfg.embed_kernels[s], cfg.embed_kernels[s] + cfg.n_embed_kernels[s]);
@@ -512,7 +512,7 @@ struct WeightPacker {
       UpL u;
       u.cin = upc[i][0]; u.cout = upc[i][1];
       if (u.cout % 32) throw StateError("decoder: a width ModelSpec::derive() should have refused");
-      if (cfg.arch == WX_ARCH_WXFORMER) {
+      if (spec.ps_decoder()) {
         // sub-pixel conv: reference channel c*4+q feeds sub-pixel q of channel c (PixelShuffle); rows reordered
         // to q*cout + c so the ConvT-style scatter epilogue (out_mode 1) performs the shuffle
         std::vector<int> src(4 * u.cout);
@@ -531,7 +531,7 @@ struct WeightPacker {
       u.g2 = push_f(spec.need(p + ".b.4.weight").data); u.b2 = push_f(spec.need(p + ".b.4.bias").data);
       tab.ups[i] = u;
     }
-    if (cfg.arch == WX_ARCH_WXFORMER) {
+    if (spec.ps_decoder()) {
       tab.cpad4 = ((spec.C_out + 31) / 32) * 32;  // padded channel count of the shuffled map (zero rows / zero input weights)
       std::vector<int> src(4 * tab.cpad4, -1);
       for (int q = 0; q < 4; ++q)

@@ -51,7 +51,8 @@ class WXConfig:
     post_conf: Dict = field(default_factory=lambda: {"activate": False})
     # which reference class the weights belong to: "crossformer" (legacy ConvTranspose decoder,
     # credit/models/crossformer.py — the class every BASELINE YAML selects) or "wxformer"
-    # (credit/models/wxformer/crossformer.py: same encoder, sub-pixel conv + PixelShuffle decoder).
+    # (credit/models/wxformer/crossformer.py: same encoder, sub-pixel conv + PixelShuffle decoder), or "camulator"
+    # (credit/models/camulator.py: the legacy CrossEmbed in front of the PixelShuffle decoder; two input frames enter as their mean).
     arch: str = "crossformer"
     # CrossFormerWithNoise (model.type crossformer-ensemble, credit/models/wxformer/crossformer_ensemble.py): 0 = deterministic.
     # The two factors only initialise the noise_factor parameters (a checkpoint overrides them); `freeze` is training-only.
@@ -97,9 +98,17 @@ class WXConfig:
 
     # ------------------------------------------------------------------ #
     def validate(self):
-        if self.arch not in ("crossformer", "wxformer"):
+        if self.arch not in ("crossformer", "wxformer", "camulator"):
             raise ValueError(f"unsupported arch {self.arch!r} ('crossformer' = legacy ConvTranspose decoder, "
-                             "'wxformer' = PixelShuffle decoder)")
+                             "'wxformer' = PixelShuffle decoder, 'camulator' = legacy CrossEmbed + PixelShuffle decoder)")
+        if self.arch == "camulator":
+            if self.frames not in (1, 2):
+                raise ValueError("camulator: frames must be 1 or 2 (camulator.py:587-588 averages frames 0 and 1; the reference drops a "
+                                 "third frame without a word and fails on four)")
+            if self.output_frames != 1:
+                raise ValueError("camulator: the class has no output_frames argument (one output frame)")
+            if self.noise_latent_dim > 0:
+                raise ValueError("camulator: noise layers belong to crossformer-ensemble, the Camulator class has none")
         if self.patch_height != 1 or self.patch_width != 1:
             raise ValueError("patch_height/patch_width > 1 (CubeEmbedding path) is not supported by the engine")
         if self.upsample_v_conv and self.arch != "crossformer":
@@ -183,7 +192,14 @@ class WXConfig:
 
     @property
     def input_channels(self):
+        """Planes of the input TENSOR [B, base_input_channels, frames, H, W] (what the caller and the PostBlock's x hold)."""
         return self.base_input_channels * self.frames
+
+    @property
+    def model_input_channels(self):
+        """Channels of the first conv.  Every class but camulator reshapes the frames into channels (c * t); camulator averages the two
+        frames (camulator.py:587-588), so its first conv takes one frame's worth whatever `frames` is."""
+        return self.base_input_channels if self.arch == "camulator" else self.input_channels
 
     @property
     def base_output_channels(self):
@@ -274,7 +290,8 @@ class WXConfig:
                 if bias:
                     spec[prefix + ".bias"] = (shape[1] if transposed else shape[0],)
 
-        dims = (self.input_channels,) + tuple(self.dim)
+        cam = self.arch == "camulator"
+        dims = (self.model_input_channels,) + tuple(self.dim)
         for s in range(4):
             cin, cout = dims[s], dims[s + 1]
             for b, (k, co) in enumerate(self.embed_dims(s)):
@@ -305,16 +322,20 @@ class WXConfig:
                         conv(p + ".layers.1", (4 * cout, cout, 1, 1))
                         conv(p + ".layers.4", (cout, 4 * cout, 1, 1))
         # unused-at-patch-1 cube embedding (present in reference checkpoints, never spectral-normed: Conv3d)
-        spec["cube_embedding.proj.weight"] = (self.dim[0], self.input_channels, self.frames, 1, 1)
+        spec["cube_embedding.proj.weight"] = (self.dim[0], self.model_input_channels, self.frames, 1, 1)
         spec["cube_embedding.proj.bias"] = (self.dim[0],)
         spec["cube_embedding.norm.weight"] = (self.dim[0],)
         spec["cube_embedding.norm.bias"] = (self.dim[0],)
         last = self.dim[-1]
         ups = [(last, last // 2), (2 * (last // 2), last // 4), (2 * (last // 4), last // 8)]
-        if self.arch == "wxformer":  # UpBlockPS / up_block4 Sequential (wxformer/crossformer.py:137-162, 817-830)
+        if self.arch in ("wxformer", "camulator"):  # UpBlockPS / up_block4 Sequential (wxformer/crossformer.py:137-162, 817-830)
             for i, (ci, co) in enumerate(ups, start=1):
                 conv(f"up_block{i}.conv", (4 * co, ci, 3, 3))
-                conv(f"up_block{i}.sharp", (co, co, 3, 3))
+                if cam:  # camulator.py:22-28: apply_spectral_norm skips every module named "sharp"
+                    spec[f"up_block{i}.sharp.weight"] = (co, co, 3, 3)
+                    spec[f"up_block{i}.sharp.bias"] = (co,)
+                else:
+                    conv(f"up_block{i}.sharp", (co, co, 3, 3))
                 for j in (0, 3):
                     conv(f"up_block{i}.b.{j}", (co, co, 3, 3))
                     spec[f"up_block{i}.b.{j + 1}.weight"] = (co,)
@@ -422,6 +443,16 @@ def named_config(name: str) -> WXConfig:
                   dim=[32, 64, 128, 256], depth=[2, 2, 2, 2], global_window_size=[10, 5, 2, 1],
                   local_window_size=10,
                   padding_conf=dict(activate=True, mode="earth", pad_lat=[40, 40], pad_lon=[80, 80]))
+    elif name in ("K0", "K0F", "K0X", "K2048"):  # credit/models/camulator.py (legacy CrossEmbed + PixelShuffle decoder, frames averaged)
+        if name == "K2048":  # CAMulator's own widths (camulator_gen2_casper.yml) on the smallest square whose four stage maps (32 .. 4)
+            # stay divisible by the windows; no padding
+            mc = dict(base, image_height=64, image_width=64, levels=3, output_only_channels=3,
+                      dim=[256, 512, 1024, 2048], depth=[1, 1, 1, 1], global_window_size=[4, 4, 2, 2], local_window_size=2)
+        else:  # K0: T0's geometry and widths; K0F: two frames; K0X: K0F with T0X's wide input and longitude pads [13, 11]
+            mc = dict(_t0_conf(base), frames=1 if name == "K0" else 2)
+            if name == "K0X":
+                mc.update(levels=57, padding_conf=dict(activate=True, mode="earth", pad_lat=[6, 6], pad_lon=[13, 11]))
+        return WXConfig.from_model_conf(mc, arch="camulator")
     elif name == "T0W":  # T0 geometry with the wxformer (PixelShuffle) decoder
         return WXConfig.from_model_conf(_t0_conf(base), arch="wxformer")
     elif name == "T0U":  # T0 geometry, upsample_v_conv=True decoder (credit/models/crossformer.py:87-92, 560-570)

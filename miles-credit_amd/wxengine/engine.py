@@ -19,7 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("WX_LIBRARY") or os.path.join(_HERE, "libwxengine.so")
 
 WX_ABI_VERSION = 3
-ARCH = {"crossformer": 0, "wxformer": 1, "crossformer_upconv": 2}
+ARCH = {"crossformer": 0, "wxformer": 1, "crossformer_upconv": 2, "camulator": 3}
 PREC = {"fp32": 0, "bf16": 1, "fp32s": 2}   # fp32s: fp32 storage, split-bf16 GEMM arithmetic (WX_PREC_FP32_SPLIT)
 
 

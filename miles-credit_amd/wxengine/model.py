@@ -296,6 +296,22 @@ class WXFormerPSHIP(WXFormerHIP):
         super().__init__(precision=precision, arch="wxformer", **model_conf)
 
 
+class CamulatorHIP(WXFormerHIP):
+    """`model.type: camulator` (credit/models/camulator.py Camulator): the legacy CrossEmbed in front of the PixelShuffle decoder; with
+    frames == 2 the model consumes the mean of the two input frames.  The reference class's kwargs (no `output_frames`) plus `precision`;
+    the YAML keys its **kwargs swallow (`frame_patch_size`) and the dropout rates, which are the identity in eval(), are absorbed.
+    No legacy key migration: its CrossEmbed parameters never moved."""
+
+    def __init__(self, precision: str = "bf16", **model_conf):
+        model_conf.pop("arch", None)
+        for k in ("frame_patch_size", "attn_dropout", "ff_dropout"):
+            model_conf.pop(k, None)
+        if "output_frames" in model_conf:
+            raise TypeError("Camulator takes no output_frames argument (credit/models/camulator.py:376-402)")
+        model_conf["output_frames"] = 1
+        super().__init__(precision=precision, arch="camulator", **model_conf)
+
+
 class WXFormerEnsembleHIP(WXFormerHIP):
     """`model.type: crossformer-ensemble` / `crossformer-style` (credit/models/wxformer/crossformer_ensemble.py CrossFormerWithNoise):
     the legacy CrossFormer with six noise-injection layers.  Same kwargs as the reference class (noise_latent_dim, encoder_noise,
@@ -341,8 +357,9 @@ def register_ensemble(model_type: str = "crossformer-ensemble_hip"):
     return register_model(model_type, "Loading the MI355X-native noise-injection ensemble CrossFormer engine ...")(WXFormerEnsembleHIP)
 
 
-def register(model_type: str = "crossformer_hip", wxformer_type: str = "wxformer_hip"):
-    """Register both engine classes with the reference's registry (credit.models.register_model)."""
+def register(model_type: str = "crossformer_hip", wxformer_type: str = "wxformer_hip", camulator_type: str = "camulator_hip"):
+    """Register the engine classes with the reference's registry (credit.models.register_model)."""
     from credit.models import register_model  # type: ignore
+    register_model(camulator_type, "Loading the MI355X-native CAMulator engine ...")(CamulatorHIP)
     register_model(wxformer_type, "Loading the MI355X-native WXFormer (PixelShuffle decoder) engine ...")(WXFormerPSHIP)
     return register_model(model_type, "Loading the MI355X-native CrossFormer engine ...")(WXFormerHIP)

@@ -39,7 +39,7 @@ def keyed_normal(key: str, shape, seed: int = 0) -> np.ndarray:
 def is_transposed_conv(prefix: str, arch: str = "crossformer", upconv: bool = False) -> bool:
     """ConvTranspose2d modules of the legacy decoder (reference crossformer.py:92,572):
     their spectral norm is taken over weight dim 1.  The wxformer decoder and the upsample_v_conv variant have none."""
-    if arch == "wxformer" or upconv:
+    if arch in ("wxformer", "camulator") or upconv:
         return False
     return prefix == "up_block4" or (prefix.startswith("up_block") and prefix.endswith(".conv"))
 

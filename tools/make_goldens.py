@@ -8,7 +8,7 @@ small .npz files under tests/golden/.  Only data (inputs are regenerated from th
 keyed RNG; outputs / strided samples / per-channel statistics) is written — no
 reference source.
 
-    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,regrid,metrics,ensemble]
+    python tools/make_goldens.py [--only T0,T1,C1,C3S,C3,pad,glue,diag,xform,wind,advect,hybrid,regrid,metrics,ensemble,camulator]
 """
 import argparse
 import os
@@ -32,6 +32,8 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 def reference_model(cfg, post_conf=None, family="base"):
+    if getattr(cfg, "arch", "crossformer") == "camulator":
+        return camulator_reference(cfg, post_conf)
     if getattr(cfg, "arch", "crossformer") == "wxformer":
         from credit.models.wxformer.crossformer import CrossFormer
     else:
@@ -51,6 +53,90 @@ def reference_model(cfg, post_conf=None, family="base"):
     m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
     m.eval()
     return m
+
+
+def camulator_reference(cfg, post_conf=None):
+    """credit.models.camulator.Camulator on CPU with the synthetic weights, strict load (the class takes no output_frames)."""
+    from credit.models.camulator import Camulator
+    m = Camulator(
+        image_height=cfg.image_height, image_width=cfg.image_width, frames=cfg.frames, channels=cfg.channels,
+        surface_channels=cfg.surface_channels, input_only_channels=cfg.input_only_channels,
+        output_only_channels=cfg.output_only_channels, levels=cfg.levels, dim=cfg.dim, depth=cfg.depth,
+        dim_head=cfg.dim_head, global_window_size=cfg.global_window_size,
+        local_window_size=tuple(cfg.local_window_size), cross_embed_kernel_sizes=cfg.cross_embed_kernel_sizes,
+        cross_embed_strides=cfg.cross_embed_strides, use_spectral_norm=cfg.use_spectral_norm, interp=cfg.interp,
+        padding_conf={"activate": cfg.pad_activate, "mode": getattr(cfg, "pad_mode", "earth"), "pad_lat": list(cfg.pad_lat),
+                      "pad_lon": list(cfg.pad_lon)},
+        post_conf=post_conf or {"activate": False})
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(cfg).items()}, strict=True)
+    return m.eval()
+
+
+def camulator_golden(name, stride, cap_stride=0, autocast=False):
+    """model_<name>.npz of a camulator config in the layout of model_golden().  The hooked sub-module outputs are stored as
+    stride-`cap_stride` samples with their full-map per-channel sums (the layout of reference_blocks_T1.npz), which keeps the file
+    under the size limit of a committed file; the input of the first CrossEmbed -- pad(avg_pool3d(x)) -- goes in as `cap/pad`."""
+    cfg = named_config(name)
+    torch.manual_seed(0)
+    m = camulator_reference(cfg)
+    x = torch.from_numpy(synth_input(cfg))
+    caps = {}
+    hooks = []
+    if cap_stride:
+        want = {f"layers.{s}.{j}" for s in range(4) for j in (0, 1)} | {f"up_block{i}" for i in (1, 2, 3, 4)}
+        for n, mod in m.named_modules():
+            if n in want:
+                hooks.append(mod.register_forward_hook(lambda _m, _i, o, n=n: caps.__setitem__(n, o.detach().clone())))
+        hooks.append(m.layers[0][0].register_forward_pre_hook(lambda _m, i: caps.__setitem__("pad", i[0].detach().clone())))
+    t = time.time()
+    with torch.no_grad():
+        y = m(x)
+    dt = time.time() - t
+    for h in hooks:
+        h.remove()
+    assert y.shape == (1, cfg.base_output_channels, 1) + tuple(cfg.out_hw), y.shape
+    out = {}
+    out["ch_sum"], out["ch_sumsq"], out["ch_maxabs"] = channel_stats(y)
+    out["stride"] = np.int64(stride)
+    out["y"] = y[0, :, 0, ::stride, ::stride].numpy().astype(np.float32)
+    if cap_stride:
+        out["cap_stride"] = np.int64(cap_stride)
+        for n, v in caps.items():
+            out["cap/" + n] = v[0, :, ::cap_stride, ::cap_stride].numpy().astype(np.float32)
+            out["cap_sum/" + n] = v[0].double().sum(dim=(1, 2)).numpy()
+    if autocast:   # what bf16 arithmetic costs at these widths, measured on the reference itself (as for the stress families)
+        with torch.no_grad(), torch.autocast("cpu", dtype=torch.bfloat16):
+            y16 = m(x).float()
+        out["bf16_autocast_l2"] = np.float64((y16 - y).norm() / y.norm())
+        print(f"[golden] {name}: reference under torch.autocast(bf16) vs its own fp32: rel-L2 {out['bf16_autocast_l2']:.3e}")
+    np.savez_compressed(os.path.join(GOLD, f"model_{name}.npz"), **out)
+    print(f"[golden] {name}: {len(m.state_dict())} keys, forward {dt:.2f}s  mean|y|={y.abs().mean():.4f} max|y|={y.abs().max():.4f}  "
+          f"y sample {out['y'].shape}")
+
+
+def camulator_post_golden():
+    """model_K0F_post.npz: the reference Camulator with its in-model PostBlock (TracerFixer + GlobalMassFixer, simple_demo grid) on
+    the case of tests/camulator_cases.py.  y of the same weights with the PostBlock off goes in too: the channels no fixer owns must
+    equal it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from camulator_cases import post_model_conf
+    from wxengine.config import WXConfig
+    out = {}
+    for tag, post in (("y_plain", False), ("y", True)):
+        mc = post_model_conf(post)
+        cfg = WXConfig.from_model_conf(mc, arch="camulator")
+        m = camulator_reference(cfg, mc["post_conf"])
+        x = torch.from_numpy(synth_input(cfg))
+        with torch.no_grad():
+            y = m(x)
+        assert y.shape == (1, cfg.base_output_channels, 1, 10, 18), y.shape
+        out[tag] = y[0, :, 0].numpy().astype(np.float32)
+    L = 7
+    moved = np.abs(out["y"] - out["y_plain"]).reshape(out["y"].shape[0], -1).max(axis=1)
+    assert (moved[L:2 * L] > 0).all() and (np.delete(moved, np.arange(L, 2 * L)) == 0).all(), moved
+    np.savez_compressed(os.path.join(GOLD, "model_K0F_post.npz"), **out)
+    print(f"[golden] K0F_post: the fixers move q by up to {moved.max():.3e} (max|q| {np.abs(out['y'][L:2 * L]).max():.3f}); "
+          f"{int((out['y_plain'][L:2 * L] < 0).sum())} values below the tracer threshold")
 
 
 def channel_stats(y):
@@ -1673,6 +1759,12 @@ def main():
             fuxi_timm_golden()
         elif item in ("T0", "T1", "T0W", "T0U", "T0M", "T0F", "T0H", "T1H", "T0X"):
             model_golden(item, 1, capture_layers=(item in ("T0", "T0W", "T0U")))
+        elif item == "camulator":   # credit/models/camulator.py: K0 / K0F with sampled sub-module outputs, K0X, K2048 (bf16 autocast figure)
+            camulator_golden("K0", 1, cap_stride=2)
+            camulator_golden("K0F", 1, cap_stride=2)
+            camulator_golden("K0X", 2)
+            camulator_golden("K2048", 1, autocast=True)
+            camulator_post_golden()
         elif item == "blocks":
             blocks_golden()
         elif item == "specs":
