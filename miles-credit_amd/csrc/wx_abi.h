@@ -7,9 +7,12 @@ namespace wx {
 static thread_local std::string g_last_error;
 }  // namespace wx
 
-struct wx_engine {
-  std::unique_ptr<wx::EngineBase> impl;
+// every opaque handle of the header: the tag keeps its name, the body is the wrapped object
+template <class Impl>
+struct Handle {
+  std::unique_ptr<Impl> impl;
 };
+struct wx_engine : Handle<wx::EngineBase> {};
 
 template <typename F>
 static int guarded(F&& fn) {
@@ -43,6 +46,32 @@ static void remap(F&& fn) {
   } catch (const std::runtime_error& e) {
     throw Err(e.what());
   }
+}
+
+// wx_X_create of a device product: a null argument, then `check()`'s reason (it needs no device to be told), then the device,
+// then the object `make()` news
+template <typename H, typename Check, typename Make>
+static int create(const char* fn, H** out, bool args_ok, int device, Check&& check, Make&& make) {
+  return guarded([&] {
+    if (!out || !args_ok) throw wx::ConfigError(std::string(fn) + ": null argument");
+    const std::string why = check();
+    if (!why.empty()) throw wx::ConfigError(std::string(fn) + ": " + why);
+    need_device(device, fn);
+    std::unique_ptr<H> h(new H);
+    h->impl.reset(make());
+    *out = h.release();
+  });
+}
+static std::string no_check() { return {}; }
+// every other wrapper of a device product: a live handle (or `what`), then `fn`; use_remapped also turns the object's
+// std::runtime_error into WX_ERR_INVALID
+template <typename H, typename F>
+static int use(const H* h, const char* what, F&& fn) {
+  return guarded([&] { need(h, what); fn(); });
+}
+template <typename H, typename F>
+static int use_remapped(const H* h, const char* what, F&& fn) {
+  return use(h, what, [&] { remap<wx::ConfigError>(fn); });
 }
 
 extern "C" {
@@ -228,233 +257,162 @@ int wx_profile_read(wx_handle h, wx_kernel_stat* out, int capacity, int* count) 
   return guarded([&] { need(h, "null engine handle"); if (!out || !count) throw wx::ConfigError("wx_profile_read: null argument"); *count = h->impl->profile_read(out, capacity); });
 }
 // ---- pre block (input normalisation + channel concatenation) ---------------------------------------------------------
-struct wx_pre {
-  std::unique_ptr<wx::PreBlock> impl;
-};
+struct wx_pre : Handle<wx::PreBlock> {};
 int wx_pre_create(int n_fields, const int32_t* n_levels, int frames, int H, int W, const float* mean, const float* stdv, int device,
                   wx_pre_handle* out) {
-  return guarded([&] {
-    if (!out || !n_levels) throw wx::ConfigError("wx_pre_create: null argument");
-    need_device(device, "wx_pre_create");
-    std::unique_ptr<wx_pre> p(new wx_pre);
-    p->impl.reset(new wx::PreBlock(n_fields, n_levels, frames, H, W, mean, stdv, device));
-    *out = p.release();
-  });
+  return create("wx_pre_create", out, n_levels != nullptr, device, no_check,
+                [&] { return new wx::PreBlock(n_fields, n_levels, frames, H, W, mean, stdv, device); });
 }
 int wx_pre_destroy(wx_pre_handle p) { return guarded([&] { delete p; }); }
 int wx_pre_channels(wx_pre_handle p, int* channels) {
-  return guarded([&] { need(p, "wx_pre_channels: null argument"); if (!channels) throw wx::ConfigError("wx_pre_channels: null argument"); *channels = p->impl->channels(); });
+  return use(p, "wx_pre_channels: null argument", [&] {
+    if (!channels) throw wx::ConfigError("wx_pre_channels: null argument");
+    *channels = p->impl->channels();
+  });
 }
 int wx_pre_apply(wx_pre_handle p, const float* const* fields_dev, float* x_dev, int batch, void* stream) {
-  return guarded([&] {
-    need(p, "wx_pre_apply: null argument");
+  return use(p, "wx_pre_apply: null argument", [&] {
     if (!fields_dev || !x_dev) throw wx::ConfigError("wx_pre_apply: null argument");
     p->impl->apply(fields_dev, x_dev, batch, (hipStream_t)stream);
   });
 }
 int wx_pre_set_transforms(wx_pre_handle p, const int32_t* kind, const float* eps, const float* log_eps, const int32_t* n_rules,
                           const int32_t* rule_op, const float* rule_search, const float* rule_fill) {
-  return guarded([&] {
-    need(p, "wx_pre_set_transforms: null pre-block handle");
+  return use_remapped(p, "wx_pre_set_transforms: null pre-block handle", [&] {
     if (!kind || !eps || !log_eps || !n_rules || !rule_op || !rule_search || !rule_fill) throw wx::ConfigError("wx_pre_set_transforms: null argument");
-    remap<wx::ConfigError>([&] { p->impl->set_transforms(kind, eps, log_eps, n_rules, rule_op, rule_search, rule_fill); });
+    p->impl->set_transforms(kind, eps, log_eps, n_rules, rule_op, rule_search, rule_fill);
   });
 }
 // ---- inverse scale + inverse transforms of named tensors (csrc/wx_unxform.h) ----------------------------------------------------
-struct wx_unxform {
-  std::unique_ptr<wx::Unxform> impl;
-};
+struct wx_unxform : Handle<wx::Unxform> {};
 int wx_unxform_create(int n_vars, const int32_t* n_levels, int H, int W, const int32_t* kind, const float* eps, const float* log_eps,
                       const int32_t* has_stats, const float* mean, const float* stdv, int device, wx_unxform_handle* out) {
-  return guarded([&] {
-    if (!out || !n_levels || !kind || !eps || !log_eps || !has_stats) throw wx::ConfigError("wx_unxform_create: null argument");
-    if (n_vars < 1 || n_vars > wx::kMaxFields) throw wx::ConfigError("wx_unxform_create: 1..64 variables");
-    if (H < 1 || W < 1) throw wx::ConfigError("wx_unxform_create: bad geometry");
-    bool any_stats = false;
+  bool any_stats = false;
+  const auto check = [&]() -> std::string {
+    if (n_vars < 1 || n_vars > wx::kMaxFields) return "1..64 variables";
+    if (H < 1 || W < 1) return "bad geometry";
     for (int v = 0; v < n_vars; ++v) {
-      if (n_levels[v] < 1) throw wx::ConfigError("wx_unxform_create: a variable needs at least one level");
-      if (kind[v] < wx::kUnxNone || kind[v] > wx::kUnxSquare) throw wx::ConfigError("wx_unxform_create: unknown transform kind " + std::to_string(kind[v]));
+      if (n_levels[v] < 1) return "a variable needs at least one level";
+      if (kind[v] < wx::kUnxNone || kind[v] > wx::kUnxSquare) return "unknown transform kind " + std::to_string(kind[v]);
       if (kind[v] >= wx::kUnxExpE && kind[v] <= wx::kUnxExp10 && !(eps[v] > 0.f && std::isfinite(eps[v]) && std::isfinite(log_eps[v])))
-        throw wx::ConfigError("wx_unxform_create: an exp transform needs a finite eps > 0 and its finite log");
+        return "an exp transform needs a finite eps > 0 and its finite log";
       any_stats = any_stats || has_stats[v] != 0;
     }
-    if (any_stats && (!mean || !stdv)) throw wx::ConfigError("wx_unxform_create: statistics flagged but mean / std are null");
-    need_device(device, "wx_unxform_create");
-    std::unique_ptr<wx_unxform> u(new wx_unxform);
-    u->impl.reset(new wx::Unxform(n_vars, n_levels, H, W, kind, eps, log_eps, has_stats, any_stats ? mean : nullptr, any_stats ? stdv : nullptr, device));
-    *out = u.release();
+    return any_stats && (!mean || !stdv) ? "statistics flagged but mean / std are null" : "";
+  };
+  return create("wx_unxform_create", out, n_levels && kind && eps && log_eps && has_stats, device, check, [&] {
+    return new wx::Unxform(n_vars, n_levels, H, W, kind, eps, log_eps, has_stats, any_stats ? mean : nullptr, any_stats ? stdv : nullptr, device);
   });
 }
 int wx_unxform_destroy(wx_unxform_handle u) { return guarded([&] { delete u; }); }
 int wx_unxform_apply(wx_unxform_handle u, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch,
                      int n_time, void* stream) {
-  return guarded([&] {
-    need(u, "wx_unxform_apply: null argument");
+  return use_remapped(u, "wx_unxform_apply: null argument", [&] {
     if (!src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_unxform_apply: null argument");
-    remap<wx::ConfigError>([&] { u->impl->apply(src_dev, batch_stride, dst_dev, batch, n_time, (hipStream_t)stream); });
+    u->impl->apply(src_dev, batch_stride, dst_dev, batch, n_time, (hipStream_t)stream);
   });
 }
 // ---- wind artifact filter (jet mask, masked Gaussian blend; csrc/wx_wind.h) -----------------------------------------------------
-struct wx_wind {
-  std::unique_ptr<wx::Wind> impl;
-};
+struct wx_wind : Handle<wx::Wind> {};
 int wx_wind_create(int H, int W, const float* smooth_lat, int n_smooth_lat, const float* smooth_lon, int n_smooth_lon,
                    const float* falloff_lat, int n_falloff_lat, const float* falloff_lon, int n_falloff_lon, int dilation_lat,
                    int dilation_lon, float speed_threshold, int preserve_amplitude, int device, wx_wind_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_wind_create: null argument");
-    const float* const w[4] = {smooth_lat, smooth_lon, falloff_lat, falloff_lon};
-    const int n[4] = {n_smooth_lat, n_smooth_lon, n_falloff_lat, n_falloff_lon};
-    const std::string why = wx::wind_check_create(H, W, w, n, dilation_lat, dilation_lon, speed_threshold);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_wind_create: " + why);
-    need_device(device, "wx_wind_create");
-    std::unique_ptr<wx_wind> f(new wx_wind);
-    f->impl.reset(new wx::Wind(H, W, w, n, dilation_lat, dilation_lon, speed_threshold, preserve_amplitude != 0, device));
-    *out = f.release();
-  });
+  const float* const w[4] = {smooth_lat, smooth_lon, falloff_lat, falloff_lon};
+  const int n[4] = {n_smooth_lat, n_smooth_lon, n_falloff_lat, n_falloff_lon};
+  return create("wx_wind_create", out, true, device,
+                [&] { return wx::wind_check_create(H, W, w, n, dilation_lat, dilation_lon, speed_threshold); },
+                [&] { return new wx::Wind(H, W, w, n, dilation_lat, dilation_lon, speed_threshold, preserve_amplitude != 0, device); });
 }
 int wx_wind_destroy(wx_wind_handle f) { return guarded([&] { delete f; }); }
 int wx_wind_apply(wx_wind_handle f, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride, int n_vars,
                   const float* const* src_dev, const int64_t* batch_stride, const int32_t* n_levels, float* const* dst_dev,
                   const int32_t* target_levels, int n_target_levels, int batch, float* mask_out_dev, void* stream) {
-  return guarded([&] {
-    need(f, "wx_wind_apply: null wind-filter handle");
+  return use_remapped(f, "wx_wind_apply: null wind-filter handle", [&] {
     if (!u_dev || !v_dev || !src_dev || !batch_stride || !n_levels || !dst_dev) throw wx::ConfigError("wx_wind_apply: null argument");
-    remap<wx::ConfigError>([&] {
-      f->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, n_vars, src_dev, batch_stride, n_levels, dst_dev, target_levels,
-                     n_target_levels, batch, mask_out_dev, (hipStream_t)stream);
-    });
+    f->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, n_vars, src_dev, batch_stride, n_levels, dst_dev, target_levels,
+                   n_target_levels, batch, mask_out_dev, (hipStream_t)stream);
   });
 }
 // ---- semi-Lagrangian tracer advection (omega, back-trajectory, trilinear gather; csrc/wx_advect.h) -----------------------------
-struct wx_advect {
-  std::unique_ptr<wx::Advect> impl;
-};
+struct wx_advect : Handle<wx::Advect> {};
 int wx_advect_create(int H, int W, int n_levels, const float* a_half, const float* b_half, const float* row_tables, float dlon_rad,
                      float timestep_seconds, int n_iterations, float dp_dlevel_floor, int surface_to_top, int device,
                      wx_advect_handle* out) {
-  return guarded([&] {
-    if (!out || !row_tables) throw wx::ConfigError("wx_advect_create: null argument");
-    const float* rows[6];
+  const float* rows[6];   // the six [H] tables of row_tables, sliced once a non-null row_tables is known
+  const auto check = [&] {
     for (int i = 0; i < 6; ++i) rows[i] = row_tables + (size_t)i * (H > 0 ? H : 0);
-    const std::string why = wx::advect_check_create(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations,
-                                                    dp_dlevel_floor);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_advect_create: " + why);
-    need_device(device, "wx_advect_create");
-    std::unique_ptr<wx_advect> a(new wx_advect);
-    a->impl.reset(new wx::Advect(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations, dp_dlevel_floor,
-                                 surface_to_top != 0, device));
-    *out = a.release();
+    return wx::advect_check_create(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations, dp_dlevel_floor);
+  };
+  return create("wx_advect_create", out, row_tables != nullptr, device, check, [&] {
+    return new wx::Advect(H, W, n_levels, a_half, b_half, rows, dlon_rad, timestep_seconds, n_iterations, dp_dlevel_floor,
+                          surface_to_top != 0, device);
   });
 }
 int wx_advect_destroy(wx_advect_handle a) { return guarded([&] { delete a; }); }
 int wx_advect_apply(wx_advect_handle a, const float* u_dev, int64_t u_batch_stride, const float* v_dev, int64_t v_batch_stride,
                     const float* sp_dev, int64_t sp_batch_stride, const float* omega_dev, int64_t omega_batch_stride, int n_tracers,
                     const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev, int batch, void* stream) {
-  return guarded([&] {
-    if (!a || !a->impl) throw wx::ConfigError("wx_advect_apply: null advection handle");
+  return use_remapped(a, "wx_advect_apply: null advection handle", [&] {
     if (!u_dev || !v_dev || !sp_dev || !src_dev || !batch_stride || !dst_dev) throw wx::ConfigError("wx_advect_apply: null argument");
-    remap<wx::ConfigError>([&] {
-      a->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, sp_dev, sp_batch_stride, omega_dev, omega_batch_stride, n_tracers,
-                     src_dev, batch_stride, dst_dev, batch, (hipStream_t)stream);
-    });
+    a->impl->apply(u_dev, u_batch_stride, v_dev, v_batch_stride, sp_dev, sp_batch_stride, omega_dev, omega_batch_stride, n_tracers,
+                   src_dev, batch_stride, dst_dev, batch, (hipStream_t)stream);
   });
 }
 // ---- hybrid-level interpolation (one set of hybrid levels onto another, linear in log p; csrc/wx_hybrid.h) ----------------------
-struct wx_hybrid {
-  std::unique_ptr<wx::Hybrid> impl;
-};
+struct wx_hybrid : Handle<wx::Hybrid> {};
 int wx_hybrid_create(int H, int W, int n_src, const float* a_src, const float* b_src, int n_dst, const float* a_dst, const float* b_dst,
                      int device, wx_hybrid_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_hybrid_create: null argument");
-    const std::string why = wx::hybrid_check_create(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_hybrid_create: " + why);
-    need_device(device, "wx_hybrid_create");
-    std::unique_ptr<wx_hybrid> h(new wx_hybrid);
-    h->impl.reset(new wx::Hybrid(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst, device));
-    *out = h.release();
-  });
+  return create("wx_hybrid_create", out, true, device,
+                [&] { return wx::hybrid_check_create(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst); },
+                [&] { return new wx::Hybrid(H, W, n_src, a_src, b_src, n_dst, a_dst, b_dst, device); });
 }
 int wx_hybrid_destroy(wx_hybrid_handle h) { return guarded([&] { delete h; }); }
 int wx_hybrid_apply(wx_hybrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, float* const* dst_dev,
                     int batch, int n_time, const float* sp_dev, int64_t sp_batch_stride, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_hybrid_apply: null hybrid-interpolation handle");
+  return use_remapped(h, "wx_hybrid_apply: null hybrid-interpolation handle", [&] {
     if (!src_dev || !batch_stride || !dst_dev || !sp_dev) throw wx::ConfigError("wx_hybrid_apply: null argument");
-    remap<wx::ConfigError>([&] {
-      h->impl->apply(n_vars, src_dev, batch_stride, dst_dev, batch, n_time, sp_dev, sp_batch_stride, (hipStream_t)stream);
-    });
+    h->impl->apply(n_vars, src_dev, batch_stride, dst_dev, batch, n_time, sp_dev, sp_batch_stride, (hipStream_t)stream);
   });
 }
 // ---- horizontal regridding (an ESMF sparse weight matrix on every plane, sliced-ELL SpMM; csrc/wx_regrid.h) -------------------------
-struct wx_regrid {
-  std::unique_ptr<wx::Regrid> impl;
-};
+struct wx_regrid : Handle<wx::Regrid> {};
 int wx_regrid_create(int64_t n_a, int64_t n_b, const int64_t* row_ptr, const int32_t* col, const float* val, int device,
                      wx_regrid_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_regrid_create: null argument");
-    const std::string why = wx::regrid_check_create(n_a, n_b, row_ptr, col, val);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_regrid_create: " + why);
-    need_device(device, "wx_regrid_create");
-    std::unique_ptr<wx_regrid> h(new wx_regrid);
-    h->impl.reset(new wx::Regrid(n_a, n_b, row_ptr, col, val, device));
-    *out = h.release();
-  });
+  return create("wx_regrid_create", out, true, device, [&] { return wx::regrid_check_create(n_a, n_b, row_ptr, col, val); },
+                [&] { return new wx::Regrid(n_a, n_b, row_ptr, col, val, device); });
 }
 int wx_regrid_destroy(wx_regrid_handle h) { return guarded([&] { delete h; }); }
 int wx_regrid_apply(wx_regrid_handle h, int n_vars, const float* const* src_dev, const int64_t* batch_stride, const int32_t* planes_per_item,
                     int batch, float* const* dst_dev, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_regrid_apply: null regridding handle");
+  return use_remapped(h, "wx_regrid_apply: null regridding handle", [&] {
     if (!src_dev || !batch_stride || !planes_per_item || !dst_dev) throw wx::ConfigError("wx_regrid_apply: null argument");
-    remap<wx::ConfigError>([&] { h->impl->apply(n_vars, src_dev, batch_stride, planes_per_item, batch, dst_dev, (hipStream_t)stream); });
+    h->impl->apply(n_vars, src_dev, batch_stride, planes_per_item, batch, dst_dev, (hipStream_t)stream);
   });
 }
 // ---- TISR forcing (top-of-atmosphere incident solar radiation per step, a coefficient table and one sum per point; csrc/wx_tisr.h) ----
-struct wx_tisr {
-  std::unique_ptr<wx::Tisr> impl;
-};
+struct wx_tisr : Handle<wx::Tisr> {};
 int wx_tisr_create(int ny, int nx, const float* lat_host, const float* lon_host, int n_tsi, const float* tsi_times_host,
                    const float* tsi_values_host, int device, wx_tisr_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_tisr_create: null argument");
-    const std::string why = wx::tisr_check_create(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_tisr_create: " + why);
-    need_device(device, "wx_tisr_create");
-    std::unique_ptr<wx_tisr> h(new wx_tisr);
-    h->impl.reset(new wx::Tisr(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host, device));
-    *out = h.release();
-  });
+  return create("wx_tisr_create", out, true, device,
+                [&] { return wx::tisr_check_create(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host); },
+                [&] { return new wx::Tisr(ny, nx, lat_host, lon_host, n_tsi, tsi_times_host, tsi_values_host, device); });
 }
 int wx_tisr_destroy(wx_tisr_handle h) { return guarded([&] { delete h; }); }
 int wx_tisr_compute(wx_tisr_handle h, int n_times, const int64_t* t_end_ns_host, int64_t period_ns, int n_steps, float* dst_dev,
                     int64_t plane_stride, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_tisr_compute: null TISR handle");
-    remap<wx::ConfigError>([&] { h->impl->compute(n_times, t_end_ns_host, period_ns, n_steps, dst_dev, plane_stride, (hipStream_t)stream); });
+  return use_remapped(h, "wx_tisr_compute: null TISR handle", [&] {
+    h->impl->compute(n_times, t_end_ns_host, period_ns, n_steps, dst_dev, plane_stride, (hipStream_t)stream);
   });
 }
 // ---- perturbed initial conditions (white, colour-filtered and AR(1) noise on the planes of one member; csrc/wx_perturb.h) ----------
-struct wx_perturb {
-  std::unique_ptr<wx::Perturb> impl;
-};
+struct wx_perturb : Handle<wx::Perturb> {};
 int wx_perturb_create(int H, int W, int kind, const float* S_host, int device, wx_perturb_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_perturb_create: null argument");
-    const std::string why = wx::perturb_check_create(H, W, kind, S_host);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_perturb_create: " + why);
-    need_device(device, "wx_perturb_create");
-    std::unique_ptr<wx_perturb> h(new wx_perturb);
-    h->impl.reset(new wx::Perturb(H, W, kind, S_host, device));
-    *out = h.release();
-  });
+  return create("wx_perturb_create", out, true, device, [&] { return wx::perturb_check_create(H, W, kind, S_host); },
+                [&] { return new wx::Perturb(H, W, kind, S_host, device); });
 }
 int wx_perturb_destroy(wx_perturb_handle h) { return guarded([&] { delete h; }); }
 int wx_perturb_batch(wx_perturb_handle h, int* planes_out) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_perturb_batch: null perturbation handle");
+  return use(h, "wx_perturb_batch: null perturbation handle", [&] {
     if (!planes_out) throw wx::ConfigError("wx_perturb_batch: null argument");
     *planes_out = h->impl->batch_planes();
   });
@@ -463,145 +421,105 @@ int wx_perturb_apply(wx_perturb_handle h, int n_planes, const float* tape_dev, u
                      const float* chan_scale_host, float rho, const float* prev_dev, int64_t prev_stride, const float* lat_weight_host,
                      const float* x_dev, int64_t x_stride, float* delta_out_dev, int64_t delta_stride, float* x_out_dev, int64_t x_out_stride,
                      void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_perturb_apply: null perturbation handle");
-    remap<wx::ConfigError>([&] {
-      h->impl->apply(n_planes, tape_dev, seed, member, step, amplitude, chan_scale_host, rho, prev_dev, prev_stride, lat_weight_host, x_dev, x_stride,
-                     delta_out_dev, delta_stride, x_out_dev, x_out_stride, (hipStream_t)stream);
-    });
+  return use_remapped(h, "wx_perturb_apply: null perturbation handle", [&] {
+    h->impl->apply(n_planes, tape_dev, seed, member, step, amplitude, chan_scale_host, rho, prev_dev, prev_stride, lat_weight_host, x_dev, x_stride,
+                   delta_out_dev, delta_stride, x_out_dev, x_out_stride, (hipStream_t)stream);
   });
 }
 // ---- zonal power spectra (PSD, latitude-mean spectra and the two spectral scores from a folded fp64 DFT; csrc/wx_spectrum.h) -------
-struct wx_spectrum {
-  std::unique_ptr<wx::Spectrum> impl;
-};
+struct wx_spectrum : Handle<wx::Spectrum> {};
 int wx_spectrum_create(int H, int W, const float* lat_w_host, int device, wx_spectrum_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_spectrum_create: null argument");
-    const std::string why = wx::spectrum_check_create(H, W, lat_w_host);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_spectrum_create: " + why);
-    need_device(device, "wx_spectrum_create");
-    std::unique_ptr<wx_spectrum> h(new wx_spectrum);
-    h->impl.reset(new wx::Spectrum(H, W, lat_w_host, device));
-    *out = h.release();
-  });
+  return create("wx_spectrum_create", out, true, device, [&] { return wx::spectrum_check_create(H, W, lat_w_host); },
+                [&] { return new wx::Spectrum(H, W, lat_w_host, device); });
 }
 int wx_spectrum_destroy(wx_spectrum_handle h) { return guarded([&] { delete h; }); }
 int wx_spectrum_apply(wx_spectrum_handle h, int n_planes, const float* a_dev, int64_t a_stride, const float* b_dev, int64_t b_stride, int k_init,
                       float* psd_a_dev, float* psd_b_dev, double* mean_psd_a_dev, double* mean_psd_b_dev, double* mean_amp_a_dev,
                       double* mean_amp_b_dev, double* scores_dev, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_spectrum_apply: null spectrum handle");
-    remap<wx::ConfigError>([&] {
-      h->impl->apply(n_planes, a_dev, a_stride, b_dev, b_stride, k_init, psd_a_dev, psd_b_dev, mean_psd_a_dev, mean_psd_b_dev, mean_amp_a_dev,
-                     mean_amp_b_dev, scores_dev, (hipStream_t)stream);
-    });
+  return use_remapped(h, "wx_spectrum_apply: null spectrum handle", [&] {
+    h->impl->apply(n_planes, a_dev, a_stride, b_dev, b_stride, k_init, psd_a_dev, psd_b_dev, mean_psd_a_dev, mean_psd_b_dev, mean_amp_a_dev,
+                   mean_amp_b_dev, scores_dev, (hipStream_t)stream);
   });
 }
 // ---- verification metrics (the eight per-variable scores from one two-pass fp64 reduction; csrc/wx_metrics.h) --------------------
-struct wx_metrics {
-  std::unique_ptr<wx::Metrics> impl;
-};
+struct wx_metrics : Handle<wx::Metrics> {};
 int wx_metrics_create(int H, int W, const float* lat_w, int device, wx_metrics_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_metrics_create: null argument");
-    const std::string why = wx::grid_check(H, W, lat_w);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_metrics_create: " + why);
-    need_device(device, "wx_metrics_create");
-    std::unique_ptr<wx_metrics> h(new wx_metrics);
-    h->impl.reset(new wx::Metrics(H, W, lat_w, device));
-    *out = h.release();
-  });
+  return create("wx_metrics_create", out, true, device, [&] { return wx::grid_check(H, W, lat_w); },
+                [&] { return new wx::Metrics(H, W, lat_w, device); });
 }
 int wx_metrics_destroy(wx_metrics_handle h) { return guarded([&] { delete h; }); }
 int wx_metrics_apply(wx_metrics_handle h, int n_vars, const float* const* pred_dev, const int64_t* pred_batch_stride,
                      const float* const* target_dev, const int64_t* target_batch_stride, const float* const* clim_dev,
                      const int64_t* clim_level_stride, const int64_t* clim_time_stride, const int32_t* n_levels, const int32_t* n_time,
                      int batch, double eps, float* scores_dev, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_metrics_apply: null metrics handle");
+  return use_remapped(h, "wx_metrics_apply: null metrics handle", [&] {
     if (!pred_dev || !pred_batch_stride || !target_dev || !target_batch_stride || !n_levels || !n_time || !scores_dev)
       throw wx::ConfigError("wx_metrics_apply: null argument");
-    remap<wx::ConfigError>([&] {
-      h->impl->apply(n_vars, pred_dev, pred_batch_stride, target_dev, target_batch_stride, clim_dev, clim_level_stride, clim_time_stride,
-                     n_levels, n_time, batch, eps, scores_dev, (hipStream_t)stream);
-    });
+    h->impl->apply(n_vars, pred_dev, pred_batch_stride, target_dev, target_batch_stride, clim_dev, clim_level_stride, clim_time_stride,
+                   n_levels, n_time, batch, eps, scores_dev, (hipStream_t)stream);
   });
 }
 // ---- ensemble verification (CRPS, spread, ensemble-mean error from one reading pass; csrc/wx_ensemble.h) ---------------------------
-struct wx_ensemble {
-  std::unique_ptr<wx::Ensemble> impl;
-};
+struct wx_ensemble : Handle<wx::Ensemble> {};
 int wx_ensemble_create(int H, int W, const float* lat_w, int n_members, int device, wx_ensemble_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_ensemble_create: null argument");
-    const std::string why = wx::ensemble_check_create(H, W, lat_w, n_members);   // needs no device to be told
-    if (!why.empty()) throw wx::ConfigError("wx_ensemble_create: " + why);
-    need_device(device, "wx_ensemble_create");
-    std::unique_ptr<wx_ensemble> h(new wx_ensemble);
-    h->impl.reset(new wx::Ensemble(H, W, lat_w, n_members, device));
-    *out = h.release();
-  });
+  return create("wx_ensemble_create", out, true, device, [&] { return wx::ensemble_check_create(H, W, lat_w, n_members); },
+                [&] { return new wx::Ensemble(H, W, lat_w, n_members, device); });
 }
 int wx_ensemble_destroy(wx_ensemble_handle h) { return guarded([&] { delete h; }); }
 int wx_ensemble_apply(wx_ensemble_handle h, int n_vars, const float* const* member_dev, const int64_t* member_batch_stride,
                       const float* const* target_dev, const int64_t* target_batch_stride, const int32_t* n_levels, const int32_t* n_time,
                       int batch, double alpha, float* const* maps_dev, double* planes_dev, void* stream) {
-  return guarded([&] {
-    if (!h || !h->impl) throw wx::ConfigError("wx_ensemble_apply: null ensemble handle");
+  return use_remapped(h, "wx_ensemble_apply: null ensemble handle", [&] {
     if (!member_dev || !member_batch_stride || !target_dev || !target_batch_stride || !n_levels || !n_time || !planes_dev)
       throw wx::ConfigError("wx_ensemble_apply: null argument");
-    remap<wx::ConfigError>([&] {
-      h->impl->apply(n_vars, member_dev, member_batch_stride, target_dev, target_batch_stride, n_levels, n_time, batch, alpha, maps_dev,
-                     planes_dev, (hipStream_t)stream);
-    });
+    h->impl->apply(n_vars, member_dev, member_batch_stride, target_dev, target_batch_stride, n_levels, n_time, batch, alpha, maps_dev,
+                   planes_dev, (hipStream_t)stream);
   });
 }
 // ---- post block ------------------------------------------------------------------------------------------------
-struct wx_post {
-  std::unique_ptr<wx::PostBlock> impl;
-};
+struct wx_post : Handle<wx::PostBlock> {};
 int wx_post_create(int H, int W, int c_in, int frames, int c_out, int device, wx_post_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_post_create: null argument");
-    need_device(device, "wx_post_create");
-    std::unique_ptr<wx_post> p(new wx_post);
-    p->impl.reset(new wx::PostBlock(H, W, c_in, frames, c_out, device));
-    *out = p.release();
-  });
+  return create("wx_post_create", out, true, device, no_check, [&] { return new wx::PostBlock(H, W, c_in, frames, c_out, device); });
 }
 int wx_post_destroy(wx_post_handle p) { return guarded([&] { delete p; }); }
 int wx_post_set_band(wx_post_handle p, int row0, int rows) {
-  return guarded([&] { need(p, "null post handle"); p->impl->set_band(row0, rows); });
+  return use(p, "null post handle", [&] { p->impl->set_band(row0, rows); });
 }
 int wx_post_set_grid_sigma(wx_post_handle p, const float* lat2d, const float* lon2d, const float* coef_a, const float* coef_b,
                            int n_levels, int midpoint, int sp_ind) {
-  return guarded([&] {
-    need(p, "null post-block handle");
+  return use(p, "null post-block handle", [&] {
     if (!lat2d || !lon2d || !coef_a || !coef_b) throw wx::ConfigError("wx_post_set_grid_sigma: null argument");
     p->impl->set_grid_sigma(lat2d, lon2d, coef_a, coef_b, n_levels, midpoint, sp_ind);
   });
 }
 int wx_post_set_grid(wx_post_handle p, const float* lat2d, const float* lon2d, const float* p_levels, int n_levels, int midpoint) {
-  return guarded([&] { need(p, "null post-block handle"); if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument"); p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint); });
+  return use(p, "null post-block handle", [&] {
+    if (!lat2d || !lon2d || !p_levels) throw wx::ConfigError("wx_post_set_grid: null argument");
+    p->impl->set_grid(lat2d, lon2d, p_levels, n_levels, midpoint);
+  });
 }
 int wx_post_set_stats(wx_post_handle p, const float* mi, const float* si, const float* mo, const float* so) {
-  return guarded([&] { need(p, "null post-block handle"); if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument"); p->impl->set_stats(mi, si, mo, so); });
+  return use(p, "null post-block handle", [&] {
+    if (!mi || !si || !mo || !so) throw wx::ConfigError("wx_post_set_stats: null argument");
+    p->impl->set_stats(mi, si, mo, so);
+  });
 }
 int wx_post_add_tracer_fixer(wx_post_handle p, const int32_t* inds, const float* thres, const float* thres_max, int n, int denorm) {
-  return guarded([&] { need(p, "null post-block handle"); if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument"); p->impl->add_tracer(inds, thres, thres_max, n, denorm); });
+  return use(p, "null post-block handle", [&] {
+    if (n < 1 || !inds || !thres) throw wx::ConfigError("wx_post_add_tracer_fixer: bad argument");
+    p->impl->add_tracer(inds, thres, thres_max, n, denorm);
+  });
 }
 int wx_post_add_mass_fixer(wx_post_handle p, int q_start, int fix_level_num, int denorm) {
-  return guarded([&] { need(p, "null post-block handle"); p->impl->add_mass(q_start, fix_level_num, denorm); });
+  return use(p, "null post-block handle", [&] { p->impl->add_mass(q_start, fix_level_num, denorm); });
 }
 int wx_post_add_water_fixer(wx_post_handle p, int q_start, int precip_ind, int evapor_ind, float n_seconds, int denorm) {
-  return guarded([&] { need(p, "null post-block handle"); p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
+  return use(p, "null post-block handle", [&] { p->impl->add_water(q_start, precip_ind, evapor_ind, n_seconds, denorm); });
 }
 int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, int n_toa,
                                     const int32_t* toa_inds, const float* toa_signs, int n_srf, const int32_t* srf_inds,
                                     const float* srf_signs, const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] {
-    need(p, "null post-block handle");
+  return use(p, "null post-block handle", [&] {
     if (!toa_inds || !toa_signs || !srf_inds || !srf_signs || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_signed: null argument");
     p->impl->add_energy_signed(T_start, q_start, U_start, V_start, n_toa, toa_inds, toa_signs, n_srf, srf_inds, srf_signs, gph_surf,
                                n_seconds, denorm);
@@ -609,53 +527,51 @@ int wx_post_add_energy_fixer_signed(wx_post_handle p, int T_start, int q_start, 
 }
 int wx_post_add_energy_fixer_updown(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t flux_inds[9],
                                     const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] {
-    need(p, "null post-block handle");
+  return use(p, "null post-block handle", [&] {
     if (!flux_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer_updown: null argument");
     p->impl->add_energy_updown(T_start, q_start, U_start, V_start, flux_inds, gph_surf, n_seconds, denorm);
   });
 }
 int wx_post_add_energy_fixer(wx_post_handle p, int T_start, int q_start, int U_start, int V_start, const int32_t rad_inds[6],
                              const float* gph_surf, float n_seconds, int denorm) {
-  return guarded([&] { need(p, "null post-block handle"); if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument"); p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm); });
+  return use(p, "null post-block handle", [&] {
+    if (!rad_inds || !gph_surf) throw wx::ConfigError("wx_post_add_energy_fixer: null argument");
+    p->impl->add_energy(T_start, q_start, U_start, V_start, rad_inds, gph_surf, n_seconds, denorm);
+  });
 }
 int wx_post_apply(wx_post_handle p, const float* x_dev, float* y_dev, void* stream) {
-  return guarded([&] { need(p, "null post-block handle"); if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer"); p->impl->apply(x_dev, y_dev, (hipStream_t)stream); });
+  return use(p, "null post-block handle", [&] {
+    if (!x_dev || !y_dev) throw wx::ConfigError("wx_post_apply: null pointer");
+    p->impl->apply(x_dev, y_dev, (hipStream_t)stream);
+  });
 }
 int wx_attach_postblock(wx_handle h, wx_post_handle p) {
   return guarded([&] { need(h, "null engine handle"); h->impl->attach_post(p ? p->impl.get() : nullptr); });
 }
 
 // ---- pressure-level products (geopotential, model -> pressure levels, MSLP; csrc/wx_diag.h) ------------------------------------
-struct wx_diag {
-  std::unique_ptr<wx::Diag> impl;
-};
+struct wx_diag : Handle<wx::Diag> {};
 int wx_diag_create(int H, int W, int n_levels, int device, wx_diag_handle* out) {
-  return guarded([&] {
-    if (!out) throw wx::ConfigError("wx_diag_create: null argument");
-    if (n_levels < 2 || n_levels > wx::kDiagMaxLevels) throw wx::ConfigError("wx_diag_create: n_levels must be 2 .. 137");   // needs no device to be told
-    need_device(device, "wx_diag_create");
-    std::unique_ptr<wx_diag> d(new wx_diag);
-    remap<wx::ConfigError>([&] { d->impl.reset(new wx::Diag(H, W, n_levels, device)); });
-    *out = d.release();
-  });
+  return create("wx_diag_create", out, true, device,
+                [&] { return n_levels < 2 || n_levels > wx::kDiagMaxLevels ? "n_levels must be 2 .. 137" : ""; }, [&] {
+                  wx::Diag* d = nullptr;
+                  remap<wx::ConfigError>([&] { d = new wx::Diag(H, W, n_levels, device); });
+                  return d;
+                });
 }
 int wx_diag_destroy(wx_diag_handle d) { return guarded([&] { delete d; }); }
 int wx_diag_set_levels(wx_diag_handle d, const float* a_half, const float* b_half, const float* a_mid, const float* b_mid, int flip_vertical) {
-  return guarded([&] { need(d, "null diagnostics handle"); remap<wx::ConfigError>([&] { d->impl->set_levels(a_half, b_half, a_mid, b_mid, flip_vertical); }); });
+  return use_remapped(d, "null diagnostics handle", [&] { d->impl->set_levels(a_half, b_half, a_mid, b_mid, flip_vertical); });
 }
 int wx_diag_set_pressure_levels(wx_diag_handle d, const float* p_pa, int n_plev, float temp_height) {
-  return guarded([&] { need(d, "null diagnostics handle"); remap<wx::ConfigError>([&] { d->impl->set_pressure_levels(p_pa, n_plev, temp_height); }); });
+  return use_remapped(d, "null diagnostics handle", [&] { d->impl->set_pressure_levels(p_pa, n_plev, temp_height); });
 }
 int wx_diag_apply(wx_diag_handle d, int batch, int n_time, const float* T, const float* q, const float* sp, const float* phis,
                   int phis_n_time, const float* t_near_surface, const float* const* fields, int n_fields, float* z_model_out,
                   float* const* plev_out, float* mslp_out, void* stream) {
-  return guarded([&] {
-    need(d, "null diagnostics handle");
-    remap<wx::ConfigError>([&] {
-      d->impl->apply(batch, n_time, T, q, sp, phis, phis_n_time, t_near_surface, fields, n_fields, z_model_out, plev_out, mslp_out,
-                     (hipStream_t)stream);
-    });
+  return use_remapped(d, "null diagnostics handle", [&] {
+    d->impl->apply(batch, n_time, T, q, sp, phis, phis_n_time, t_near_surface, fields, n_fields, z_model_out, plev_out, mslp_out,
+                   (hipStream_t)stream);
   });
 }
 
@@ -737,9 +653,7 @@ int wx_winattn_apply(wx_winattn_handle w, const void* qkv_dev, void* out_dev, vo
 }
 
 // ---- a stage of Swin V2 (Cr) blocks (BASELINE config 5: the FuXi U-Transformer's stage) -----------------
-struct wx_swin {
-  std::unique_ptr<wx::SwinStageBase> impl;
-};
+struct wx_swin : Handle<wx::SwinStageBase> {};
 int wx_swin_create(const wx_swin_desc* d, int device, wx_swin_handle* out) {
   return guarded([&] {
     if (!d || !out) throw wx::ConfigError("null argument");
@@ -784,9 +698,7 @@ int wx_swin_flops(wx_swin_handle w, double* flops) {
 int wx_swin_destroy(wx_swin_handle w) { return guarded([&] { delete w; }); }
 
 // ---- the FuXi forward (BASELINE config 5; credit/models/fuxi.py:454-500) -----------------------------------------------------------
-struct wx_fuxi {
-  std::unique_ptr<wx::FuxiBase> impl;
-};
+struct wx_fuxi : Handle<wx::FuxiBase> {};
 int wx_fuxi_create(const wx_fuxi_desc* d, int device, wx_fuxi_handle* out) {
   return guarded([&] {
     if (!d || !out) throw wx::ConfigError("null argument");

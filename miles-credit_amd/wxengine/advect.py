@@ -23,7 +23,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .diagnostics import _lookup
-from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _named_tensor_args, _stream_ptr, load_library
+from .native import (HandleCache, WXEngineError, _check, _f32, _named_tensor_args, _stream_ptr, batch_stride, check_named_tensor, copy_batch,
+                     load_library, require_gpu)
 from .transforms import _check_data_types
 
 logger = logging.getLogger(__name__)
@@ -110,11 +111,8 @@ class _AdvectionEngine:
             raise ValueError(f"{name}: {self.lat_deg.size} latitude(s); the latitude spacing needs at least two")
         self._warned = False
         self._tables = {}    # (H, W) -> metric_tables
-        self._handles = {}   # (H, W, L, device) -> NativeHandle
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the semi-Lagrangian advection has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the semi-Lagrangian advection has no CPU fallback", load=load_library)
+        self._handles = HandleCache(self.lib, "wx_advect")   # by (H, W, L, device)
 
     def grid_for(self, H: int, W: int):
         """advect.py:301-314: the given coordinates where their lengths match the data grid, else the uniform global grid, with one
@@ -128,31 +126,19 @@ class _AdvectionEngine:
         return uniform_grid(H, W)
 
     def _handle(self, H, W, L, dev):
-        if (H, W, L, dev) not in self._handles:
+        def args():
             if (H, W) not in self._tables:
                 self._tables[(H, W)] = metric_tables(*self.grid_for(H, W), self.coslat_floor)
             t = self._tables[(H, W)]
-            h = NativeHandle(self.lib.wx_advect_destroy)
-            _check(self.lib.wx_advect_create(H, W, L, _f32(self.a_half), _f32(self.b_half), _f32(t["rows"]), float(t["dlon"]),
-                                             self.timestep_seconds, self.n_iterations, self.dp_dlevel_floor,
-                                             int(self.level_order == "surface_to_top"), dev, h.out))
-            self._handles[(H, W, L, dev)] = h
-        return self._handles[(H, W, L, dev)]
-
-    @staticmethod
-    def _check_tensor(key, t):
-        if not _gpu_tensor(t, ndim=5):
-            raise WXEngineError(f"{key} must be a float32 [B, n_levels, 1, H, W] tensor on the GPU")
-        if t.shape[2] != 1:
-            raise WXEngineError(f"{key}: n_time = {t.shape[2]}; the device block advects one time level (n_time must be 1)")
-        if not _gpu_tensor(t, item_contiguous=True):
-            raise WXEngineError(f"{key}: a batch item must be contiguous [n_levels, 1, H, W] memory")
+            return (H, W, L, _f32(self.a_half), _f32(self.b_half), _f32(t["rows"]), float(t["dlon"]), self.timestep_seconds,
+                    self.n_iterations, self.dp_dlevel_floor, int(self.level_order == "surface_to_top"), dev)
+        return self._handles.get((H, W, L, dev), args)
 
     def advect_nested(self, nested: dict) -> None:
         """advect.py:325-423: every tracer of `nested` ({source: {var_key: tensor}}) advected one step; the tracers' entries are rebound."""
         import torch
         u = _lookup(nested, self.u_var)
-        self._check_tensor(self.u_var, u)
+        check_named_tensor(self.u_var, u, one_time=True)
         B, L, _, H, W = u.shape
         named = [(self.v_var, _lookup(nested, self.v_var), L), (self.surface_pressure_var, _lookup(nested, self.surface_pressure_var), 1)]
         if self.omega_var is not None:
@@ -160,12 +146,10 @@ class _AdvectionEngine:
         ts = [_lookup(nested, k) for k in self.tracer_vars]
         named += [(k, t, L) for k, t in zip(self.tracer_vars, ts)]
         for key, t, levels in named:
-            self._check_tensor(key, t)
-            if t.device != u.device:
-                raise WXEngineError(f"{key} is on {t.device}, {self.u_var} on {u.device}: all tensors of one call live on one device")
-            if tuple(t.shape) != (B, levels, 1, H, W):
+            check_named_tensor(key, t, like=(self.u_var, u), one_time=True)
+            if t.shape[1] != levels:
                 raise WXEngineError(f"{key}: shape {tuple(t.shape)} does not match {self.u_var}: {tuple(u.shape)} "
-                                    f"(batch and H x W must agree, and the block needs {levels} level(s) here)")
+                                    f"(the block needs {levels} level(s) here)")
         if self.a_half.size != L + 1:
             raise ValueError(f"SemiLagrangianAdvection: built {self.a_half.size} interface pressures for {L} levels; expected {L + 1}. "
                              "Set `levels` to the model levels present in the data.")
@@ -176,13 +160,12 @@ class _AdvectionEngine:
         dev = u.device.index
         h = self._handle(H, W, L, dev)
         src, bs, _, outs, dst = _named_tensor_args(ts)
-        stride = lambda t: t.stride(0) if B > 1 else 0  # noqa: E731
         v, sp = named[0][1], named[1][1]
         om = named[2][1] if self.omega_var is not None else None
         with torch.cuda.device(dev):
-            _check(self.lib.wx_advect_apply(h, C.c_void_p(u.data_ptr()), stride(u), C.c_void_p(v.data_ptr()), stride(v),
-                                            C.c_void_p(sp.data_ptr()), stride(sp), C.c_void_p(om.data_ptr()) if om is not None else None,
-                                            stride(om) if om is not None else 0, len(ts), src, bs, dst, B, _stream_ptr(dev)))
+            _check(self.lib.wx_advect_apply(h, C.c_void_p(u.data_ptr()), batch_stride(u, B), C.c_void_p(v.data_ptr()), batch_stride(v, B),
+                                            C.c_void_p(sp.data_ptr()), batch_stride(sp, B), C.c_void_p(om.data_ptr()) if om is not None else None,
+                                            batch_stride(om, B) if om is not None else 0, len(ts), src, bs, dst, B, _stream_ptr(dev)))
         for key, o in zip(self.tracer_vars, outs):
             nested[key.split("/")[0]][key] = o
 
@@ -210,10 +193,9 @@ class SemiLagrangianAdvectionPre:
         self.engine = _AdvectionEngine(**engine_kwargs)
 
     def __call__(self, batch: dict) -> dict:
-        batch = dict(batch)      # new dicts down to the variable level of what is advected (credit/preblock/base.py:12-22): tensors are shared
+        batch = copy_batch(batch, self.data_types)
         for data_type in self.data_types:
             if data_type in batch:       # absent (no "target" at inference): skipped
-                batch[data_type] = {src: dict(variables) for src, variables in batch[data_type].items()}
                 self.engine.advect_nested(batch[data_type])
         return batch
 

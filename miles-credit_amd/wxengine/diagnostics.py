@@ -22,7 +22,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import WXDiag, WXEngineError, load_library
+from .engine import WXDiag
+from .native import require_gpu
 
 _T = "ARCO_ERA5/prognostic/3d/temperature"
 _Q = "ARCO_ERA5/prognostic/3d/specific_humidity"
@@ -59,10 +60,7 @@ def pressure_output_key(var_key: str, output_suffix: str = "_PRES") -> str:
 
 
 def _require_device():
-    import torch
-    load_library()
-    if not torch.cuda.is_available():
-        raise WXEngineError("no GPU visible: the pressure-level products have no CPU fallback")
+    require_gpu("the pressure-level products have no CPU fallback")
 
 
 def _lookup(nested: dict, var_key: str):

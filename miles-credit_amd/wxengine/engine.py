@@ -7,296 +7,18 @@ missing or no GPU is visible, construction raises.
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 
 from .config import WXConfig
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# WX_LIBRARY: an alternate build of the SAME sources (A/B timing of compile-time switches); the source-hash check still applies
-LIB_PATH = os.environ.get("WX_LIBRARY") or os.path.join(_HERE, "libwxengine.so")
+from .native import (LIB_PATH, NativeHandle, WXEngineError, _check, _check_not_stale, _f32, _gpu_tensor, _i32,  # noqa: F401
+                     _named_tensor_args, _stream_ptr, exported_symbols, load_library, require_gpu, wx_band_msg, wx_config,
+                     wx_kernel_stat)
 
 WX_ABI_VERSION = 3
 ARCH = {"crossformer": 0, "wxformer": 1, "crossformer_upconv": 2, "camulator": 3}
 PREC = {"fp32": 0, "bf16": 1, "fp32s": 2}   # fp32s: fp32 storage, split-bf16 GEMM arithmetic (WX_PREC_FP32_SPLIT)
-
-
-class wx_config(C.Structure):
-    _fields_ = [
-        ("abi_version", C.c_int32),
-        ("image_height", C.c_int32), ("image_width", C.c_int32),
-        ("frames", C.c_int32), ("output_frames", C.c_int32),
-        ("channels", C.c_int32), ("surface_channels", C.c_int32), ("input_only_channels", C.c_int32),
-        ("output_only_channels", C.c_int32), ("levels", C.c_int32),
-        ("dim", C.c_int32 * 4), ("depth", C.c_int32 * 4), ("dim_head", C.c_int32),
-        ("global_window_size", C.c_int32 * 4), ("local_window_size", C.c_int32 * 4),
-        ("n_embed_kernels", C.c_int32 * 4), ("embed_kernels", (C.c_int32 * 4) * 4), ("embed_strides", C.c_int32 * 4),
-        ("pad_activate", C.c_int32), ("pad_lat", C.c_int32 * 2), ("pad_lon", C.c_int32 * 2),
-        ("interp", C.c_int32), ("use_spectral_norm", C.c_int32), ("precision", C.c_int32), ("max_batch", C.c_int32),
-        ("arch", C.c_int32),
-        ("noise_latent_dim", C.c_int32), ("encoder_noise", C.c_int32), ("noise_correlated", C.c_int32),
-    ]
-
-
-class wx_band_msg(C.Structure):
-    _fields_ = [("peer", C.c_int32), ("offset", C.c_int64), ("bytes", C.c_int64)]
-
-
-class wx_kernel_stat(C.Structure):
-    _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
-                ("bytes", C.c_double)]
-
-
-class WXEngineError(RuntimeError):
-    pass
-
-
-_lib = None
-
-_PROTOTYPES = {
-    "wx_create": ([C.POINTER(wx_config), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_load_tensor": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int64)], C.c_int),
-    "wx_finalize_weights": ([C.c_void_p], C.c_int),
-    "wx_destroy": ([C.c_void_p], C.c_int),
-    "wx_num_tensors": ([C.c_void_p], C.c_int),
-    "wx_tensor_info": ([C.c_void_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_int), C.POINTER(C.c_int64)], C.c_int),
-    "wx_set_denorm": ([C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int], C.c_int),
-    "wx_set_tracer_fixer": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int], C.c_int),
-    "wx_set_layout": ([C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_int),
-    "wx_set_layout_groups": ([C.c_void_p, C.c_int] + [C.POINTER(C.c_int32)] * 4, C.c_int),
-    "wx_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
-    "wx_step": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_rollout": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p], C.c_int),
-    "wx_band_enable": ([C.c_void_p, C.c_int, C.c_int], C.c_int),
-    "wx_band_info": ([C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)], C.c_int),
-    "wx_band_set_staging": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64], C.c_int),
-    "wx_band_exchange": ([C.c_void_p, C.c_int, C.POINTER(wx_band_msg), C.c_int, C.POINTER(C.c_int), C.POINTER(wx_band_msg), C.c_int,
-                          C.POINTER(C.c_int)], C.c_int),
-    "wx_band_begin": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)], C.c_int),
-    "wx_band_resume": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
-    "wx_band_rccl_unique_id": ([C.POINTER(C.c_uint8)], C.c_int),
-    "wx_band_rccl_init": ([C.c_void_p, C.POINTER(C.c_uint8)], C.c_int),
-    "wx_band_step_rccl": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_band_plan_create": ([C.POINTER(wx_config), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_band_plan_destroy": ([C.c_void_p], C.c_int),
-    "wx_band_plan_num_exchanges": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
-    "wx_band_plan_exchange_name": ([C.c_void_p, C.c_int, C.POINTER(C.c_char_p)], C.c_int),
-    "wx_band_plan_messages": ([C.c_void_p, C.c_int, C.c_int, C.POINTER(wx_band_msg), C.c_int, C.POINTER(C.c_int), C.POINTER(wx_band_msg),
-                               C.c_int, C.POINTER(C.c_int)], C.c_int),
-    "wx_band_plan_partition": ([C.c_void_p, C.c_int, C.POINTER(C.c_int32)], C.c_int),
-    "wx_set_noise": ([C.c_void_p, C.c_uint64, C.c_int, C.c_int], C.c_int),
-    "wx_set_noise_tape": ([C.c_void_p, C.POINTER(C.c_void_p), C.c_int], C.c_int),
-    "wx_set_debug": ([C.c_void_p, C.c_int], C.c_int),
-    "wx_debug_read": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)], C.c_int),
-    "wx_query": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)], C.c_int),
-    "wx_profile": ([C.c_void_p, C.c_int], C.c_int),
-    "wx_profile_reset": ([C.c_void_p], C.c_int),
-    "wx_profile_read": ([C.c_void_p, C.POINTER(wx_kernel_stat), C.c_int, C.POINTER(C.c_int)], C.c_int),
-    "wx_post_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_post_destroy": ([C.c_void_p], C.c_int),
-    "wx_post_set_band": ([C.c_void_p, C.c_int, C.c_int], C.c_int),
-    "wx_pre_create": ([C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
-                       C.POINTER(C.c_void_p)], C.c_int),
-    "wx_pre_destroy": ([C.c_void_p], C.c_int),
-    "wx_pre_channels": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
-    "wx_pre_apply": ([C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_void_p], C.c_int),
-    "wx_pre_set_transforms": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
-                               C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float)], C.c_int),
-    "wx_unxform_create": ([C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                           C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_unxform_destroy": ([C.c_void_p], C.c_int),
-    "wx_unxform_apply": ([C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p], C.c_int),
-    "wx_post_set_grid": ([C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int], C.c_int),
-    "wx_post_set_grid_sigma": ([C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                C.c_int, C.c_int, C.c_int], C.c_int),
-    "wx_post_set_stats": ([C.c_void_p] + [C.POINTER(C.c_float)] * 4, C.c_int),
-    "wx_post_add_tracer_fixer": ([C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int], C.c_int),
-    "wx_post_add_mass_fixer": ([C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_int),
-    "wx_post_add_water_fixer": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int], C.c_int),
-    "wx_post_add_energy_fixer_signed": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
-                                         C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int], C.c_int),
-    "wx_post_add_energy_fixer_updown": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float),
-                                         C.c_float, C.c_int], C.c_int),
-    "wx_post_add_energy_fixer": ([C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_float, C.c_int], C.c_int),
-    "wx_post_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_attach_postblock": ([C.c_void_p, C.c_void_p], C.c_int),
-    "wx_diag_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_diag_destroy": ([C.c_void_p], C.c_int),
-    "wx_diag_set_levels": ([C.c_void_p] + [C.POINTER(C.c_float)] * 4 + [C.c_int], C.c_int),
-    "wx_diag_set_pressure_levels": ([C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_float], C.c_int),
-    "wx_diag_apply": ([C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
-                       C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p], C.c_int),
-    "wx_wind_create": ([C.c_int, C.c_int] + [C.POINTER(C.c_float), C.c_int] * 4 + [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
-                        C.POINTER(C.c_void_p)], C.c_int),
-    "wx_wind_destroy": ([C.c_void_p], C.c_int),
-    "wx_wind_apply": ([C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                       C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_advect_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float,
-                          C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_advect_destroy": ([C.c_void_p], C.c_int),
-    "wx_advect_apply": ([C.c_void_p] + [C.c_void_p, C.c_int64] * 4 + [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                         C.POINTER(C.c_void_p), C.c_int, C.c_void_p], C.c_int),
-    "wx_hybrid_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float),
-                          C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_hybrid_destroy": ([C.c_void_p], C.c_int),
-    "wx_hybrid_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.c_int, C.c_int,
-                         C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
-    "wx_regrid_create": ([C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
-                          C.POINTER(C.c_void_p)], C.c_int),
-    "wx_regrid_destroy": ([C.c_void_p], C.c_int),
-    "wx_regrid_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int,
-                         C.POINTER(C.c_void_p), C.c_void_p], C.c_int),
-    "wx_tisr_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                        C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_tisr_destroy": ([C.c_void_p], C.c_int),
-    "wx_tisr_compute": ([C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
-    "wx_perturb_create": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_perturb_destroy": ([C.c_void_p], C.c_int),
-    "wx_perturb_batch": ([C.c_void_p, C.POINTER(C.c_int)], C.c_int),
-    "wx_perturb_apply": ([C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_float, C.c_void_p,
-                          C.c_int64, C.POINTER(C.c_float), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
-    "wx_spectrum_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_spectrum_destroy": ([C.c_void_p], C.c_int),
-    "wx_spectrum_apply": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int] + [C.c_void_p] * 7 + [C.c_void_p],
-                          C.c_int),
-    "wx_metrics_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_metrics_destroy": ([C.c_void_p], C.c_int),
-    "wx_metrics_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                          C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                          C.c_int, C.c_double, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_ensemble_create": ([C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_ensemble_destroy": ([C.c_void_p], C.c_int),
-    "wx_ensemble_apply": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
-                           C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_double, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p],
-                          C.c_int),
-    "wx_winattn_create": ([C.c_void_p, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_winattn_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_winattn_destroy": ([C.c_void_p], C.c_int),
-    "wx_band_comm_stream": ([C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_swin_create": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_swin_load": ([C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.c_int64], C.c_int),
-    "wx_swin_finalize": ([C.c_void_p], C.c_int),
-    "wx_swin_apply": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_swin_flops": ([C.c_void_p, C.POINTER(C.c_double)], C.c_int),
-    "wx_swin_destroy": ([C.c_void_p], C.c_int),
-    "wx_fuxi_create": ([C.c_void_p, C.c_int, C.POINTER(C.c_void_p)], C.c_int),
-    "wx_fuxi_load": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64], C.c_int),
-    "wx_fuxi_finalize": ([C.c_void_p], C.c_int),
-    "wx_fuxi_forward": ([C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
-    "wx_fuxi_debug_map": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_float), C.c_int64, C.POINTER(C.c_int64)], C.c_int),
-    "wx_fuxi_query": ([C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)], C.c_int),
-    "wx_fuxi_flops": ([C.c_void_p, C.POINTER(C.c_double)], C.c_int),
-    "wx_fuxi_destroy": ([C.c_void_p], C.c_int),
-    "wx_last_error": ([], C.c_char_p),
-    "wx_version": ([], C.c_char_p),
-}
-
-
-def exported_symbols():
-    return sorted(_PROTOTYPES)
-
-
-def load_library():
-    """dlopen libwxengine.so (torch must be imported first so its bundled HIP runtime is the one bound)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise WXEngineError(f"{LIB_PATH} not found: build it with `python miles-credit_amd/build.py` "
-                            "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-    import torch  # noqa: F401  (loads libamdhip64 with the SONAME our library needs)
-    lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (args, res) in _PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = res
-    _check_not_stale(lib)
-    _lib = lib
-    return lib
-
-
-def _check_not_stale(lib):
-    """The .so is git-ignored and ships prebuilt: make sure it was built from the sources lying next to it (build.py embeds
-    their hash in wx_version()).  WX_ALLOW_STALE=1 downgrades the error for bisecting with an old library."""
-    build_py = os.path.join(os.path.dirname(_HERE), "build.py")
-    if not os.path.isfile(build_py) or not os.path.isdir(os.path.join(os.path.dirname(_HERE), "csrc")):
-        return   # installed without sources: nothing to compare with
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_wx_build", build_py)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    want = mod.source_hash()
-    have = lib.wx_version().decode().rsplit("wxsrc:", 1)[-1]
-    if have != want and os.environ.get("WX_ALLOW_STALE") != "1":
-        raise WXEngineError(f"{LIB_PATH} was built from other sources (library wxsrc:{have}, sources wxsrc:{want}): "
-                            "rebuild with `python miles-credit_amd/build.py`")
-
-
-def _check(status: int):
-    if status != 0:
-        msg = load_library().wx_last_error().decode()
-        raise WXEngineError(f"wxengine error {status}: {msg}")
-
-
-class NativeHandle:
-    """One handle of the C ABI and the wx_*_destroy that frees it.  ctypes takes the object itself wherever a handle is an argument
-    (`_as_parameter_`); `out` is the out argument of the wx_*_create call that fills it."""
-
-    def __init__(self, destroy):
-        self._as_parameter_ = C.c_void_p()
-        self._destroy = destroy
-
-    @property
-    def out(self):
-        return C.byref(self._as_parameter_)
-
-    def close(self) -> None:
-        h, self._as_parameter_ = self._as_parameter_, C.c_void_p()
-        if h.value:
-            self._destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _gpu_tensor(t, ndim=None, contiguous=False, item_contiguous=False, device=None, dtype=None) -> bool:
-    """The test of a tensor that goes to the library as a raw pointer: a torch tensor on the GPU, float32 (or `dtype`) and, where
-    asked, of `ndim` dims, contiguous as a whole or per batch item, on GPU `device`.  The caller words the error."""
-    import torch
-    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == (dtype or torch.float32)
-            and (ndim is None or t.dim() == ndim) and (not contiguous or t.is_contiguous())
-            and (not item_contiguous or t[0].is_contiguous()) and (device is None or t.device.index == device))
-
-
-def _f32(a):
-    """float* to a numpy argument (made contiguous float32 if it is not; the pointer keeps the array alive); None stays None."""
-    return None if a is None else np.ascontiguousarray(a, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _i32(a):
-    return None if a is None else np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _stream_ptr(device=None):
-    """torch's current stream on `device` (None: the current device) as the ABI's stream argument."""
-    import torch
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _named_tensor_args(ts):
-    """A list of named tensors [B, n_levels, T, H, W] (checked by the caller: float32, one device, batch items contiguous), read
-    where they lie -> (source pointer array, batch strides in floats -- 0 when B = 1 --, levels, fresh contiguous outputs, their
-    pointer array)."""
-    import torch
-    n, B = len(ts), ts[0].shape[0]
-    outs = [torch.empty(t.shape, dtype=torch.float32, device=t.device) for t in ts]
-    return ((C.c_void_p * n)(*[t.data_ptr() for t in ts]), (C.c_int64 * n)(*[t.stride(0) if B > 1 else 0 for t in ts]),
-            (C.c_int32 * n)(*[t.shape[1] for t in ts]), outs, (C.c_void_p * n)(*[o.data_ptr() for o in outs]))
 
 
 def make_c_config(cfg: WXConfig, precision: str = "bf16", max_batch: int = 1) -> wx_config:
@@ -336,10 +58,7 @@ class WXEngine:
     """Owns one wx_handle.  Inputs/outputs are torch CUDA (HIP) tensors, float32, contiguous."""
 
     def __init__(self, cfg: WXConfig, precision: str = "bf16", device: int = 0):
-        import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the wxengine HIP path cannot run and there is no CPU fallback")
+        self.lib = require_gpu("the wxengine HIP path cannot run and there is no CPU fallback")
         self.cfg = cfg
         self.precision = precision
         self.device = device
@@ -553,10 +272,7 @@ class WXPostBlock:
     """Device-side PostBlock (credit/postblock/gen1.py) for pressure-level grids: ordered fixers applied in place."""
 
     def __init__(self, H: int, W: int, c_in: int, frames: int, c_out: int, device: int = 0):
-        import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the post block has no CPU fallback")
+        self.lib = require_gpu("the post block has no CPU fallback")
         self.shape = (H, W, c_in, frames, c_out)
         self._p = NativeHandle(self.lib.wx_post_destroy)
         _check(self.lib.wx_post_create(H, W, c_in, frames, c_out, device, self._p.out))
@@ -623,10 +339,7 @@ class WXDiag:
     pressure levels and MSLP of one set of named tensors in one launch.  The blocks of wxengine/diagnostics.py sit on top."""
 
     def __init__(self, H: int, W: int, n_levels: int, device: int = 0):
-        import torch
-        self.lib = load_library()
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the pressure-level products have no CPU fallback")
+        self.lib = require_gpu("the pressure-level products have no CPU fallback")
         self.H, self.W, self.L, self.device = int(H), int(W), int(n_levels), int(device)
         self._d = NativeHandle(self.lib.wx_diag_destroy)
         _check(self.lib.wx_diag_create(self.H, self.W, self.L, self.device, self._d.out))

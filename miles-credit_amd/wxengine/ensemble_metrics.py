@@ -29,7 +29,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _stream_ptr, load_library
+from .native import (HandleCache, PendingResult, WXEngineError, _check, _f32, _stream_ptr, batch_stride, copy_out, flatten_named,
+                     i32_array, i64_array, ptr_array, require_gpu)
 
 MAX_VARIABLES = 32      # kEnsMaxVars
 MAX_MEMBERS = 64        # kEnsMaxMembers
@@ -55,15 +56,7 @@ def check_arguments(n_members, alpha=1.0, maps=()):
 
 def flatten_state(state: dict, name: str) -> dict:
     """{var: tensor} of a flat or a nested {source: {var: tensor}} dict."""
-    flat = {}
-    for key, value in state.items():
-        if isinstance(value, dict):
-            flat.update(value)
-        else:
-            flat[key] = value
-    if not flat:
-        raise ValueError(f"EnsembleVerification: '{name}' is empty")
-    return flat
+    return flatten_named(state, name, "EnsembleVerification")
 
 
 def member_table(members, n_members: int, var_keys: Sequence[str]):
@@ -163,29 +156,19 @@ class EnsembleScores(dict):
         return self.maps["ens_std"][var_key] * (self.n_members + 1) / (self.n_members - 1)
 
 
-class PendingEnsembleScores:
-    """The scores of one `submit`: kernels and the copy of the plane table into a pinned buffer are enqueued, `result()` waits."""
+class PendingEnsembleScores(PendingResult):
+    """The scores of one `submit`: kernels and the copy of the plane table into a pinned buffer are enqueued, `result()` waits and is
+    the EnsembleScores."""
 
     def __init__(self, owner, pinned, event, shapes, maps, keep):
-        self._owner, self._pinned, self._event, self._shapes, self._maps, self._keep = owner, pinned, event, shapes, maps, keep
-        self._result = None
-
-    def done(self) -> bool:
-        return self._result is not None or self._event.query()
-
-    def result(self) -> EnsembleScores:
-        if self._result is None:
-            self._event.synchronize()
-            table = self._pinned.numpy()
+        def finish(table):
             planes, row = {}, 0
-            for k, (B, L, T, H, W) in self._shapes.items():
+            for k, (B, L, T, H, W) in shapes.items():
                 planes[k] = table[row:row + B * L * T].reshape(B, L, T, len(SUM_ORDER)).copy()
                 row += B * L * T
-            H, W = next(iter(self._shapes.values()))[3:]
-            scores = scores_from_planes(planes, self._owner.n_members, self._owner.alpha, H * W)
-            self._result = EnsembleScores(scores, planes, self._maps, self._owner.n_members)
-            self._keep = None
-        return self._result
+            H, W = next(iter(shapes.values()))[3:]
+            return EnsembleScores(scores_from_planes(planes, owner.n_members, owner.alpha, H * W), planes, maps, owner.n_members)
+        super().__init__(pinned, event, finish, keep)
 
 
 class EnsembleVerification:
@@ -197,24 +180,15 @@ class EnsembleVerification:
                 raise ValueError("latitude (degrees) is required when use_latitude_weights=True.")
             from .metrics import cos_lat_weights
             self.lat_weights = cos_lat_weights(latitude)
-        self._handles = {}
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the ensemble verification has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the ensemble verification has no CPU fallback")
+        self._handles = HandleCache(self.lib, "wx_ensemble")   # by (H, W, device)
 
     def _handle(self, H, W, dev):
-        if (H, W, dev) not in self._handles:
-            w = None
-            if self.lat_weights is not None:
-                if self.lat_weights.numel() != H:
-                    raise ValueError(f"EnsembleVerification: {self.lat_weights.numel()} latitudes but the fields have {H} rows")
-                w = np.ascontiguousarray(self.lat_weights.numpy(), dtype=np.float32)
-            h = NativeHandle(self.lib.wx_ensemble_destroy)
-            _check(self.lib.wx_ensemble_create(H, W, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float)), self.n_members, dev,
-                                               h.out))
-            self._handles[(H, W, dev)] = h
-        return self._handles[(H, W, dev)]
+        def args():
+            if self.lat_weights is not None and self.lat_weights.numel() != H:
+                raise ValueError(f"EnsembleVerification: {self.lat_weights.numel()} latitudes but the fields have {H} rows")
+            return H, W, _f32(None if self.lat_weights is None else self.lat_weights.numpy()), self.n_members, dev
+        return self._handles.get((H, W, dev), args)
 
     def _on_device(self, x, what, device=None):
         import torch
@@ -280,18 +254,14 @@ class EnsembleVerification:
                     ptrs = (C.c_void_p * (k * M))(*[p for row in table[sl] for p in row["ptrs"]])
                     map_ptrs = None
                     if self.maps:
-                        map_ptrs = (C.c_void_p * (k * len(MAP_ORDER)))(*[maps[name][key].data_ptr() if name in maps else None
-                                                                        for key in var_keys[sl] for name in MAP_ORDER])
+                        map_ptrs = ptr_array([maps[name][key] if name in maps else None for key in var_keys[sl] for name in MAP_ORDER])
                     _check(self.lib.wx_ensemble_apply(
-                        h, k, ptrs, (C.c_int64 * k)(*[row["batch_stride"] if B > 1 else 0 for row in table[sl]]),
-                        (C.c_void_p * k)(*[t.data_ptr() for t in truth[sl]]), (C.c_int64 * k)(*[t.stride(0) if B > 1 else 0 for t in truth[sl]]),
-                        (C.c_int32 * k)(*[row["shape"][1] for row in table[sl]]), (C.c_int32 * k)(*[row["shape"][2] for row in table[sl]]),
+                        h, k, ptrs, i64_array([row["batch_stride"] if B > 1 else 0 for row in table[sl]]),
+                        ptr_array(truth[sl]), i64_array([batch_stride(t, B) for t in truth[sl]]),
+                        i32_array([row["shape"][1] for row in table[sl]]), i32_array([row["shape"][2] for row in table[sl]]),
                         B, self.alpha, map_ptrs, C.c_void_p(planes[row0].data_ptr()), _stream_ptr(dev)))
                     row0 += sum(n_planes[sl])
-                pinned = torch.empty(planes.shape, dtype=torch.float64, pin_memory=True)
-                pinned.copy_(planes, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record(torch.cuda.current_stream(dev))
+                pinned, event = copy_out(planes, dev)
         return PendingEnsembleScores(self, pinned, event, shapes, maps, (members, truth, planes))
 
     def __call__(self, members, target: dict) -> EnsembleScores:

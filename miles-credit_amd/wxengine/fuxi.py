@@ -22,7 +22,8 @@ from typing import Dict, Optional, Tuple
 
 import numpy as np
 
-from .engine import PREC, NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, load_library
+from .engine import PREC
+from .native import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, require_gpu
 from .swin import TIMM_DERIVED_SUFFIXES, effective_logit_scale, relative_position_bias, timm_block_tensors
 from .synth import keyed_normal, power_iterate
 
@@ -332,11 +333,9 @@ class FuxiHIP:
 
     def __init__(self, precision: str = "bf16", device: Optional[int] = None, **model_conf):
         import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the FuXi engine has no CPU fallback")
+        self.lib = require_gpu("the FuXi engine has no CPU fallback")
         self.cfg = cfg = model_conf.pop("cfg", None) or FuxiConfig.from_model_conf(model_conf)
         cfg.check()
-        self.lib = load_library()
         self.precision = precision
         self.device = torch.cuda.current_device() if device is None else int(device)
         g = cfg.groups

@@ -21,7 +21,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, load_library
+from .native import (HandleCache, WXEngineError, _check, _f32, _named_tensor_args, _stream_ptr, batch_stride, check_named_tensor,
+                     copy_batch, load_library, require_gpu)
 from .transforms import _check_data_types
 
 MAX_VARIABLES = 32     # kHybridMaxVars
@@ -84,26 +85,12 @@ class _HybridInterpEngine:
         for what, x in (("source_a", self.source_a), ("source_b", self.source_b), ("dest_a", self.dest_a), ("dest_b", self.dest_b)):
             if not np.isfinite(x).all():
                 raise ValueError(f"{name}: {what} has a non-finite midpoint coefficient")
-        self._handles = {}   # (H, W, device) -> NativeHandle
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the hybrid-level interpolation has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the hybrid-level interpolation has no CPU fallback", load=load_library)
+        self._handles = HandleCache(self.lib, "wx_hybrid")   # by (H, W, device)
 
     def _handle(self, H, W, dev):
-        if (H, W, dev) not in self._handles:
-            h = NativeHandle(self.lib.wx_hybrid_destroy)
-            _check(self.lib.wx_hybrid_create(H, W, self.source_a.size, _f32(self.source_a), _f32(self.source_b), self.dest_a.size,
-                                             _f32(self.dest_a), _f32(self.dest_b), dev, h.out))
-            self._handles[(H, W, dev)] = h
-        return self._handles[(H, W, dev)]
-
-    @staticmethod
-    def _check_tensor(key, t):
-        if not _gpu_tensor(t, ndim=5):
-            raise WXEngineError(f"{key} must be a float32 [B, n_levels, n_time, H, W] tensor on the GPU")
-        if not _gpu_tensor(t, item_contiguous=True):
-            raise WXEngineError(f"{key}: a batch item must be contiguous [n_levels, n_time, H, W] memory")
+        return self._handles.get((H, W, dev), lambda: (H, W, self.source_a.size, _f32(self.source_a), _f32(self.source_b), self.dest_a.size,
+                                                       _f32(self.dest_a), _f32(self.dest_b), dev))
 
     def interp_nested(self, nested: dict) -> None:
         """hybrid_interp.py:108-161: every configured variable present in `nested` ({source: {var_key: tensor}}) onto the destination
@@ -113,32 +100,21 @@ class _HybridInterpEngine:
         if not present:
             return
         sp = nested[self.surface_pressure_var.split("/")[0]][self.surface_pressure_var]
-        self._check_tensor(self.surface_pressure_var, sp)
+        check_named_tensor(self.surface_pressure_var, sp)
         B, _, T, H, W = sp.shape
         if sp.shape[1] != 1:
             raise WXEngineError(f"{self.surface_pressure_var}: shape {tuple(sp.shape)}; the surface pressure is [B, 1, n_time, H, W]")
         ts = [nested[v.split("/")[0]][v] for v in present]
-        Ls, Ld = self.source_a.size, self.dest_a.size
         for key, t in zip(present, ts):
-            if hasattr(t, "shape") and len(t.shape) > 1 and t.shape[1] != Ls:
+            if hasattr(t, "shape") and len(t.shape) > 1 and t.shape[1] != self.source_a.size:
                 raise ValueError(f"HybridLevelInterp: {key!r} has {t.shape[1]} levels but the source "
-                                 f"coefficients define {Ls} midpoint levels.")
-            self._check_tensor(key, t)
-            if t.device != sp.device:
-                raise WXEngineError(f"{key} is on {t.device}, {self.surface_pressure_var} on {sp.device}: all tensors of one call live on one device")
-            if tuple(t.shape) != (B, Ls, T, H, W):
-                raise WXEngineError(f"{key}: shape {tuple(t.shape)} does not match {self.surface_pressure_var}: {tuple(sp.shape)} "
-                                    f"(batch, n_time and H x W must agree)")
+                                 f"coefficients define {self.source_a.size} midpoint levels.")
+            check_named_tensor(key, t, like=(self.surface_pressure_var, sp))
         dev = sp.device.index
         h = self._handle(H, W, dev)
-        n = len(ts)
-        outs = [torch.empty((B, Ld, T, H, W), dtype=torch.float32, device=sp.device) for _ in ts]
-        src = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-        bs = (C.c_int64 * n)(*[t.stride(0) if B > 1 else 0 for t in ts])
-        dst = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+        src, bs, _, outs, dst = _named_tensor_args(ts, out_levels=self.dest_a.size)
         with torch.cuda.device(dev):
-            _check(self.lib.wx_hybrid_apply(h, n, src, bs, dst, B, T, C.c_void_p(sp.data_ptr()), sp.stride(0) if B > 1 else 0,
-                                            _stream_ptr(dev)))
+            _check(self.lib.wx_hybrid_apply(h, len(ts), src, bs, dst, B, T, C.c_void_p(sp.data_ptr()), batch_stride(sp, B), _stream_ptr(dev)))
         for key, o in zip(present, outs):
             nested[key.split("/")[0]][key] = o
 
@@ -168,10 +144,9 @@ class HybridLevelInterpPre:
         self.engine = _HybridInterpEngine(**engine_kwargs)
 
     def __call__(self, batch: dict) -> dict:
-        batch = dict(batch)      # new dicts down to the variable level of what is interpolated (credit/preblock/base.py:12-22): tensors are shared
+        batch = copy_batch(batch, self.data_types)
         for data_type in self.data_types:
             if data_type in batch:       # absent (no "target" at inference): skipped
-                batch[data_type] = {src: dict(variables) for src, variables in batch[data_type].items()}
                 self.engine.interp_nested(batch[data_type])
         return batch
 

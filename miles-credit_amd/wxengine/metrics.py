@@ -26,7 +26,8 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _stream_ptr, load_library
+from .native import (HandleCache, PendingResult, WXEngineError, _check, _f32, _stream_ptr, batch_stride, copy_out, flatten_named,
+                     i32_array, i64_array, load_library, ptr_array, require_gpu)
 
 logger = logging.getLogger(__name__)
 
@@ -48,15 +49,6 @@ def cos_lat_weights(latitude):
     lat = torch.tensor(np.asarray(latitude, dtype=np.float64).reshape(-1), dtype=torch.float32)
     weights = torch.cos(torch.deg2rad(lat))
     return weights / weights.mean()
-
-
-def _flatten_state(state: dict, name: str) -> dict:
-    flat = {}
-    for source_vars in state.values():
-        flat.update(source_vars)
-    if not flat:
-        raise ValueError(f"CombinedMetric: '{name}' is empty — check the per_step postblocks config.")
-    return flat
 
 
 def _same_climatology(a, b) -> bool:
@@ -116,21 +108,11 @@ class _Weighting:
         return weights
 
 
-class PendingScores:
-    """The scores of one `submit`: kernels and the copy into a pinned buffer are enqueued, `result()` waits for them."""
+class PendingScores(PendingResult):
+    """The scores of one `submit`: kernels and the copy into a pinned buffer are enqueued, `result()` waits for them and is the dict."""
 
     def __init__(self, owner: "CombinedMetric", pinned, event, var_keys):
-        self._owner, self._pinned, self._event, self._var_keys = owner, pinned, event, var_keys
-        self._result = None
-
-    def done(self) -> bool:
-        return self._result is not None or self._event.query()
-
-    def result(self) -> dict:
-        if self._result is None:
-            self._event.synchronize()
-            self._result = self._owner._combine(self._pinned.numpy(), self._var_keys)
-        return self._result
+        super().__init__(pinned, event, lambda scores: owner._combine(scores, var_keys))
 
 
 class CombinedMetric:
@@ -193,11 +175,9 @@ class CombinedMetric:
         self.var_keys = None
         self._combination_weights = None
         self.last_var_scores = {name: {} for name in self.metric_names}
-        self._handles = {}
         self._clim_on = {}
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the verification metrics have no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the verification metrics have no CPU fallback", load=load_library)
+        self._handles = HandleCache(self.lib, "wx_metrics")   # by (H, W, device)
 
     # ---- setup (base.py:263-310) ----------------------------------------------------------------------------------------------------
     def _resolve_var_keys(self, pred: dict, target: dict) -> list:
@@ -265,17 +245,12 @@ class CombinedMetric:
 
     # ---- the device call ------------------------------------------------------------------------------------------------------------
     def _handle(self, H, W, dev):
-        if (H, W, dev) not in self._handles:
-            w = None
-            if self.lat_weights is not None:
-                if self.lat_weights.numel() != H:
-                    raise ValueError(f"CombinedMetric: {self.lat_weights.numel()} latitudes but the fields have {H} rows; "
-                                     "latitude-sharded scoring (lat-band mode) is out of scope")
-                w = np.ascontiguousarray(self.lat_weights.numpy(), dtype=np.float32)
-            h = NativeHandle(self.lib.wx_metrics_destroy)
-            _check(self.lib.wx_metrics_create(H, W, None if w is None else w.ctypes.data_as(C.POINTER(C.c_float)), dev, h.out))
-            self._handles[(H, W, dev)] = h
-        return self._handles[(H, W, dev)]
+        def args():
+            if self.lat_weights is not None and self.lat_weights.numel() != H:
+                raise ValueError(f"CombinedMetric: {self.lat_weights.numel()} latitudes but the fields have {H} rows; "
+                                 "latitude-sharded scoring (lat-band mode) is out of scope")
+            return H, W, _f32(None if self.lat_weights is None else self.lat_weights.numpy()), dev
+        return self._handles.get((H, W, dev), args)
 
     def submit(self, full_data_dict: dict) -> PendingScores:
         import torch
@@ -285,8 +260,8 @@ class CombinedMetric:
             raise KeyError("CombinedMetric requires full_data_dict['y_target_processed'] — add to postblocks.per_step: "
                            "reconstruct_target: {type: reconstruct, args: {in_key: 'y', out_key: 'y_target_processed'}} "
                            "followed by a bridgescaler_transformer postblock with key: 'y_target_processed'.")
-        pred = _flatten_state(full_data_dict["y_processed"], "y_processed")
-        target = _flatten_state(full_data_dict["y_target_processed"], "y_target_processed")
+        pred = flatten_named(full_data_dict["y_processed"], "y_processed", "CombinedMetric")
+        target = flatten_named(full_data_dict["y_target_processed"], "y_target_processed", "CombinedMetric")
         if self.need_climatology:
             self._update_climatology(target)
         if self.var_keys is None:
@@ -329,18 +304,13 @@ class CombinedMetric:
             with torch.cuda.device(dev):
                 for v0 in range(0, n, MAX_VARIABLES):
                     sl = slice(v0, min(n, v0 + MAX_VARIABLES))
-                    k = sl.stop - sl.start
-                    ptr = lambda xs: (C.c_void_p * k)(*[x.data_ptr() for x in xs])      # noqa: E731
-                    i64 = lambda xs: (C.c_int64 * k)(*xs)                                # noqa: E731
-                    clim = (ptr([c[0] for c in cs[sl]]), i64([c[1] for c in cs[sl]]), i64([c[2] for c in cs[sl]])) if cs else (None, None, None)
-                    _check(self.lib.wx_metrics_apply(h, k, ptr(ps[sl]), i64([x.stride(0) if B > 1 else 0 for x in ps[sl]]), ptr(ts[sl]),
-                                                     i64([x.stride(0) if B > 1 else 0 for x in ts[sl]]), *clim,
-                                                     (C.c_int32 * k)(*[x.shape[1] for x in ps[sl]]), (C.c_int32 * k)(*[x.shape[2] for x in ps[sl]]),
+                    clim = ((ptr_array([c[0] for c in cs[sl]]), i64_array([c[1] for c in cs[sl]]), i64_array([c[2] for c in cs[sl]]))
+                            if cs else (None, None, None))
+                    _check(self.lib.wx_metrics_apply(h, sl.stop - sl.start, ptr_array(ps[sl]), i64_array([batch_stride(x, B) for x in ps[sl]]),
+                                                     ptr_array(ts[sl]), i64_array([batch_stride(x, B) for x in ts[sl]]), *clim,
+                                                     i32_array([x.shape[1] for x in ps[sl]]), i32_array([x.shape[2] for x in ps[sl]]),
                                                      B, self.eps, C.c_void_p(scores[v0].data_ptr()), _stream_ptr(dev)))
-                pinned = torch.empty((n, len(METRIC_ORDER)), dtype=torch.float32, pin_memory=True)
-                pinned.copy_(scores, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record(torch.cuda.current_stream(dev))
+                pinned, event = copy_out(scores, dev)
         return PendingScores(self, pinned, event, list(var_keys))
 
     def _combine(self, scores: np.ndarray, var_keys) -> dict:

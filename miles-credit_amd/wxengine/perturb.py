@@ -14,7 +14,7 @@ from typing import Optional
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _stream_ptr, load_library
+from .native import HandleCache, WXEngineError, _check, _f32, _stream_ptr, require_gpu
 from .noise import SLOT_PERTURB  # noqa: F401  (the generator's slot of these draws)
 
 KIND_WHITE, KIND_COLOUR = 0, 1
@@ -73,26 +73,17 @@ class _Noise:
     def __init__(self, amplitude, device=0):
         self._amp = _scalar_amplitude(amplitude)
         self.amplitude = amplitude
-        self._handles = {}
         self._open(device)
 
     def _open(self, device) -> None:
-        import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the perturbation noise has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the perturbation noise has no CPU fallback", device)
+        self._handles = HandleCache(self.lib, "wx_perturb")   # by (H, W, device)
 
     def _weights(self, H: int, W: int):
         return None
 
     def _handle(self, H: int, W: int, index: int):
-        key = (H, W, index)
-        if key not in self._handles:
-            h = NativeHandle(self.lib.wx_perturb_destroy)
-            _check(self.lib.wx_perturb_create(H, W, self.kind, _f32(self._weights(H, W)), index, h.out))
-            self._handles[key] = h
-        return self._handles[key]
+        return self._handles.get((H, W, index), lambda: (H, W, self.kind, _f32(self._weights(H, W)), index))
 
     def batch_planes(self, H: int, W: int, device: int = 0) -> int:
         """The number of planes the colour filter takes through its scratch at a time on this grid."""

@@ -20,7 +20,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _i32, _stream_ptr, load_library
+from .native import NativeHandle, WXEngineError, _check, _f32, _i32, _stream_ptr, require_gpu
 
 FIELD_TYPE_RANK = {"prognostic": 0, "static": 1, "dynamic_forcing": 2, "diagnostic": 3}
 
@@ -72,9 +72,7 @@ class DevicePreblock:
         current device (rank r of a replicas run works on cuda:r -- a block pinned to GPU 0 would launch on another device's
         stream there)."""
         import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the device preblock has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the device preblock has no CPU fallback")
         self.keys = ordered_keys(example_input)
         flat = {k: v for src in example_input.values() for k, v in src.items()}
         if device is None:

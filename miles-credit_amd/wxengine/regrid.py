@@ -20,7 +20,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _stream_ptr, load_library
+from .native import (HandleCache, WXEngineError, _check, _f32, _i32, _stream_ptr, copy_batch, i32_array, i64_array, load_library,
+                     ptr_array, require_gpu)
 from .transforms import _check_data_types
 
 logger = logging.getLogger(__name__)
@@ -116,22 +117,13 @@ class Regridder:
         self.dst_grid_type, self.dst_lat, self.dst_lon = grid_type, dst_lat, dst_lon
         self.dst_shape = dst_shape
         self.row_ptr, self.col, self.val = coalesce_weights(row, col, S, self.n_a, self.n_b)
-        self._handles = {}      # (device, spatial shape, kept flips) -> NativeHandle
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the regridding block has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the regridding block has no CPU fallback", load=load_library)
+        self._handles = HandleCache(self.lib, "wx_regrid")   # by (device, spatial shape, kept flips)
 
     def _handle(self, dev, spatial, flips):
-        key = (dev, spatial, flips)
-        if key not in self._handles:
-            col = np.ascontiguousarray(fold_flips(self.col, spatial, flips) if flips else self.col, dtype=np.int32)
-            h = NativeHandle(self.lib.wx_regrid_destroy)
-            _check(self.lib.wx_regrid_create(self.n_a, self.n_b, self.row_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
-                                             col.ctypes.data_as(C.POINTER(C.c_int32)), self.val.ctypes.data_as(C.POINTER(C.c_float)),
-                                             dev, h.out))
-            self._handles[key] = h
-        return self._handles[key]
+        return self._handles.get((dev, spatial, flips), lambda: (
+            self.n_a, self.n_b, self.row_ptr.ctypes.data_as(C.POINTER(C.c_int64)),
+            _i32(fold_flips(self.col, spatial, flips) if flips else self.col), _f32(self.val), dev))
 
     def _plan(self, key, x):
         """regrid.py:139-163 without the arithmetic: -> (handle key, batch, batch stride, planes per item, output shape)."""
@@ -187,15 +179,12 @@ class Regridder:
             h = self._handle(*hkey)
             for c0 in range(0, len(members), MAX_VARIABLES):
                 chunk = members[c0:c0 + MAX_VARIABLES]
-                n = len(chunk)
                 for i in chunk:
                     outs[i] = torch.empty(plans[i][4], dtype=torch.float32, device=named[i][1].device)
-                src = (C.c_void_p * n)(*[named[i][1].data_ptr() for i in chunk])
-                bs = (C.c_int64 * n)(*[plans[i][2] for i in chunk])
-                ppi = (C.c_int32 * n)(*[plans[i][3] for i in chunk])
-                dst = (C.c_void_p * n)(*[outs[i].data_ptr() for i in chunk])
                 with torch.cuda.device(hkey[0]):
-                    _check(self.lib.wx_regrid_apply(h, n, src, bs, ppi, batch, dst, _stream_ptr(hkey[0])))
+                    _check(self.lib.wx_regrid_apply(h, len(chunk), ptr_array([named[i][1] for i in chunk]), i64_array([plans[i][2] for i in chunk]),
+                                                    i32_array([plans[i][3] for i in chunk]), batch, ptr_array([outs[i] for i in chunk]),
+                                                    _stream_ptr(hkey[0])))
         return outs
 
     def _regrid(self, x):
@@ -203,9 +192,7 @@ class Regridder:
         return self._regrid_many([("the input", x)])[0]
 
     def __call__(self, batch: dict) -> dict:
-        # new dicts down to the variable level (credit/preblock/base.py:12-22): the caller's dict is not mutated, tensors are shared
-        batch = {dt: ({src: dict(vars_) if isinstance(vars_, dict) else vars_ for src, vars_ in srcs.items()} if isinstance(srcs, dict) else srcs)
-                 for dt, srcs in batch.items()}
+        batch = copy_batch(batch, self.data_types)
         for data_type in self.data_types:
             if data_type not in batch:
                 continue            # absent (no "target" at inference)

@@ -26,7 +26,8 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _stream_ptr, load_library
+from .native import NativeHandle, PendingResult, WXEngineError, _check, _f32, _stream_ptr, copy_out, require_gpu
+from .native import flatten_named as _flatten_named
 
 MAX_W = 4096            # kPerturbMaxN: the twiddle table lies in LDS
 PARTS = ("mean_psd_pred", "mean_psd_target", "mean_amp_pred", "mean_amp_target")     # the [P][Wh] blocks of a variable's table, then [P][2]
@@ -59,14 +60,7 @@ def check_wavenum(wavenum_init, W) -> int:
 
 def flatten_named(state: dict, name: str) -> dict:
     """{var: tensor} of a flat or a nested {source: {var: tensor}} dict, in sorted key order."""
-    flat = {}
-    for key, value in state.items():
-        if isinstance(value, dict):
-            flat.update(value)
-        else:
-            flat[key] = value
-    if not flat:
-        raise ValueError(f"ZonalSpectrum: '{name}' is empty")
+    flat = _flatten_named(state, name, "ZonalSpectrum")
     return {k: flat[k] for k in sorted(flat)}
 
 
@@ -107,32 +101,22 @@ def table_layout(planes: Dict[str, int], Wh: int):
     return offsets, at
 
 
-class PendingSpectra:
-    """The spectra of one `submit`: the kernels and the copy of the table into a pinned buffer are enqueued, `result()` waits."""
+class PendingSpectra(PendingResult):
+    """The spectra of one `submit`: the kernels and the copy of the table into a pinned buffer are enqueued, `result()` waits and is
+    {var: SpectrumResult} of named tensors, the SpectrumResult of a tensor pair."""
 
     def __init__(self, pinned, event, leads, Wh, wavenum_init, named, keep):
-        self._pinned, self._event, self._leads, self._Wh = pinned, event, leads, Wh
-        self._wavenum_init, self._named, self._keep = wavenum_init, named, keep
-        self._result = None
-
-    def done(self) -> bool:
-        return self._result is not None or self._event.query()
-
-    def result(self):
-        if self._result is None:
-            self._event.synchronize()
-            table = np.array(self._pinned.numpy(), dtype=np.float64)
-            Wh = self._Wh
-            planes = {k: int(np.prod(lead, dtype=np.int64)) for k, lead in self._leads.items()}
+        def finish(host):
+            table = np.array(host, dtype=np.float64)
+            planes = {k: int(np.prod(lead, dtype=np.int64)) for k, lead in leads.items()}
             offsets, _ = table_layout(planes, Wh)
             out = {}
-            for k, lead in self._leads.items():
+            for k, lead in leads.items():
                 P, o = planes[k], offsets[k]
                 out[k] = SpectrumResult(table[o:o + 4 * P * Wh].reshape(4, P, Wh), table[o + 4 * P * Wh:o + 4 * P * Wh + 2 * P].reshape(P, 2),
-                                        lead, self._wavenum_init)
-            self._result = out if self._named else out[None]
-            self._keep = None
-        return self._result
+                                        lead, wavenum_init)
+            return out if named else out[None]
+        super().__init__(pinned, event, finish, keep)
 
 
 class ZonalSpectrum:
@@ -148,11 +132,9 @@ class ZonalSpectrum:
 
     def _open(self, device) -> None:
         import torch
+        self.lib = require_gpu("the zonal spectrum has no CPU fallback", device)
         dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if dev.type != "cuda" or not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the zonal spectrum has no CPU fallback")
         self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self.lib = load_library()
         self._h = NativeHandle(self.lib.wx_spectrum_destroy)
         _check(self.lib.wx_spectrum_create(self.H, self.W, _f32(self.lat_weights), self.device.index, self._h.out))
 
@@ -229,10 +211,7 @@ class ZonalSpectrum:
                     block = 8 * P * Wh
                     self._apply(P, a[1], a[3], b[1], b[3], k_init, mean_psd_a=o, mean_psd_b=o + block, mean_amp_a=o + 2 * block,
                                 mean_amp_b=o + 3 * block, scores=o + 4 * block)
-                pinned = torch.empty((total,), dtype=torch.float64, pin_memory=True)
-                pinned.copy_(table, non_blocking=True)
-                event = torch.cuda.Event()
-                event.record(torch.cuda.current_stream(self.device.index))
+                pinned, event = copy_out(table, self.device.index)
         return PendingSpectra(pinned, event, leads, Wh, k_init, named, (fields, table))
 
     def compare(self, pred, target, wavenum_init: int = 20):

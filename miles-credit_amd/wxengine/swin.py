@@ -17,7 +17,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import PREC, NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, load_library
+from .engine import PREC
+from .native import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _stream_ptr, require_gpu
 
 KIND = {"block": 0, "dilated": 1, "shifted": 3}
 
@@ -69,9 +70,7 @@ class WindowAttention:
         """bias: [heads, N, N] or [1, N, N] or None; logit_scale: [heads] (already exponentiated) selects cosine attention;
         mask_axes: 1 = the latitude-only seam mask of swin.py:411-427, 3 = both axes (timm's SwinTransformerV2Block)."""
         import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: window attention has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("window attention has no CPU fallback")
         ws = (int(window), int(window)) if np.isscalar(window) else (int(window[0]), int(window[1]))
         self.feat, self.heads, self.head_dim, self.window, self.shift = tuple(feat), heads, head_dim, ws, (int(shift[0]), int(shift[1]))
         self.precision = precision
@@ -154,9 +153,7 @@ class SwinStage:
         if variant not in ("cr", "timm"):
             raise ValueError("SwinStage: variant must be 'cr' or 'timm'")
         self.variant = variant
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the Swin stage has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the Swin stage has no CPU fallback")
         ws = (int(window_size), int(window_size)) if np.isscalar(window_size) else (int(window_size[0]), int(window_size[1]))
         # swin.py:405-409 `_calc_window_shift`: a window is clipped to the map, and a clipped axis is not shifted
         self.window = tuple(f if f <= w else w for f, w in zip(feat_size, ws))

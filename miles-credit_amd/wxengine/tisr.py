@@ -15,7 +15,7 @@ from typing import Iterable, Iterator, Optional, Sequence
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _stream_ptr, load_library
+from .native import NativeHandle, WXEngineError, _check, _f32, _stream_ptr, require_gpu
 
 MAX_STEPS = 2 ** 22 - 1      # kTisrTableEntries - 1
 
@@ -115,10 +115,7 @@ class TISRForcing:
         self._handle = self._create_handle()
 
     def _create_handle(self):
-        import torch
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the TISR forcing has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the TISR forcing has no CPU fallback", self.device)
         h = NativeHandle(self.lib.wx_tisr_destroy)
         _check(self.lib.wx_tisr_create(self.ny, self.nx, _f32(self.latitude), _f32(self.longitude), self.tsi_times.size,
                                        _f32(self.tsi_times), _f32(self.tsi_values), self.device.index, h.out))

@@ -30,7 +30,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _i32, _named_tensor_args, _stream_ptr, load_library
+from .native import HandleCache, _check, _f32, _i32, _named_tensor_args, _stream_ptr, check_named_tensor, require_gpu
 from .preblock import channel_stats
 
 MAX_FILL_RULES = 8          # WX_MAX_FILL_RULES
@@ -204,11 +204,8 @@ class _Unxform:
     """One wx_unxform handle per (variables, shapes, device) signature, made on first use."""
 
     def __init__(self):
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the device transforms have no CPU fallback")
-        self.lib = load_library()
-        self._handles = {}   # signature -> NativeHandle
+        self.lib = require_gpu("the device transforms have no CPU fallback")
+        self._handles = HandleCache(self.lib, "wx_unxform")   # by signature
 
     def run(self, nested: Dict[str, Dict], plan):
         """plan: [(key, kind, eps, log_eps, mean or None, std or None)]; rebinds nested[source][key] to fresh tensors."""
@@ -220,29 +217,22 @@ class _Unxform:
         ts = [nested[p[0].split("/")[0]][p[0]] for p in plan]
         t0 = ts[0]
         for p, t in zip(plan, ts):
-            if not _gpu_tensor(t, ndim=5):
-                raise WXEngineError(f"{p[0]} must be a float32 [B, n_levels, n_time, H, W] tensor on the GPU")
-            if t.device != t0.device or (t.shape[0], *t.shape[2:]) != (t0.shape[0], *t0.shape[2:]):
-                raise WXEngineError(f"{p[0]}: shape {tuple(t.shape)} on {t.device} does not match {tuple(t0.shape)} on {t0.device}")
-            if not _gpu_tensor(t, item_contiguous=True):
-                raise WXEngineError(f"{p[0]}: a batch item must be contiguous [n_levels, n_time, H, W] memory")
+            check_named_tensor(p[0], t, like=(plan[0][0], t0))
         B, _, nT, H, W = t0.shape
         dev = t0.device.index
-        sig = (tuple((p[0], t.shape[1]) for p, t in zip(plan, ts)), H, W, dev)
-        if sig not in self._handles:
-            lv = [t.shape[1] for t in ts]
+        lv = [t.shape[1] for t in ts]
+
+        def args():
             has = [p[4] is not None for p in plan]
             # per-(variable, level) statistics, keyed like the input side's: by the variable's short name
             named = [(p[0].split("/")[-1], p) for p in plan if p[4] is not None]
             mean, std = channel_stats([p[0] for p in plan], lv, {n: p[4] for n, p in named}, {n: p[5] for n, p in named})
-            h = NativeHandle(self.lib.wx_unxform_destroy)
-            _check(self.lib.wx_unxform_create(len(plan), _i32(lv), H, W, _i32([p[1] for p in plan]), _f32([p[2] for p in plan]),
-                                              _f32([p[3] for p in plan]), _i32(has), _f32(mean) if any(has) else None,
-                                              _f32(std) if any(has) else None, dev, h.out))
-            self._handles[sig] = h
+            return (len(plan), _i32(lv), H, W, _i32([p[1] for p in plan]), _f32([p[2] for p in plan]), _f32([p[3] for p in plan]), _i32(has),
+                    _f32(mean) if any(has) else None, _f32(std) if any(has) else None, dev)
+        h = self._handles.get((tuple((p[0], n) for p, n in zip(plan, lv)), H, W, dev), args)
         src, bs, _, outs, dst = _named_tensor_args(ts)
         with torch.cuda.device(dev):
-            _check(self.lib.wx_unxform_apply(self._handles[sig], src, bs, dst, B, nT, _stream_ptr(dev)))
+            _check(self.lib.wx_unxform_apply(h, src, bs, dst, B, nT, _stream_ptr(dev)))
         for p, o in zip(plan, outs):
             nested[p[0].split("/")[0]][p[0]] = o
 

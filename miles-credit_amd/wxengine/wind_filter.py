@@ -24,7 +24,8 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 
 from .conservation import _pred, _set_pred
-from .engine import NativeHandle, WXEngineError, _check, _f32, _gpu_tensor, _i32, _named_tensor_args, _stream_ptr, load_library
+from .native import (HandleCache, WXEngineError, _check, _f32, _i32, _named_tensor_args, _stream_ptr, batch_stride, check_named_tensor,
+                     require_gpu)
 
 logger = logging.getLogger(__name__)
 
@@ -112,46 +113,26 @@ class WindArtifactFilter:
         self.kernels = filter_kernels(smooth_sigma, smooth_sigma_zonal, smooth_sigma_meridional, falloff_sigma)
         self._levels = np.array(sorted(self.target_levels), np.int32)
         self._warned = set()
-        self._handles = {}   # (H, W, device) -> NativeHandle
-        import torch
-        if not torch.cuda.is_available():
-            raise WXEngineError("no GPU visible: the wind artifact filter has no CPU fallback")
-        self.lib = load_library()
+        self.lib = require_gpu("the wind artifact filter has no CPU fallback")
+        self._handles = HandleCache(self.lib, "wx_wind")   # by (H, W, device)
 
     def _handle(self, H, W, dev):
-        if (H, W, dev) not in self._handles:
-            args = []
-            for n in ("smooth_lat", "smooth_lon", "falloff_lat", "falloff_lon"):
-                args += [_f32(self.kernels[n]), self.kernels[n].size]
-            h = NativeHandle(self.lib.wx_wind_destroy)
-            _check(self.lib.wx_wind_create(H, W, *args, self.dilation_meridional, self.dilation_zonal, self.speed_threshold,
-                                           int(self.preserve_amplitude), dev, h.out))
-            self._handles[(H, W, dev)] = h
-        return self._handles[(H, W, dev)]
-
-    @staticmethod
-    def _check_tensor(key, t):
-        if not (_gpu_tensor(t, ndim=5) and t.shape[2] == 1):
-            raise WXEngineError(f"{key} must be a float32 [B, n_levels, 1, H, W] tensor on the GPU")
-        if not _gpu_tensor(t, item_contiguous=True):
-            raise WXEngineError(f"{key}: a batch item must be contiguous [n_levels, 1, H, W] memory")
+        def args():
+            weights = [x for n in ("smooth_lat", "smooth_lon", "falloff_lat", "falloff_lon") for x in (_f32(self.kernels[n]), self.kernels[n].size)]
+            return (H, W, *weights, self.dilation_meridional, self.dilation_zonal, self.speed_threshold, int(self.preserve_amplitude), dev)
+        return self._handles.get((H, W, dev), args)
 
     def __call__(self, batch_dict: dict) -> dict:
         import torch
         u, v = _pred(batch_dict, self.u_var), _pred(batch_dict, self.v_var)
-        self._check_tensor(self.u_var, u)
-        self._check_tensor(self.v_var, v)
+        check_named_tensor(self.u_var, u, one_time=True)
+        check_named_tensor(self.v_var, v, like=(self.u_var, u), one_time=True)
         B, Lu, _, H, W = u.shape
         if self.mask_level >= Lu or self.mask_level >= v.shape[1]:
             raise WXEngineError(f"mask_level {self.mask_level} is beyond the {min(Lu, v.shape[1])} levels of {self.u_var} / {self.v_var}")
-        if v.device != u.device or (v.shape[0], *v.shape[3:]) != (B, H, W):
-            raise WXEngineError(f"{self.v_var}: shape {tuple(v.shape)} on {v.device} does not match {self.u_var}: {tuple(u.shape)} on {u.device}")
         ts = [_pred(batch_dict, k) for k in self.target_vars]
         for key, t in zip(self.target_vars, ts):
-            self._check_tensor(key, t)
-            if t.device != u.device or (t.shape[0], *t.shape[3:]) != (B, H, W):
-                raise WXEngineError(f"{key}: shape {tuple(t.shape)} on {t.device} does not match {self.u_var}: {tuple(u.shape)} on {u.device} "
-                                    "(batch and H x W must agree)")
+            check_named_tensor(key, t, like=(self.u_var, u), one_time=True)
             if t.shape[1] > MAX_LEVELS:
                 raise WXEngineError(f"{key}: {t.shape[1]} levels, the kernel takes at most {MAX_LEVELS}")
             out_of_range = [lev for lev in sorted(self.target_levels) if lev >= t.shape[1]]
@@ -165,8 +146,8 @@ class WindArtifactFilter:
         mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=u.device) if self.return_mask else None
         um, vm = u[:, self.mask_level], v[:, self.mask_level]
         with torch.cuda.device(dev):
-            _check(self.lib.wx_wind_apply(h, C.c_void_p(um.data_ptr()), u.stride(0) if B > 1 else 0, C.c_void_p(vm.data_ptr()),
-                                          v.stride(0) if B > 1 else 0, len(ts), src, bs, nl, dst, _i32(self._levels), int(self._levels.size), B,
+            _check(self.lib.wx_wind_apply(h, C.c_void_p(um.data_ptr()), batch_stride(u, B), C.c_void_p(vm.data_ptr()),
+                                          batch_stride(v, B), len(ts), src, bs, nl, dst, _i32(self._levels), int(self._levels.size), B,
                                           C.c_void_p(mask.data_ptr()) if mask is not None else None, _stream_ptr(dev)))
         for key, o in zip(self.target_vars, outs):
             _set_pred(batch_dict, key, o)

@@ -36,6 +36,65 @@ def test_library_exports_every_symbol_in_header(lib):
     assert b"gfx950" in lib.wx_version()
 
 
+def _header_declarations():
+    """{name: [argument text]} of every `int | const char* wx_name(args);` of include/wxengine.h, comments stripped."""
+    hdr = open(os.path.join(ROOT, "include", "wxengine.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    decls = {}
+    for name, args in re.findall(r"\b(?:int|const\s+char\s*\*)\s*(wx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr):
+        args = " ".join(args.split())
+        decls[name] = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
+    return decls
+
+
+_SCALARS = {"int": (ctypes.c_int, ctypes.c_int32), "int32_t": (ctypes.c_int, ctypes.c_int32), "int64_t": (ctypes.c_int64,),
+            "uint64_t": (ctypes.c_uint64,), "float": (ctypes.c_float,), "double": (ctypes.c_double,)}
+
+
+def test_prototypes_match_the_header_argument_by_argument(lib):
+    """engine._PROTOTYPES against include/wxengine.h by position: a pointer (anything with * or [, or a handle typedef) must be a
+    ctypes pointer class, a scalar must be the ctypes type of exactly its C type -- a c_int where the header says int64_t would
+    corrupt the argument silently."""
+    from wxengine.native import _PROTOTYPES
+    decls = _header_declarations()
+    assert len(decls) == 111 and set(decls) == set(_PROTOTYPES)
+    for name, args in sorted(decls.items()):
+        ctypes_args = _PROTOTYPES[name][0]
+        assert len(args) == len(ctypes_args), f"{name}: {len(args)} arguments in the header, {len(ctypes_args)} in _PROTOTYPES"
+        for i, (arg, ct) in enumerate(zip(args, ctypes_args)):
+            words = re.sub(r"\bconst\b", " ", arg).split()
+            if "*" in arg or "[" in arg or re.fullmatch(r"wx_\w*handle|wx_band_plan", words[0]):
+                is_pointer = ct in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ct, ctypes._Pointer)
+                assert is_pointer, f"{name} argument {i} `{arg}` is a pointer, _PROTOTYPES has {ct.__name__}"
+            else:
+                assert words[0] in _SCALARS, f"{name} argument {i} `{arg}`: unknown scalar type"
+                assert ct in _SCALARS[words[0]], f"{name} argument {i} `{arg}`: _PROTOTYPES has {ct.__name__}"
+
+
+WX_ERR_INVALID, WX_ERR_STATE = -1, -2
+NULL_HANDLE_IS_STATE = {"wx_fuxi_finalize", "wx_fuxi_forward", "wx_fuxi_query", "wx_swin_apply", "wx_swin_finalize", "wx_winattn_apply"}
+
+
+def test_every_function_takes_a_null_handle_as_an_error(lib):
+    """Every exported function but the creates, wx_last_error, wx_version and wx_band_rccl_unique_id, called with None for every
+    pointer and 0 for every scalar: a destroy of nothing is WX_OK, everything else an error status with its reason -- WX_ERR_STATE
+    for the six Swin / FuXi / window-attention calls that say so, WX_ERR_INVALID for the rest -- and never a crash."""
+    from wxengine.native import _PROTOTYPES
+    skipped = {"wx_last_error", "wx_version", "wx_band_rccl_unique_id"}
+    names = [n for n in E.exported_symbols() if not n.endswith("_create") and n not in skipped]
+    destroys = [n for n in names if n.endswith("_destroy")]
+    assert len(destroys) == 18
+    got = {}
+    for name in names:
+        args = [None if (ct in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(ct, ctypes._Pointer)) else 0 for ct in _PROTOTYPES[name][0]]
+        got[name] = getattr(lib, name)(*args)
+        if name not in destroys:
+            assert got[name] < 0 and lib.wx_last_error(), name
+    want = {n: 0 if n in destroys else WX_ERR_STATE if n in NULL_HANDLE_IS_STATE else WX_ERR_INVALID for n in names}
+    assert NULL_HANDLE_IS_STATE <= set(names) and got == want, {n: (got[n], want[n]) for n in names if got[n] != want[n]}
+
+
 def test_config_struct_matches_header_layout():
     # 4-byte ints only, so the ctypes mirror and the C struct agree when the field count does
     hdr = open(os.path.join(ROOT, "include", "wxengine.h")).read()
