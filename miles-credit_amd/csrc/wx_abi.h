@@ -757,6 +757,42 @@ int wx_fuxi_flops(wx_fuxi_handle w, double* flops) {
 }
 int wx_fuxi_destroy(wx_fuxi_handle w) { return guarded([&] { delete w; }); }
 
+// ---- spherical harmonic transforms (scalar pair, vector analysis, spectra; csrc/wx_sht.h, declared in include/wxengine_sht.h) --------
+struct wx_sht : Handle<wx::Sht> {};
+int wx_sht_create(int nlat, int nlon, int lmax, int mmax, const double* theta_host, const double* w_host, int csphase, const char* norm,
+                  int device, wx_sht_handle* out) {
+  return create("wx_sht_create", out, theta_host && w_host, device, [&] { return wx::sht_check_create(nlat, nlon, lmax, mmax, theta_host, w_host, norm); },
+                [&] { return new wx::Sht(nlat, nlon, lmax, mmax, theta_host, w_host, csphase, device); });
+}
+int wx_sht_destroy(wx_sht_handle h) { return guarded([&] { delete h; }); }
+int wx_sht_analysis(wx_sht_handle h, int n_planes, const void* x_dev, int64_t x_stride, int dtype, double* c_dev, void* stream) {
+  return use_remapped(h, "wx_sht_analysis: null sht handle", [&] { h->impl->analysis(n_planes, x_dev, x_stride, dtype, c_dev, (hipStream_t)stream); });
+}
+int wx_sht_synthesis(wx_sht_handle h, int n_planes, const double* c_dev, void* x_dev, int dtype, void* stream) {
+  return use_remapped(h, "wx_sht_synthesis: null sht handle", [&] { h->impl->synthesis(n_planes, c_dev, x_dev, dtype, (hipStream_t)stream); });
+}
+int wx_sht_vector_analysis(wx_sht_handle h, int n_planes, const void* u_dev, int64_t u_stride, const void* v_dev, int64_t v_stride, int dtype,
+                           double* s_dev, double* t_dev, void* stream) {
+  return use_remapped(h, "wx_sht_vector_analysis: null sht handle", [&] {
+    h->impl->vector_analysis(n_planes, u_dev, u_stride, v_dev, v_stride, dtype, s_dev, t_dev, (hipStream_t)stream);
+  });
+}
+int wx_sht_spectra(wx_sht_handle h, int n_planes, const double* c_dev, double* zonal_dev, double* total_dev, void* stream) {
+  return use_remapped(h, "wx_sht_spectra: null sht handle", [&] { h->impl->spectra(n_planes, c_dev, zonal_dev, total_dev, (hipStream_t)stream); });
+}
+int wx_sht_table(int nlat, int lmax, int mmax, const double* theta_host, const double* w_host, int csphase, int table, int m,
+                 double* out_host, int* folds_out) {
+  return guarded([&] {
+    if (!theta_host || !out_host || (folds_out && !w_host)) throw wx::ConfigError("wx_sht_table: null argument");
+    const std::string why = wx::sht_check_table(nlat, lmax, mmax, theta_host, table, m);
+    if (!why.empty()) throw wx::ConfigError("wx_sht_table: " + why);
+    std::vector<double> col;
+    wx::sht_table_column(table, m, lmax, theta_host, nlat, csphase, col);
+    std::memcpy(out_host, col.data(), col.size() * sizeof(double));
+    if (folds_out) *folds_out = wx::sht_folds(nlat, theta_host, w_host) ? 1 : 0;
+  });
+}
+
 const char* wx_last_error(void) { return wx::g_last_error.c_str(); }
 #ifndef WX_SOURCE_HASH
 #define WX_SOURCE_HASH "unhashed"

@@ -7,6 +7,7 @@
 //   wx_rccl.h     RCCL bound at run time for the lat-band transport
 //   wx_abi.h      the extern "C" wrappers of include/wxengine.h
 #include "../../include/wxengine.h"
+#include "../../include/wxengine_sht.h"
 
 #include <algorithm>
 #include <climits>
@@ -46,6 +47,7 @@
 #include "wx_tisr.h"
 #include "wx_perturb.h"
 #include "wx_spectrum.h"
+#include "wx_sht.h"
 #include "wx_metrics.h"
 #include "wx_ensemble.h"
 #include "wx_noise.h"

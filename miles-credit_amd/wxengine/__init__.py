@@ -13,6 +13,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   metrics           the gen-2 verification metrics, eight scores per variable from one reduction (CombinedMetric, PendingScores, exported here)
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   spectrum          zonal power spectra, PSD / latitude-mean spectra / spectral scores from a folded fp64 DFT (ZonalSpectrum, PendingSpectra, SpectrumResult, exported here)
+  sht               spherical harmonic transforms, scalar pair / vector analysis / spectra by zonal and total wavenumber (SphericalHarmonics, RealSHT, InverseRealSHT, grid_nodes, zonal_spectrum, average_zonal_spectrum, div_rot_spectrum, average_div_rot_spectrum, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
 There is no CPU fallback: without the HIP library or a GPU, construction raises.
 """
@@ -46,4 +47,8 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
     if name in ("ZonalSpectrum", "PendingSpectra", "SpectrumResult"):
         from . import spectrum
         return getattr(spectrum, name)
+    if name in ("SphericalHarmonics", "RealSHT", "InverseRealSHT", "grid_nodes", "zonal_spectrum", "average_zonal_spectrum", "div_rot_spectrum",
+                "average_div_rot_spectrum", "cached_transform", "clear_cache"):
+        from . import sht
+        return getattr(sht, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

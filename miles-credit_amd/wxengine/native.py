@@ -1,5 +1,5 @@
-"""The binding layer of libwxengine.so (C ABI in include/wxengine.h): the ctypes prototypes and the loader, the owner of a native
-handle, and what every device product needs to hand torch tensors to the library -- the GPU guard, the per-geometry handle cache, the
+"""The binding layer of libwxengine.so (C ABI in include/wxengine.h and its extension include/wxengine_sht.h): the ctypes prototypes
+and the loader, the owner of a native handle, and what every device product needs to hand torch tensors to the library -- the GPU guard, the per-geometry handle cache, the
 named-tensor test and pointer tables, and the pending result of an asynchronous call.
 
 PyTorch is used only as the owner of device memory and streams: tensors are handed to the library as raw device pointers.  There is
@@ -187,8 +187,23 @@ _PROTOTYPES = {
     "wx_version": ([], C.c_char_p),
 }
 
+# include/wxengine_sht.h: the extension header of the same library, bound by load_library() as well
+_EXTENSION_PROTOTYPES = {
+    "wx_sht_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_int,
+                       C.POINTER(C.c_void_p)], C.c_int),
+    "wx_sht_destroy": ([C.c_void_p], C.c_int),
+    "wx_sht_analysis": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p], C.c_int),
+    "wx_sht_synthesis": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "wx_sht_vector_analysis": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_void_p], C.c_int),
+    "wx_sht_spectra": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int),
+    "wx_sht_table": ([C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
+                      C.POINTER(C.c_double), C.POINTER(C.c_int)], C.c_int),
+}
+
 
 def exported_symbols():
+    """The functions of include/wxengine.h (the extension header's are _EXTENSION_PROTOTYPES)."""
     return sorted(_PROTOTYPES)
 
 
@@ -202,7 +217,7 @@ def load_library():
                             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     import torch  # noqa: F401  (loads libamdhip64 with the SONAME our library needs)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (args, res) in _PROTOTYPES.items():
+    for name, (args, res) in list(_PROTOTYPES.items()) + list(_EXTENSION_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
@@ -270,6 +285,10 @@ def _gpu_tensor(t, ndim=None, contiguous=False, item_contiguous=False, device=No
 def _f32(a):
     """float* to a numpy argument (made contiguous float32 if it is not; the pointer keeps the array alive); None stays None."""
     return None if a is None else np.ascontiguousarray(a, dtype=np.float32).ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _f64(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _i32(a):
