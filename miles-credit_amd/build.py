@@ -17,7 +17,8 @@ MARK = b"wxsrc:"
 
 def deps():
     return SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
-        os.path.join(os.path.dirname(HERE), "include", "wxengine.h"), os.path.join(os.path.dirname(HERE), "include", "wxengine_sht.h")]
+        os.path.join(os.path.dirname(HERE), "include", "wxengine.h"), os.path.join(os.path.dirname(HERE), "include", "wxengine_sht.h"),
+        os.path.join(os.path.dirname(HERE), "include", "wxengine_polefilter.h")]
 
 
 def source_hash() -> str:

@@ -793,6 +793,70 @@ int wx_sht_table(int nlat, int lmax, int mmax, const double* theta_host, const d
   });
 }
 
+// ---- inverse vector transform, diffusion and pole filter (csrc/wx_polefilter.h, declared in include/wxengine_polefilter.h) ----------
+int wx_sht_vector_synthesis(wx_sht_handle h, int n_planes, const double* s_dev, const double* t_dev, void* u_dev, void* v_dev, int dtype,
+                            void* stream) {
+  return use_remapped(h, "wx_sht_vector_synthesis: null sht handle", [&] {
+    h->impl->vector_synthesis(n_planes, s_dev, t_dev, nullptr, u_dev, v_dev, dtype, (hipStream_t)stream);
+  });
+}
+// the transform first: the filter, which refers to it, is destroyed before it
+struct wx_polefilter {
+  wx_sht sht;
+  std::unique_ptr<wx::PoleFilter> impl;
+};
+int wx_polefilter_create(int nlat, int nlon, int lmax, int mmax, const double* theta_host, const double* w_host, double radius, int indpol,
+                         int cutoff_index, const float* sig_host, int device, wx_polefilter_handle* out) {
+  return guarded([&] {
+    if (!out || !theta_host || !w_host || !sig_host) throw wx::ConfigError("wx_polefilter_create: null argument");
+    std::string why = wx::sht_check_create(nlat, nlon, lmax, mmax, theta_host, w_host, "ortho");
+    if (why.empty()) why = wx::polefilter_check_create(nlat, nlon, radius, indpol, cutoff_index, sig_host);
+    if (!why.empty()) throw wx::ConfigError("wx_polefilter_create: " + why);
+    need_device(device, "wx_polefilter_create");
+    std::unique_ptr<wx_polefilter> h(new wx_polefilter);
+    h->sht.impl.reset(new wx::Sht(nlat, nlon, lmax, mmax, theta_host, w_host, 0, device));
+    h->impl.reset(new wx::PoleFilter(*h->sht.impl, radius, indpol, cutoff_index, sig_host, device));
+    *out = h.release();
+  });
+}
+int wx_polefilter_destroy(wx_polefilter_handle h) { return guarded([&] { delete h; }); }
+int wx_polefilter_sht(wx_polefilter_handle h, wx_sht_handle* out) {
+  return use(h, "wx_polefilter_sht: null polefilter handle", [&] {
+    if (!out) throw wx::ConfigError("wx_polefilter_sht: null argument");
+    *out = &h->sht;
+  });
+}
+int wx_polefilter_lowpass(wx_polefilter_handle h, int n_planes, const void* x_dev, int64_t x_stride, int dtype, void* out_dev, int64_t out_stride,
+                          void* stream) {
+  return use_remapped(h, "wx_polefilter_lowpass: null polefilter handle",
+                      [&] { h->impl->lowpass(n_planes, x_dev, x_stride, dtype, out_dev, out_stride, (hipStream_t)stream); });
+}
+int wx_polefilter_scalar(wx_polefilter_handle h, int n_planes, const void* x_dev, int64_t x_stride, int dtype, int substeps, double coef,
+                         void* out_dev, int64_t out_stride, void* stream) {
+  return use_remapped(h, "wx_polefilter_scalar: null polefilter handle",
+                      [&] { h->impl->scalar(n_planes, x_dev, x_stride, dtype, substeps, coef, out_dev, out_stride, (hipStream_t)stream); });
+}
+int wx_polefilter_vector(wx_polefilter_handle h, int n_planes, const void* u_dev, int64_t u_stride, const void* v_dev, int64_t v_stride, int dtype,
+                         int substeps, double coef, void* u_out_dev, int64_t u_out_stride, void* v_out_dev, int64_t v_out_stride, void* stream) {
+  return use_remapped(h, "wx_polefilter_vector: null polefilter handle", [&] {
+    h->impl->vector(n_planes, u_dev, u_stride, v_dev, v_stride, dtype, substeps, coef, u_out_dev, u_out_stride, v_out_dev, v_out_stride,
+                    (hipStream_t)stream);
+  });
+}
+int wx_polefilter_gradient(wx_polefilter_handle h, int n_planes, const double* c_dev, void* gx_dev, void* gy_dev, int dtype, void* stream) {
+  return use_remapped(h, "wx_polefilter_gradient: null polefilter handle",
+                      [&] { h->impl->gradient(n_planes, c_dev, gx_dev, gy_dev, dtype, (hipStream_t)stream); });
+}
+int wx_polefilter_workspace(int nlat, int nlon, int lmax, int mmax, int n_planes, int64_t* bytes_out) {
+  return guarded([&] {
+    if (!bytes_out) throw wx::ConfigError("wx_polefilter_workspace: null argument");
+    if (nlat < 1 || nlon < 1 || lmax < 1 || mmax < 1 || nlat > 32768 || nlon > wx::kPerturbMaxN || lmax > 32768 || mmax > lmax)
+      throw wx::ConfigError("wx_polefilter_workspace: nlat, lmax in 1 .. 32768, nlon in 1 .. 4096 and mmax in 1 .. lmax are needed");
+    if (n_planes < 1) throw wx::ConfigError("wx_polefilter_workspace: n_planes must be >= 1, got " + std::to_string(n_planes));
+    *bytes_out = wx::polefilter_workspace(nlat, nlon, lmax, mmax, n_planes);
+  });
+}
+
 const char* wx_last_error(void) { return wx::g_last_error.c_str(); }
 #ifndef WX_SOURCE_HASH
 #define WX_SOURCE_HASH "unhashed"

@@ -8,6 +8,7 @@
 //   wx_abi.h      the extern "C" wrappers of include/wxengine.h
 #include "../../include/wxengine.h"
 #include "../../include/wxengine_sht.h"
+#include "../../include/wxengine_polefilter.h"
 
 #include <algorithm>
 #include <climits>
@@ -48,6 +49,7 @@
 #include "wx_perturb.h"
 #include "wx_spectrum.h"
 #include "wx_sht.h"
+#include "wx_polefilter.h"
 #include "wx_metrics.h"
 #include "wx_ensemble.h"
 #include "wx_noise.h"

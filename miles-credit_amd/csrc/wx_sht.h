@@ -210,6 +210,18 @@ inline std::string sht_check_vector(int nlat, int nlon, int lmax, int mmax, int 
   const ShtRange out[2] = {{s, sht_coeff_bytes(lmax, mmax, n_planes)}, {t, sht_coeff_bytes(lmax, mmax, n_planes)}};
   return sht_check_ranges(in, 2, out, 2);
 }
+// t (the gradient form) and one of u, v (a component alone) may be null
+inline std::string sht_check_vector_synthesis(int nlat, int nlon, int lmax, int mmax, int n_planes, const double* s, const double* t, const void* u,
+                                              const void* v, int dtype) {
+  if (!s) return "a null pointer: the spheroidal coefficients are needed (the toroidal ones may be null)";
+  if (!u && !v) return "no output requested: u and v are both null";
+  const int64_t stride = (int64_t)nlat * nlon;
+  const std::string why = sht_check_planes(nlat, nlon, n_planes, dtype, 1, &stride);
+  if (!why.empty()) return why;
+  const ShtRange in[2] = {{s, sht_coeff_bytes(lmax, mmax, n_planes)}, {t, sht_coeff_bytes(lmax, mmax, n_planes)}};
+  const ShtRange out[2] = {{u, sht_field_bytes(nlat, nlon, n_planes, stride, dtype)}, {v, sht_field_bytes(nlat, nlon, n_planes, stride, dtype)}};
+  return sht_check_ranges(in, 2, out, 2);
+}
 inline std::string sht_check_spectra(int lmax, int mmax, int n_planes, const double* c, const double* zonal, const double* total) {
   if (n_planes < 1) return "n_planes must be >= 1, got " + std::to_string(n_planes);
   if (!c) return "the coefficients are a null pointer";
@@ -445,6 +457,90 @@ __global__ __launch_bounds__(256) void sht_legendre_inv_kernel(const double* __r
   }
 }
 
+// Vector synthesis, first launch: sht_legendre_inv_kernel's tiling on the two vector tables.  With (i z)[re] = -z[im], (i z)[im] = z[re]:
+//   Gu = F_phi = sum_l Qt (i s) + dPt t,   Gv = -F_theta = sum_l -dPt s + Qt (i t);   u = lon_synth(Gu), v = lon_synth(Gv)
+// Qt has Pbar's parity about the equator and dPt the opposite one, so a product lands in the accumulator of its own symmetry: [0]
+// symmetric, [1] antisymmetric, row k = [0] + [1], mirror row = [0] - [1].  Unfolded, the two are simply added.  lscale (may be null):
+// a factor per degree l, multiplied into the table operand.  HAS_T false: tor is never read (the gradient form).  COMP: 1 = Gu alone,
+// 2 = Gv alone, 3 = both.  sph, tor: the coefficients of plane 0 of the pass.
+template <bool HAS_T, int COMP>
+__global__ __launch_bounds__(256) void sht_legendre_vinv_kernel(const double* __restrict__ tab_d, const double* __restrict__ tab_q,
+                                                                const double* __restrict__ lscale, const double* __restrict__ sph,
+                                                                const double* __restrict__ tor, ShtGeom s, int ktiles, double* __restrict__ Gu,
+                                                                double* __restrict__ Gv) {
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int tile = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (tile >= s.mmax * ktiles) return;
+  const int m = tile / ktiles, kt = tile - m * ktiles;
+  const int ncb = s.nb >> 4;
+  const int k = kt * 16 + c;
+  const bool k_ok = k < s.kk;
+  const int64_t coff = sht_table_offset(m, s.lmax, s.kk) + (k_ok ? k : 0);
+  const double* dcol = tab_d + coff;
+  const double* qcol = tab_q + coff;
+  f64x4_t au[2][4] = {}, av[2][4] = {};
+  const int step = s.fold ? 2 : 1;
+#pragma unroll
+  for (int par = 0; par < 2; ++par) {
+    if (par == 1 && !s.fold) break;
+    for (int ic = 0; m + par + step * ic < s.lmax; ic += 16) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int l = m + par + step * (ic + 4 * g + j);
+        const bool l_ok = l < s.lmax;
+        const bool a_ok = l_ok && k_ok;
+        const double ls = (l_ok && lscale) ? lscale[l] : 1.0;
+        const double d = a_ok ? ls * dcol[(int64_t)(l - m) * s.kk] : 0.0;
+        const double q = a_ok ? ls * qcol[(int64_t)(l - m) * s.kk] : 0.0;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          if (t < ncb) {
+            const int n = 16 * t + c, pl = n >> 1, im = n & 1;
+            const bool ok = l_ok && pl < s.np;
+            const int64_t base = (((int64_t)pl * s.lmax + l) * s.mmax + m) * 2;
+            const double sg = im ? 1.0 : -1.0;
+            const double sn = ok ? sph[base + im] : 0.0;
+            const double sx = ok ? sg * sph[base + (im ^ 1)] : 0.0;
+            const double tn = (HAS_T && ok) ? tor[base + im] : 0.0;
+            const double tx = (HAS_T && ok) ? sg * tor[base + (im ^ 1)] : 0.0;
+            if (COMP & 1) {
+              au[par][t] = perturb_mfma(q, sx, au[par][t]);
+              if (HAS_T) au[par ^ 1][t] = perturb_mfma(d, tn, au[par ^ 1][t]);
+            }
+            if (COMP & 2) {
+              av[par ^ 1][t] = perturb_mfma(d, -sn, av[par ^ 1][t]);
+              if (HAS_T) av[par][t] = perturb_mfma(q, tx, av[par][t]);
+            }
+          }
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t < ncb) {
+      const int n = 16 * t + c;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int ko = kt * 16 + g + 4 * r;
+        if (ko < s.kk) {
+          const int mir = s.nlat - 1 - ko;
+          const bool both = s.fold && mir != ko;
+          const int64_t o = ((int64_t)m * s.nlat + ko) * s.nb + n, om = ((int64_t)m * s.nlat + mir) * s.nb + n;
+          if (COMP & 1) {
+            Gu[o] = au[0][t][r] + au[1][t][r];
+            if (both) Gu[om] = au[0][t][r] - au[1][t][r];
+          }
+          if (COMP & 2) {
+            Gv[o] = av[0][t][r] + av[1][t][r];
+            if (both) Gv[om] = av[0][t][r] - av[1][t][r];
+          }
+        }
+      }
+    }
+  }
+}
+
 // Synthesis, second launch: pass C of wx_perturb.h on G[m][k][nb].  dst: plane p of the pass at dst + p * nlat * nlon.
 // grid = (ceil(nlon / 64), ceil(np * nlat / 64)), LDS 16 nlon bytes.
 template <typename T>
@@ -602,6 +698,50 @@ class Sht {
       WX_HIP(hipGetLastError());
     }
   }
+
+  // (u, v) [n_planes][nlat][nlon] from spheroidal sph and toroidal tor (null: the gradient form); u or v null: the other component
+  // alone.  lscale: [lmax] on the device or null, a factor per degree.
+  void vector_synthesis(int n_planes, const double* sph, const double* tor, const double* lscale, void* u, void* v, int dtype, hipStream_t stream) {
+    const std::string why = sht_check_vector_synthesis(nlat, nlon, lmax, mmax, n_planes, sph, tor, u, v, dtype);
+    if (!why.empty()) throw std::runtime_error("wx_sht_vector_synthesis: " + why);
+    WX_HIP(hipSetDevice(device));
+    if (!tab[1]) build_tables(true);
+    const int ktiles = cdiv(kk, 16);
+    const int comp = (u ? 1 : 0) | (v ? 2 : 0);
+    for (int p0 = 0; p0 < n_planes; p0 += kShtMaxPlanes) {
+      const ShtGeom s = pass(std::min(kShtMaxPlanes, n_planes - p0), 2);
+      const dim3 lgrid((unsigned)cdiv((int64_t)mmax * ktiles, 4));
+      const int64_t coff = (int64_t)p0 * lmax * mmax * 2;
+      const double* sp = sph + coff;
+      const double* tp = tor ? tor + coff : nullptr;
+#define WX_SHT_VINV(HAS_T, COMP)                                                                                                        \
+  hipLaunchKernelGGL((sht_legendre_vinv_kernel<HAS_T, COMP>), lgrid, dim3(256), 0, stream, tab[1], tab[2], lscale, sp, tp, s, ktiles, buf[0], buf[1])
+      if (tor) {
+        if (comp == 1) WX_SHT_VINV(true, 1); else if (comp == 2) WX_SHT_VINV(true, 2); else WX_SHT_VINV(true, 3);
+      } else {
+        if (comp == 1) WX_SHT_VINV(false, 1); else if (comp == 2) WX_SHT_VINV(false, 2); else WX_SHT_VINV(false, 3);
+      }
+#undef WX_SHT_VINV
+      WX_HIP(hipGetLastError());
+      const dim3 grid((unsigned)cdiv(nlon, 64), (unsigned)cdiv((int64_t)s.np * nlat, 64));
+      const size_t lds = (size_t)nlon * sizeof(double2);
+      const int64_t off = (int64_t)p0 * nlat * nlon;
+      void* dst[2] = {u, v};
+      for (int i = 0; i < 2; ++i) {
+        if (!dst[i]) continue;
+        if (dtype == kShtF64) hipLaunchKernelGGL(sht_lon_inv_kernel<double>, grid, dim3(256), lds, stream, buf[i], s, twiddle, (double*)dst[i] + off);
+        else hipLaunchKernelGGL(sht_lon_inv_kernel<float>, grid, dim3(256), lds, stream, buf[i], s, twiddle, (float*)dst[i] + off);
+        WX_HIP(hipGetLastError());
+      }
+    }
+  }
+
+  // the scratch of a pass of np planes, in bytes: both buffers
+  static int64_t scratch_bytes(int nlat, int mmax, int np) { return 2 * (int64_t)mmax * nlat * ((2 * np + 15) / 16 * 16) * 8; }
+  int n_lat() const { return nlat; }
+  int n_lon() const { return nlon; }
+  int l_max() const { return lmax; }
+  int m_max() const { return mmax; }
 
   void spectra(int n_planes, const double* c, double* zonal, double* total, hipStream_t stream) {
     const std::string why = sht_check_spectra(lmax, mmax, n_planes, c, zonal, total);

@@ -14,6 +14,7 @@ Everything here sits above the C ABI of include/wxengine.h (libwxengine.so, buil
   ensemble_metrics  ensemble verification, CRPS / spread / ensemble-mean error from one reading pass (EnsembleVerification, PendingEnsembleScores, exported here)
   spectrum          zonal power spectra, PSD / latitude-mean spectra / spectral scores from a folded fp64 DFT (ZonalSpectrum, PendingSpectra, SpectrumResult, exported here)
   sht               spherical harmonic transforms, scalar pair / vector analysis / spectra by zonal and total wavenumber (SphericalHarmonics, RealSHT, InverseRealSHT, grid_nodes, zonal_spectrum, average_zonal_spectrum, div_rot_spectrum, average_div_rot_spectrum, exported here)
+  pole_filter       the diffusion and pole filter of a forecast step, polar zonal low-pass and three explicit diffusion schemes on the transforms (Diffusion_and_Pole_Filter, exported here)
   config / synth    model geometry, name-keyed synthetic weights and inputs for tests and the benchmark
 There is no CPU fallback: without the HIP library or a GPU, construction raises.
 """
@@ -51,4 +52,7 @@ def __getattr__(name):   # lazily: importing the package stays free of torch
                 "average_div_rot_spectrum", "cached_transform", "clear_cache"):
         from . import sht
         return getattr(sht, name)
+    if name == "Diffusion_and_Pole_Filter":
+        from .pole_filter import Diffusion_and_Pole_Filter
+        return Diffusion_and_Pole_Filter
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

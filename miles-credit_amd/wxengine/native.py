@@ -201,6 +201,22 @@ _EXTENSION_PROTOTYPES = {
                       C.POINTER(C.c_double), C.POINTER(C.c_int)], C.c_int),
 }
 
+# include/wxengine_polefilter.h: the inverse vector transform and the diffusion and pole filter, bound by load_library() as well
+_POLEFILTER_PROTOTYPES = {
+    "wx_sht_vector_synthesis": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "wx_polefilter_create": ([C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_int, C.c_int,
+                              C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_polefilter_destroy": ([C.c_void_p], C.c_int),
+    "wx_polefilter_sht": ([C.c_void_p, C.POINTER(C.c_void_p)], C.c_int),
+    "wx_polefilter_lowpass": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "wx_polefilter_scalar": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p],
+                             C.c_int),
+    "wx_polefilter_vector": ([C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p,
+                              C.c_int64, C.c_void_p, C.c_int64, C.c_void_p], C.c_int),
+    "wx_polefilter_gradient": ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p], C.c_int),
+    "wx_polefilter_workspace": ([C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)], C.c_int),
+}
+
 
 def exported_symbols():
     """The functions of include/wxengine.h (the extension header's are _EXTENSION_PROTOTYPES)."""
@@ -217,7 +233,7 @@ def load_library():
                             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     import torch  # noqa: F401  (loads libamdhip64 with the SONAME our library needs)
     lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-    for name, (args, res) in list(_PROTOTYPES.items()) + list(_EXTENSION_PROTOTYPES.items()):
+    for name, (args, res) in list(_PROTOTYPES.items()) + list(_EXTENSION_PROTOTYPES.items()) + list(_POLEFILTER_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -217,3 +217,16 @@ def spectra_of_rollout(out, targets, spectrum, channel_map, wavenum_init=20):
     for y, target in zip(out, targets):
         pending.append(spectrum.submit(split(y), target if isinstance(target, dict) else split(target), wavenum_init))
     return pending
+
+
+def filter_rollout(out, dpf):
+    """The diffusion and pole filter on the per-step physical output of a rollout, where it lies: the device counterpart of
+    rollout_metrics.py's `if use_laplace_filter: y_pred = dpf.diff_lap2d_filt(y_pred.to(device).squeeze())` before scoring and saving.
+
+    out[step]: a [1, C, H, W] tensor (C >= 70, the reference's channel layout); dpf: a pole_filter.Diffusion_and_Pole_Filter on H x W.
+    Every step is filtered in place without a host sync.  Returns `out`."""
+    for y in out:
+        if y.dim() != 4 or y.shape[0] != 1:
+            raise ValueError(f"filter_rollout: a step's output must be [1, C, H, W], got {tuple(y.shape)}")
+        dpf.diff_lap2d_filt(y[0], out=y[0])
+    return out

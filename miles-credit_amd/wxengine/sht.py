@@ -106,6 +106,17 @@ class SphericalHarmonics:
         self.theta, self.w = grid_nodes(self.nlat, grid)
         self._open(0 if device is None else device)
 
+    @classmethod
+    def borrowed(cls, handle, owner, lib, device, nlat, nlon, lmax, mmax, grid, csphase=False):
+        """A transform over a native wx_sht handle that another object owns (`owner`, kept alive here; `handle` is never destroyed
+        from this side): the pole filter's own transform.  `device` is a torch.device with an index."""
+        self = cls.__new__(cls)
+        self.nlat, self.nlon, self.lmax, self.mmax = check_transform(nlat, nlon, lmax, mmax, grid, "ortho")
+        self.grid, self.norm, self.csphase = grid, "ortho", bool(csphase)
+        self.theta, self.w = grid_nodes(self.nlat, grid)
+        self.lib, self.device, self._handles, self._owner, self._h = lib, device, None, owner, handle
+        return self
+
     def _open(self, device) -> None:
         import torch
         self.lib = require_gpu("the spherical harmonic transform has no CPU fallback", device)
@@ -181,6 +192,30 @@ class SphericalHarmonics:
             _check(self.lib.wx_sht_vector_analysis(self._h, P, C.c_void_p(a.data_ptr()), a_stride, C.c_void_p(b.data_ptr()), b_stride, dtype,
                                                    C.c_void_p(s.data_ptr()), C.c_void_p(t.data_ptr()), _stream_ptr(self.device.index)))
         return s, t
+
+    def vector_synthesis(self, s, t=None, dtype=None, components="uv"):
+        """(u east, v north) [..., nlat, nlon] from the spheroidal s and toroidal t coefficients: F_theta = sum_l dPt s - i Qt t,
+        F_phi = sum_l i Qt s + dPt t, u = lon_synth(F_phi), v = -lon_synth(F_theta), the longitude synthesis of `synthesis`.
+        t=None: no toroidal part (the gradient form, half the work).  components "u" or "v": that component alone (the other is None)."""
+        import torch
+        dtype = torch.float64 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"SphericalHarmonics.vector_synthesis: dtype must be torch.float32 or torch.float64, got {dtype}")
+        if components not in ("uv", "u", "v"):
+            raise ValueError(f"SphericalHarmonics.vector_synthesis: components must be 'uv', 'u' or 'v', got {components!r}")
+        a, P, lead = self._coeffs(s, "s")
+        b = None
+        if t is not None:
+            b, Pb, lead_b = self._coeffs(t, "t")
+            if lead != lead_b:
+                raise WXEngineError(f"s {tuple(s.shape)} and t {tuple(t.shape)} must be one shape")
+        u = torch.empty(lead + (self.nlat, self.nlon), dtype=dtype, device=self.device) if "u" in components else None
+        v = torch.empty(lead + (self.nlat, self.nlon), dtype=dtype, device=self.device) if "v" in components else None
+        ptr = lambda x: C.c_void_p(None if x is None else x.data_ptr())      # noqa: E731
+        with torch.cuda.device(self.device.index):
+            _check(self.lib.wx_sht_vector_synthesis(self._h, P, ptr(a), ptr(b), ptr(u), ptr(v), 1 if dtype == torch.float64 else 0,
+                                                    _stream_ptr(self.device.index)))
+        return u, v
 
     def spectra(self, c):
         """(zonal [..., mmax], total [..., lmax]) float64 of the coefficients c."""

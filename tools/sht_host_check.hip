@@ -1,5 +1,5 @@
-// Stand-alone check of the host side of csrc/wx_sht.h -- the table builder, the fold test, the tile list and the ""-or-reason
-// checkers -- for a sanitizer build.  No device is touched: it runs on a machine without a GPU.
+// Stand-alone check of the host side of csrc/wx_sht.h and csrc/wx_polefilter.h -- the table builder, the fold test, the tile list,
+// the ""-or-reason checkers, the plane overlap test and the per-degree scales -- for a sanitizer build.  No device is touched: it runs on a machine without a GPU.
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined tools/sht_host_check.hip -o sht_host_check
 //   ./sht_host_check          # prints "sht_host_check: ok" and exits 0, or the first failed expectation
@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "../miles-credit_amd/csrc/wx_polefilter.h"
 #include "../miles-credit_amd/csrc/wx_sht.h"
 
 #define EXPECT(cond)                                                          \
@@ -105,6 +106,41 @@ int main() {
     EXPECT(sht_check_spectra(lmax, mmax, 2, c.data(), z.data(), z.data() + 2 * mmax).empty());
     EXPECT(!sht_check_spectra(lmax, mmax, 2, c.data(), nullptr, nullptr).empty());
     EXPECT(!sht_check_spectra(lmax, mmax, 2, c.data(), z.data(), z.data() + 1).empty());
+    // the inverse vector transform: the toroidal part and one component may be missing
+    EXPECT(sht_check_vector_synthesis(nlat, nlon, lmax, mmax, 1, c.data(), c.data() + (size_t)lmax * mmax * 2, x.data(), x.data() + hw, kShtF32).empty());
+    EXPECT(sht_check_vector_synthesis(nlat, nlon, lmax, mmax, 1, c.data(), nullptr, nullptr, x.data(), kShtF32).empty());
+    EXPECT(!sht_check_vector_synthesis(nlat, nlon, lmax, mmax, 1, nullptr, c.data(), x.data(), x.data() + hw, kShtF32).empty());
+    EXPECT(!sht_check_vector_synthesis(nlat, nlon, lmax, mmax, 1, c.data(), nullptr, nullptr, nullptr, kShtF32).empty());
+    EXPECT(!sht_check_vector_synthesis(nlat, nlon, lmax, mmax, 1, c.data(), nullptr, x.data(), x.data() + 1, kShtF32).empty());
+    // the pole filter's checkers and its per-degree scales
+    std::vector<float> sig((size_t)nlat, 1.f);
+    const int indpol = (nlat - 1) / 2;
+    EXPECT(polefilter_check_create(nlat, nlon, 6.37122e6, indpol, nlon / 2, sig.data()).empty());
+    EXPECT(!polefilter_check_create(nlat, nlon, 6.37122e6, indpol + 1, 0, sig.data()).empty());
+    EXPECT(!polefilter_check_create(nlat, nlon, 0.0, indpol, 0, sig.data()).empty());
+    EXPECT(!polefilter_check_create(nlat, nlon, NAN, indpol, 0, sig.data()).empty());
+    EXPECT(!polefilter_check_create(nlat, nlon, 1.0, indpol, nlon / 2 + 1, sig.data()).empty());
+    EXPECT(!polefilter_check_create(nlat, nlon, 1.0, -1, 0, sig.data()).empty());
+    sig[nlat - 1] = INFINITY;
+    EXPECT(!polefilter_check_create(nlat, nlon, 1.0, indpol, 0, sig.data()).empty());
+    const PoleField a = {x.data(), hw}, b = {x.data() + hw, hw}, ai = {x.data(), 2 * hw}, bi = {x.data() + hw, 2 * hw}, shifted = {x.data() + 1, hw};
+    EXPECT(polefilter_check_call(nlat, nlon, 1, kShtF32, 3, 1e8, &a, &b, 1).empty());
+    EXPECT(polefilter_check_call(nlat, nlon, 2, kShtF32, 0, 0.0, &a, &a, 1).empty());           // in place
+    EXPECT(!polefilter_check_call(nlat, nlon, 2, kShtF32, 3, 1e8, &a, &b, 1).empty());          // plane 1 of a is plane 0 of b
+    EXPECT(!polefilter_check_call(nlat, nlon, 1, kShtF32, 3, 1e8, &a, &shifted, 1).empty());
+    EXPECT(!polefilter_check_call(nlat, nlon, 1, kShtF32, -1, 1e8, &a, &b, 1).empty());
+    EXPECT(!polefilter_check_call(nlat, nlon, 1, kShtF32, 1, INFINITY, &a, &b, 1).empty());
+    EXPECT(!polefilter_check_call(nlat, nlon, 0, kShtF32, 1, 1e8, &a, &b, 1).empty());
+    EXPECT(!polefilter_check_call(nlat, nlon, 1, 9, 1, 1e8, &a, &b, 1).empty());
+    const PoleField pair_in[2] = {ai, bi}, pair_bad[2] = {ai, ai};
+    EXPECT(polefilter_check_call(nlat, nlon, 1, kShtF32, 1, 2e16, pair_in, pair_in, 2).empty()); // interleaved planes, in place
+    EXPECT(!polefilter_check_call(nlat, nlon, 1, kShtF32, 1, 2e16, pair_in, pair_bad, 2).empty());
+    EXPECT(!polefilter_planes_overlap(ai, bi, 1, hw, 4) && polefilter_planes_overlap(ai, shifted, 1, hw, 4));
+    EXPECT(polefilter_workspace(nlat, nlon, lmax, mmax, 40) == polefilter_workspace(nlat, nlon, lmax, mmax, kPoleChunk));
+    std::vector<double> sg, sdg;
+    polefilter_scales(lmax, 6.37122e6, sg, sdg);
+    EXPECT((int)sg.size() == lmax && sg[0] == 0.0 && sdg[0] == 0.0);
+    for (int l = 1; l < lmax; ++l) EXPECT(sg[l] > sg[l - 1] && sdg[l] == -(sg[l] * sg[l]));
   }
   std::printf("sht_host_check: ok\n");
   return 0;
