@@ -850,7 +850,7 @@ int wx_polefilter_gradient(wx_polefilter_handle h, int n_planes, const double* c
 int wx_polefilter_workspace(int nlat, int nlon, int lmax, int mmax, int n_planes, int64_t* bytes_out) {
   return guarded([&] {
     if (!bytes_out) throw wx::ConfigError("wx_polefilter_workspace: null argument");
-    if (nlat < 1 || nlon < 1 || lmax < 1 || mmax < 1 || nlat > 32768 || nlon > wx::kPerturbMaxN || lmax > 32768 || mmax > lmax)
+    if (nlat < 1 || nlon < 1 || lmax < 1 || mmax < 1 || nlat > 32768 || nlon > wx::kDftMaxN || lmax > 32768 || mmax > lmax)
       throw wx::ConfigError("wx_polefilter_workspace: nlat, lmax in 1 .. 32768, nlon in 1 .. 4096 and mmax in 1 .. lmax are needed");
     if (n_planes < 1) throw wx::ConfigError("wx_polefilter_workspace: n_planes must be >= 1, got " + std::to_string(n_planes));
     *bytes_out = wx::polefilter_workspace(nlat, nlon, lmax, mmax, n_planes);

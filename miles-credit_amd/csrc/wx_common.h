@@ -15,6 +15,10 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;   // v_pk_{fma,mul,add}_f32 operand
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+typedef __attribute__((ext_vector_type(4))) double f64x4_t;  // v_mfma_f64_16x16x4_f64 accumulator
+
+// D = A B + C on v_mfma_f64_16x16x4_f64: lane l holds A[l & 15][l >> 4], B[l >> 4][l & 15] and D[(l >> 4) + 4 reg][l & 15], reg 0 .. 3
+__device__ inline f64x4_t mfma_f64_16x16x4(double a, double b, f64x4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 
 struct HipError : std::runtime_error {
   using std::runtime_error::runtime_error;
@@ -259,6 +263,12 @@ __device__ __forceinline__ float max_over_rows(float x) {
 __device__ __forceinline__ int pair_rows16_channel(int g) { return 16 * (g & 1) + 4 * (g & ~1); }
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Do the byte ranges [a, a + a_bytes) and [b, b + b_bytes) share memory?  The pointers are compared, never read.
+inline bool bytes_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)a_bytes, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)b_bytes;
+  return a0 < b1 && b0 < a1;
+}
 
 // Owner of the device allocations of one object on one device.  Held as a MEMBER: a constructor that throws halfway still frees what it
 // had allocated, and a destructor body (streams, graphs, communicators) runs before the memory goes.  The caller has made `device`

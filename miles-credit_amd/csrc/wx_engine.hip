@@ -46,6 +46,7 @@
 #include "wx_hybrid.h"
 #include "wx_regrid.h"
 #include "wx_tisr.h"
+#include "wx_dft.h"
 #include "wx_perturb.h"
 #include "wx_spectrum.h"
 #include "wx_sht.h"

@@ -10,24 +10,16 @@
 // general not quad-aligned: noise_run4.  A draw depends on (seed, member, step, e) alone: not on the launch geometry, the plane
 // batching, the plane count or on which other members or steps were drawn.
 //
-// Kind colour: dense DFTs, fp64 accumulation on v_mfma_f64_16x16x4_f64 (D = A B + C; lane l holds A[l & 15][l >> 4], B[l >> 4][l & 15]
-// and D[(l >> 4) + 4 reg][l & 15], reg 0 .. 3), no FFT library and no factorisation; Wh = W / 2 + 1, a complex number is (re, im)
-// interleaved, so a half-complex row is 2 Wh doubles:
+// Kind colour: the dense fp64 DFTs of wx_dft.h (MFMA lane layout, LDS twiddle table, DftPhase and the fixed sum order are stated
+// there); Wh = W / 2 + 1, a complex number is (re, im) interleaved, so a half-complex row is 2 Wh doubles:
 //   pass A  perturb_rows_fwd_kernel   lon, real -> half-complex    X1[(p, h)][n] = sum_x r[(p, h)][x] T_W[x][n]          M = Pb H, N = 2 Wh, K = W
-//                                     T_W[x][2k] = cos(2 pi k x / W), T_W[x][2k + 1] = -sin(2 pi k x / W)
+//                                     T_W[x][2k] = cos(2 pi k x / W), T_W[x][2k + 1] = -sin(2 pi k x / W); unfolded
 //   pass B  perturb_cols_kernel       lat, complex, two launches: forward with the product by S in the store, then inverse (+i, unscaled)
 //                                     per plane  D[l][n] = sum_h cos(.) X[h][n] + (-+sin(.)) Xs[h][n],  (.) = 2 pi l h / H,
 //                                     Xs[h][2k] = -X[h][2k + 1], Xs[h][2k + 1] = X[h][2k]                               M = H, N = 2 Wh, K = H
-//   pass C  perturb_rows_inv_kernel   lon, half-complex -> real by irfft's conventions: bin 0 and, for even W, the Nyquist bin count once
-//                                     and their imaginary parts are ignored; every other bin counts twice; scale 1 / (H W); then
-//                                     the epilogue                                                                       M = Pb H, N = W, K = 2 Wh
-// A wave owns a 16 x 64 tile of D (four accumulators; the A operand is shared by the four), a workgroup of four waves 64 x 64.  K runs in
-// chunks of 16: lane group g = l >> 4 takes k = chunk + 4 g + j in MFMA j = 0 .. 3, so a lane reads four consecutive elements of its row.
-// Twiddles never come from a matrix in memory: each pass stages the length-N table (cos, sin)(2 pi j / N), built on the host in fp64,
-// in LDS (16 N bytes, N <= kPerturbMaxN = 4096) and indexes it with (k x) mod N kept in INTEGER arithmetic -- one 64-bit modulo at the
-// start, then additions with a conditional subtraction -- which is what keeps the phase exact at N = 1440.
-// Every sum has one fixed order (k ascending by chunk and j; inside an MFMA the hardware's); an output element depends on its own row
-// and column only, so a plane's result is bit-identical whatever P, the batch split or its position in the batch.
+//   pass C  perturb_rows_inv_kernel   lon, half-complex -> real: dft_rows_inverse, scale 1 / (H W), then the epilogue   M = Pb H, N = W, K = 2 Wh
+// A wave owns a 16 x 64 tile of D (four accumulators; the A operand is shared by the four), a workgroup of four waves 64 x 64.
+// A plane's result is bit-identical whatever P, the batch split or its position in the batch.
 // Intermediates are complex fp64 in two scratch buffers of the handle, processed in plane batches: a plane takes 2 * 16 H Wh bytes
 // (16.6 MB at 721 x 1440), a batch is min(kPerturbMaxBatch = 64, kPerturbScratchBytes = 256 MiB / that) planes -- 16 planes, 266 MB, at
 // 721 x 1440 -- plus 4 H W bytes per plane for the generator's draws (the generator fills a tape of its own for a batch, so that no
@@ -48,6 +40,7 @@
 #include <vector>
 
 #include "wx_common.h"
+#include "wx_dft.h"
 #include "wx_noise.h"
 
 namespace wx {
@@ -55,12 +48,9 @@ namespace wx {
 constexpr uint32_t SLOT_PERTURB = 16;
 constexpr int kPerturbWhite = 0;
 constexpr int kPerturbColour = 1;
-constexpr int kPerturbMaxN = 4096;                       // the LDS table of one pass: 16 bytes per entry, 64 KB
 constexpr int kPerturbMaxBatch = 64;
 constexpr int64_t kPerturbScratchBytes = 256LL << 20;    // both complex buffers of a batch
 constexpr int64_t kPerturbMaxElems = 1LL << 34;          // q = e >> 2 is a 32-bit counter word
-
-typedef __attribute__((ext_vector_type(4))) double f64x4_t;
 
 struct PerturbEpi {
   float amplitude, rho;
@@ -85,19 +75,14 @@ inline std::string perturb_check_create(int H, int W, int kind, const float* S) 
   if (H < 1 || W < 2) return "H must be >= 1 and W >= 2, got " + std::to_string(H) + " x " + std::to_string(W);
   if ((int64_t)H * W > kPerturbMaxElems) return "H * W is beyond the generator's counter (2^34 elements)";
   if (kind == kPerturbColour) {
-    if (H > kPerturbMaxN || W > kPerturbMaxN)
-      return "the colour filter takes grids up to " + std::to_string(kPerturbMaxN) + " points a side, got " + std::to_string(H) + " x " + std::to_string(W);
+    if (H > kDftMaxN || W > kDftMaxN)
+      return "the colour filter takes grids up to " + std::to_string(kDftMaxN) + " points a side, got " + std::to_string(H) + " x " + std::to_string(W);
     if (!S) return "the colour filter needs the spectral weights S [H][W / 2 + 1], got a null pointer";
     const int64_t n = (int64_t)H * (W / 2 + 1);
     for (int64_t i = 0; i < n; ++i)
       if (!std::isfinite(S[i])) return "the spectral weights S must be finite, entry " + std::to_string(i) + " is not";
   }
   return "";
-}
-
-inline bool perturb_overlap(const float* a, int64_t a_len, const float* b, int64_t b_len) {
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)a_len * 4, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)b_len * 4;
-  return a0 < b1 && b0 < a1;
 }
 
 // "" or the reason wx_perturb_apply refuses, decided on the host before anything is launched or copied.
@@ -117,28 +102,20 @@ inline std::string perturb_check_apply(int H, int W, int n_planes, const float* 
   };
   if (far(prev, prev_stride) || far(x_out ? x : nullptr, x_stride) || far(delta_out, delta_stride) || far(x_out, xout_stride))
     return "a plane stride takes the planes beyond 2^44 floats";
-  const auto span = [&](int64_t s) { return (int64_t)(n_planes - 1) * s + hw; };
-  if (tape && ((delta_out && perturb_overlap(tape, hw * n_planes, delta_out, span(delta_stride))) ||
-               (x_out && perturb_overlap(tape, hw * n_planes, x_out, span(xout_stride)))))
+  const auto span = [&](int64_t s) { return ((int64_t)(n_planes - 1) * s + hw) * 4; };   // bytes
+  const int64_t tape_bytes = hw * n_planes * 4;
+  if (tape && ((delta_out && bytes_overlap(tape, tape_bytes, delta_out, span(delta_stride))) ||
+               (x_out && bytes_overlap(tape, tape_bytes, x_out, span(xout_stride)))))
     return "the tape overlaps an output: a later plane batch would read draws that an earlier one has overwritten";
   // an input may be an output's own memory element for element, never a shifted view of it
   const auto shifted = [&](const float* in, int64_t si, const float* out, int64_t so) {
-    return in && out && perturb_overlap(in, span(si), out, span(so)) && !(in == out && si == so);
+    return in && out && bytes_overlap(in, span(si), out, span(so)) && !(in == out && si == so);
   };
   if (shifted(prev, prev_stride, delta_out, delta_stride) || shifted(prev, prev_stride, x_out, xout_stride) ||
       (x_out && (shifted(x, x_stride, x_out, xout_stride) || shifted(x, x_stride, delta_out, delta_stride))) ||
       shifted(delta_out, delta_stride, x_out, xout_stride) || (delta_out && x_out && delta_out == x_out))
     return "an input overlaps an output without being the same view (same pointer and stride), or the two outputs overlap";
   return "";
-}
-
-// (cos, sin)(2 pi j / N), j = 0 .. N - 1, in fp64
-inline void perturb_table(int N, std::vector<double2>& t) {
-  t.resize(N);
-  for (int j = 0; j < N; ++j) {
-    const double a = 2.0 * 3.14159265358979323846 * (double)j / (double)N;
-    t[j] = make_double2(std::cos(a), std::sin(a));
-  }
 }
 
 // ---- device side -------------------------------------------------------------------------------------------------------------------
@@ -193,18 +170,11 @@ __global__ __launch_bounds__(256) void perturb_white_kernel(const float* tape, N
   }
 }
 
-__device__ inline f64x4_t perturb_mfma(double a, double b, f64x4_t c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
-__device__ inline void perturb_stage_table(double2* tab, const double2* tab_g, int N) {
-  for (int i = threadIdx.x; i < N; i += 256) tab[i] = tab_g[i];
-  __syncthreads();
-}
-__device__ inline int perturb_wrap(int i, int N) { return i >= N ? i - N : i; }   // i < 2 N
-
 // Pass A.  src [M][W] float32 (M = Pb H rows), out [M][2 Wh] fp64.  grid = (ceil(2 Wh / 64), ceil(M / 64)), LDS 16 W bytes.
 __global__ __launch_bounds__(256) void perturb_rows_fwd_kernel(const float* __restrict__ src, int M, int W, const double2* __restrict__ tab_g,
                                                                double* __restrict__ out) {
   extern __shared__ double2 perturb_tab[];
-  perturb_stage_table(perturb_tab, tab_g, W);
+  dft_stage_table(perturb_tab, tab_g, W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int N = 2 * (W / 2 + 1);
   const int m0 = ((int)blockIdx.y * 4 + wave) * 16, n0 = (int)blockIdx.x * 64;
@@ -212,16 +182,13 @@ __global__ __launch_bounds__(256) void perturb_rows_fwd_kernel(const float* __re
   const int row = m0 + c;
   const bool row_ok = row < M;
   const float* srow = src + (int64_t)(row_ok ? row : 0) * W;
-  int idx[4], step1[4], step12[4];
+  DftPhase ph[4];
   bool im[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int n = n0 + 16 * t + c;
-    const int k = (n >> 1) % W;                        // columns beyond 2 Wh are computed and never stored
     im[t] = n & 1;
-    idx[t] = (int)(((int64_t)k * (4 * g)) % W);
-    step1[t] = k;
-    step12[t] = (int)(((int64_t)k * 12) % W);
+    ph[t].init(n >> 1, 4 * g, 12, W);
   }
   f64x4_t acc[4] = {};
   for (int kc = 0; kc < W; kc += 16) {
@@ -233,13 +200,13 @@ __global__ __launch_bounds__(256) void perturb_rows_fwd_kernel(const float* __re
     for (int j = 0; j < 4; ++j) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const double2 cs = perturb_tab[idx[t]];
-        acc[t] = perturb_mfma(a[j], im[t] ? -cs.y : cs.x, acc[t]);
-        idx[t] = perturb_wrap(idx[t] + step1[t], W);
+        const double2 cs = perturb_tab[ph[t].idx];
+        acc[t] = mfma_f64_16x16x4(a[j], im[t] ? -cs.y : cs.x, acc[t]);
+        ph[t].step(W);
       }
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) idx[t] = perturb_wrap(idx[t] + step12[t], W);
+    for (int t = 0; t < 4; ++t) ph[t].skip(W);
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -257,34 +224,33 @@ __global__ __launch_bounds__(256) void perturb_rows_fwd_kernel(const float* __re
 __global__ __launch_bounds__(256) void perturb_cols_kernel(const double* __restrict__ in, int H, int N, double sgn, const float* __restrict__ S,
                                                            const double2* __restrict__ tab_g, double* __restrict__ out) {
   extern __shared__ double2 perturb_tab[];
-  perturb_stage_table(perturb_tab, tab_g, H);
+  dft_stage_table(perturb_tab, tab_g, H);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int m0 = ((int)blockIdx.y * 4 + wave) * 16, n0 = (int)blockIdx.x * 64;
   if (m0 >= H) return;
   const int64_t plane = (int64_t)blockIdx.z * H * N;
   const double* X = in + plane;
-  const int l = (m0 + c) % H;                          // rows beyond H are computed and never stored
-  int idx = (int)(((int64_t)l * (4 * g)) % H);
-  const int step12 = (int)(((int64_t)l * 12) % H);
+  DftPhase ph;
+  ph.init(m0 + c, 4 * g, 12, H);                       // k = l, the output row
   f64x4_t acc[4] = {};
   for (int kc = 0; kc < H; kc += 16) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int h = kc + 4 * g + j;
-      const double2 cs = perturb_tab[idx];
+      const double2 cs = perturb_tab[ph.idx];
       const double ca = cs.x, sa = sgn * cs.y;
-      idx = perturb_wrap(idx + l, H);
+      ph.step(H);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const int n = n0 + 16 * t + c;
         const bool ok = h < H && n < N;
         const double v = ok ? X[(int64_t)h * N + n] : 0.0;
         const double w = ok ? X[(int64_t)h * N + (n ^ 1)] : 0.0;   // N is even: n ^ 1 < N
-        acc[t] = perturb_mfma(ca, v, acc[t]);
-        acc[t] = perturb_mfma(sa, (n & 1) ? w : -w, acc[t]);
+        acc[t] = mfma_f64_16x16x4(ca, v, acc[t]);
+        acc[t] = mfma_f64_16x16x4(sa, (n & 1) ? w : -w, acc[t]);
       }
     }
-    idx = perturb_wrap(idx + step12, H);
+    ph.skip(H);
   }
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -305,7 +271,7 @@ __global__ __launch_bounds__(256) void perturb_cols_kernel(const double* __restr
 __global__ __launch_bounds__(256) void perturb_rows_inv_kernel(const double* __restrict__ in, int M, int H, int W, double scale,
                                                                const double2* __restrict__ tab_g, int64_t p0, PerturbEpi epi) {
   extern __shared__ double2 perturb_tab[];
-  perturb_stage_table(perturb_tab, tab_g, W);
+  dft_stage_table(perturb_tab, tab_g, W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int Wh = W / 2 + 1, N = 2 * Wh;
   const int m0 = ((int)blockIdx.y * 4 + wave) * 16, n0 = (int)blockIdx.x * 64;
@@ -313,35 +279,9 @@ __global__ __launch_bounds__(256) void perturb_rows_inv_kernel(const double* __r
   const int row = m0 + c;
   const bool row_ok = row < M;
   const double* zrow = in + (int64_t)(row_ok ? row : 0) * N;
-  int idx[4], step1[4], step8[4];                      // idx: (ka x) mod W of the lane's first bin ka = (chunk + 4 g) / 2
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int x = (n0 + 16 * t + c) % W;               // columns beyond W are computed and never stored
-    idx[t] = (int)(((int64_t)x * (2 * g)) % W);
-    step1[t] = x;
-    step8[t] = (int)(((int64_t)x * 8) % W);
-  }
   f64x4_t acc[4] = {};
-  for (int kc = 0; kc < N; kc += 16) {
-    const int kk0 = kc + 4 * g;
-    double a[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) a[j] = (row_ok && kk0 + j < N) ? zrow[kk0 + j] : 0.0;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {                      // the lane's two bins
-      const int k = (kk0 >> 1) + b;
-      const bool once = k == 0 || 2 * k == W;          // bin 0 and the Nyquist bin: weight 1, imaginary part ignored
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int i = b ? perturb_wrap(idx[t] + step1[t], W) : idx[t];
-        const double2 cs = perturb_tab[i];
-        acc[t] = perturb_mfma(a[2 * b], once ? cs.x : 2.0 * cs.x, acc[t]);
-        acc[t] = perturb_mfma(a[2 * b + 1], once ? 0.0 : -2.0 * cs.y, acc[t]);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) idx[t] = perturb_wrap(idx[t] + step8[t], W);
-  }
+  dft_rows_inverse([&](int k) { return (row_ok && k < Wh) ? make_double2(zrow[2 * k], zrow[2 * k + 1]) : make_double2(0.0, 0.0); }, Wh, W, n0,
+                   perturb_tab, acc);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int x = n0 + 16 * t + c;
@@ -362,9 +302,9 @@ class Perturb {
     WX_HIP(hipSetDevice(device));
     if (kind == kPerturbColour) {
       std::vector<double2> t;
-      perturb_table(W, t);
+      dft_table(W, t);
       tab_w = mem.upload(t.data(), t.size());
-      perturb_table(H, t);
+      dft_table(H, t);
       tab_h = mem.upload(t.data(), t.size());
       S = mem.upload(S_host, (size_t)H * (W / 2 + 1));
     }
@@ -409,11 +349,11 @@ class Perturb {
                            (int64_t)p0, nb, H, W, raw, epi);
       }
       const dim3 rows_grid((unsigned)cdiv(N, 64), (unsigned)cdiv(M, 64)), cols_grid((unsigned)cdiv(N, 64), (unsigned)cdiv(H, 64), (unsigned)nb);
-      hipLaunchKernelGGL(perturb_rows_fwd_kernel, rows_grid, dim3(256), (size_t)W * sizeof(double2), stream, src, M, W, tab_w, buf_a);
-      hipLaunchKernelGGL(perturb_cols_kernel, cols_grid, dim3(256), (size_t)H * sizeof(double2), stream, buf_a, H, N, -1.0, S, tab_h, buf_b);
-      hipLaunchKernelGGL(perturb_cols_kernel, cols_grid, dim3(256), (size_t)H * sizeof(double2), stream, buf_b, H, N, 1.0, (const float*)nullptr,
+      hipLaunchKernelGGL(perturb_rows_fwd_kernel, rows_grid, dim3(256), dft_lds_bytes(W), stream, src, M, W, tab_w, buf_a);
+      hipLaunchKernelGGL(perturb_cols_kernel, cols_grid, dim3(256), dft_lds_bytes(H), stream, buf_a, H, N, -1.0, S, tab_h, buf_b);
+      hipLaunchKernelGGL(perturb_cols_kernel, cols_grid, dim3(256), dft_lds_bytes(H), stream, buf_b, H, N, 1.0, (const float*)nullptr,
                          tab_h, buf_a);
-      hipLaunchKernelGGL(perturb_rows_inv_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(M, 64)), dim3(256), (size_t)W * sizeof(double2), stream,
+      hipLaunchKernelGGL(perturb_rows_inv_kernel, dim3((unsigned)cdiv(W, 64), (unsigned)cdiv(M, 64)), dim3(256), dft_lds_bytes(W), stream,
                          buf_a, M, H, W, scale, tab_w, (int64_t)p0, epi);
     }
     WX_HIP(hipGetLastError());

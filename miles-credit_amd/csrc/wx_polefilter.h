@@ -58,7 +58,7 @@ struct PoleField {
 // planes of two fields may interleave, as the channels of one tensor do --, the test of the whole ranges otherwise.
 inline bool polefilter_planes_overlap(const PoleField& a, const PoleField& b, int n, int64_t hw, int elem) {
   const int64_t ab = ((int64_t)(n - 1) * a.stride + hw) * elem, bb = ((int64_t)(n - 1) * b.stride + hw) * elem;
-  if (!spectrum_overlap(a.p, ab, b.p, bb)) return false;
+  if (!bytes_overlap(a.p, ab, b.p, bb)) return false;
   if (a.stride != b.stride || n == 1) return true;
   const int64_t S = a.stride * elem, H = hw * elem;
   const int64_t d = (int64_t)((intptr_t)b.p - (intptr_t)a.p);      // plane j of b against plane i of a: d + (j - i) S, |j - i| <= n - 1

@@ -29,14 +29,13 @@
 // unfolded, kk = nlat.  The weight w_k multiplies the field operand, so the one table serves analysis and synthesis.
 //
 // Launch A, sht_lon_kernel: planes of float32 or float64 -> F[m][k][n] fp64 in the handle's scratch, n = 2 (plane in pass) + (re, im)
-//   innermost.  Operand layout, LDS twiddle table indexed in integer arithmetic and MFMA are pass A's of wx_perturb.h
-//   (perturb_stage_table, perturb_wrap, perturb_mfma, perturb_table); tile and longitude fold are those of wx_spectrum.h.
+//   innermost: the folded forward transform of wx_dft.h (dft_rows_folded).
 // Launch B, sht_legendre_kernel: per m, C[l][n] = sum_k T_m[l][k] B[k][n] on v_mfma_f64_16x16x4_f64.  A wave owns one tile: 16 degrees
 //   l of one parity of one m times all n of the pass (up to four accumulators); lane (c = lane & 15, g = lane >> 4) holds A[l_c][k_g]
 //   and B[k_g][n_c], and D[g + 4 reg][c].  Every tile contracts over the same kk rows, so the flat tile list (built on the host; l < m
 //   is never in it) keeps the chip even.  The vector form accumulates its four products into s and t in the same registers.
 // Synthesis, sht_legendre_inv_kernel then sht_lon_inv_kernel: the transposed contraction (tiles of 16 rows k of one m, orders
-//   ascending: the long contractions first) and the inverse DFT of wx_perturb.h's pass C.
+//   ascending: the long contractions first) and the inverse transform of wx_dft.h (dft_rows_inverse).
 // A pass takes up to kShtMaxPlanes planes; more planes take more passes.  Every sum has one fixed order and an output depends on its
 // own plane only: coefficients, fields and spectra are bit-identical whatever P, the plane's position or the split into calls.
 #pragma once
@@ -46,9 +45,8 @@
 #include <vector>
 
 #include "wx_common.h"
-#include "wx_perturb.h"
+#include "wx_dft.h"
 #include "wx_reduce.h"
-#include "wx_spectrum.h"
 
 namespace wx {
 
@@ -125,7 +123,7 @@ __host__ __device__ inline int64_t sht_table_offset(int m, int lmax, int kk) { r
 // "" or the reason wx_sht_create (and wx_sht_table) refuses.
 inline std::string sht_check_create(int nlat, int nlon, int lmax, int mmax, const double* theta, const double* w, const char* norm) {
   if (nlat < 2 || nlon < 2) return "nlat and nlon must be >= 2, got " + std::to_string(nlat) + " x " + std::to_string(nlon);
-  if (nlon > kPerturbMaxN) return "nlon must be <= " + std::to_string(kPerturbMaxN) + " (the twiddle table lies in LDS), got " + std::to_string(nlon);
+  if (nlon > kDftMaxN) return "nlon must be <= " + std::to_string(kDftMaxN) + " (the twiddle table lies in LDS), got " + std::to_string(nlon);
   if (nlat > 32768) return "nlat must be <= 32768, got " + std::to_string(nlat);
   if (lmax < 1 || lmax > 32768) return "lmax must be in 1 .. 32768, got " + std::to_string(lmax);
   if (mmax < 1 || mmax > std::min(lmax, nlon / 2 + 1))
@@ -161,9 +159,9 @@ inline std::string sht_check_ranges(const ShtRange* in, int n_in, const ShtRange
   for (int i = 0; i < n_out; ++i) {
     if (!out[i].p) continue;
     for (int j = 0; j < n_in; ++j)
-      if (in[j].p && spectrum_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes)) return "an output overlaps an input";
+      if (in[j].p && bytes_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes)) return "an output overlaps an input";
     for (int j = 0; j < i; ++j)
-      if (out[j].p && spectrum_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return "two outputs overlap";
+      if (out[j].p && bytes_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return "two outputs overlap";
   }
   return "";
 }
@@ -256,58 +254,18 @@ template <typename T>
 __global__ __launch_bounds__(256) void sht_lon_kernel(const T* __restrict__ src, int64_t stride, ShtGeom s, const double2* __restrict__ tab_g,
                                                       double* __restrict__ F, int col_blocks) {
   extern __shared__ double2 sht_lds[];
-  const int W = s.nlon, Wh = W / 2 + 1, M = s.np * s.nlat;
-  perturb_stage_table(sht_lds, tab_g, W);
+  const int W = s.nlon, M = s.np * s.nlat;
+  dft_stage_table(sht_lds, tab_g, W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int cb = (int)(blockIdx.x % (unsigned)col_blocks), rt = (int)(blockIdx.x / (unsigned)col_blocks);
-  const int r0 = rt * kSpecTileRows + wave * kSpecWaveRows, k0 = cb * kSpecTileCols;
+  const int r0 = rt * kDftTileRows + wave * kDftWaveRows, k0 = cb * kDftTileCols;
   if (r0 >= M) return;                                   // wave-uniform, after the only barrier
   const int row = r0 + c;
   const bool row_ok = row < M;
   const int rpl = row_ok ? row / s.nlat : 0, rk = row_ok ? row - rpl * s.nlat : 0;
-  const T* arow = src + (int64_t)rpl * stride + (int64_t)rk * W;
-  int idx[2], step1[2], step12[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int k = (k0 + 16 * t + c) % W;                 // wavenumbers beyond mmax are computed and never stored
-    idx[t] = (int)(((int64_t)k * (4 * g)) % W);
-    step1[t] = k;
-    step12[t] = (int)(((int64_t)k * 12) % W);
-  }
-  f64x4_t re[2] = {}, im[2] = {};
-  double va[4], ma[4];
-  const auto fetch = [&](int kc) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = kc + 4 * g + j;
-      const bool ok = row_ok && x < Wh;
-      const bool pair = ok && spectrum_has_mirror(W, x);
-      va[j] = ok ? (double)arow[x] : 0.0;
-      ma[j] = pair ? (double)arow[W - x] : 0.0;
-    }
-  };
-  fetch(0);
-  for (int kc = 0; kc < Wh; kc += 16) {
-    double e[4], o[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      e[j] = va[j] + ma[j];
-      o[j] = spectrum_has_mirror(W, kc + 4 * g + j) ? va[j] - ma[j] : 0.0;
-    }
-    fetch(kc + 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const double2 cs = sht_lds[idx[t]];
-        re[t] = perturb_mfma(e[j], cs.x, re[t]);
-        im[t] = perturb_mfma(o[j], cs.y, im[t]);
-        idx[t] = perturb_wrap(idx[t] + step1[t], W);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) idx[t] = perturb_wrap(idx[t] + step12[t], W);
-  }
+  const T* arow[1] = {src + (int64_t)rpl * stride + (int64_t)rk * W};
+  f64x4_t re[1][2] = {}, im[1][2] = {};
+  dft_rows_folded<1, T>(arow, row_ok, W, k0, sht_lds, re, im);
   const double scale = 2.0 * kShtPi / (double)W;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
@@ -318,7 +276,7 @@ __global__ __launch_bounds__(256) void sht_lon_kernel(const T* __restrict__ src,
       if (R < M && m < s.mmax) {
         const int pl = R / s.nlat, k = R - pl * s.nlat;
         double2* dst = (double2*)(F + ((int64_t)m * s.nlat + k) * s.nb + 2 * pl);
-        *dst = make_double2(scale * re[t][r], -(scale * im[t][r]));
+        *dst = make_double2(scale * re[0][t][r], -(scale * im[0][t][r]));
       }
     }
   }
@@ -371,7 +329,7 @@ __global__ __launch_bounds__(256) void sht_legendre_kernel(const int2* __restric
           const int n = 16 * t + c;
           if (!VEC) {
             const double b = k_ok ? wk * sht_operand(F, s, m, k, n, par) : 0.0;
-            acc[t] = perturb_mfma(a, b, acc[t]);
+            acc[t] = mfma_f64_16x16x4(a, b, acc[t]);
           } else {
             // s += -dPt Fv + Qt (-i Fu),  t += dPt Fu + Qt (-i Fv);  (-i z)[re] = z[im], (-i z)[im] = -z[re];  dPt has the parity !par
             const double sg = (n & 1) ? -1.0 : 1.0;
@@ -379,10 +337,10 @@ __global__ __launch_bounds__(256) void sht_legendre_kernel(const int2* __restric
             const double bv = k_ok ? wk * sht_operand(F2, s, m, k, n, !par) : 0.0;
             const double bux = k_ok ? sg * (wk * sht_operand(F, s, m, k, n ^ 1, par)) : 0.0;
             const double bvx = k_ok ? sg * (wk * sht_operand(F2, s, m, k, n ^ 1, par)) : 0.0;
-            acc[t] = perturb_mfma(a, -bv, acc[t]);
-            acc[t] = perturb_mfma(a2, bux, acc[t]);
-            acc2[t] = perturb_mfma(a, bu, acc2[t]);
-            acc2[t] = perturb_mfma(a2, bvx, acc2[t]);
+            acc[t] = mfma_f64_16x16x4(a, -bv, acc[t]);
+            acc[t] = mfma_f64_16x16x4(a2, bux, acc[t]);
+            acc2[t] = mfma_f64_16x16x4(a, bu, acc2[t]);
+            acc2[t] = mfma_f64_16x16x4(a2, bvx, acc2[t]);
           }
         }
       }
@@ -433,7 +391,7 @@ __global__ __launch_bounds__(256) void sht_legendre_inv_kernel(const double* __r
           if (t < ncb) {
             const int n = 16 * t + c, pl = n >> 1;
             const double b = (l_ok && pl < s.np) ? cin[(((int64_t)pl * s.lmax + l) * s.mmax + m) * 2 + (n & 1)] : 0.0;
-            acc[par][t] = perturb_mfma(a, b, acc[par][t]);
+            acc[par][t] = mfma_f64_16x16x4(a, b, acc[par][t]);
           }
         }
       }
@@ -504,12 +462,12 @@ __global__ __launch_bounds__(256) void sht_legendre_vinv_kernel(const double* __
             const double tn = (HAS_T && ok) ? tor[base + im] : 0.0;
             const double tx = (HAS_T && ok) ? sg * tor[base + (im ^ 1)] : 0.0;
             if (COMP & 1) {
-              au[par][t] = perturb_mfma(q, sx, au[par][t]);
-              if (HAS_T) au[par ^ 1][t] = perturb_mfma(d, tn, au[par ^ 1][t]);
+              au[par][t] = mfma_f64_16x16x4(q, sx, au[par][t]);
+              if (HAS_T) au[par ^ 1][t] = mfma_f64_16x16x4(d, tn, au[par ^ 1][t]);
             }
             if (COMP & 2) {
-              av[par ^ 1][t] = perturb_mfma(d, -sn, av[par ^ 1][t]);
-              if (HAS_T) av[par][t] = perturb_mfma(q, tx, av[par][t]);
+              av[par ^ 1][t] = mfma_f64_16x16x4(d, -sn, av[par ^ 1][t]);
+              if (HAS_T) av[par][t] = mfma_f64_16x16x4(q, tx, av[par][t]);
             }
           }
         }
@@ -541,13 +499,13 @@ __global__ __launch_bounds__(256) void sht_legendre_vinv_kernel(const double* __
   }
 }
 
-// Synthesis, second launch: pass C of wx_perturb.h on G[m][k][nb].  dst: plane p of the pass at dst + p * nlat * nlon.
+// Synthesis, second launch: dft_rows_inverse on G[m][k][nb].  dst: plane p of the pass at dst + p * nlat * nlon.
 // grid = (ceil(nlon / 64), ceil(np * nlat / 64)), LDS 16 nlon bytes.
 template <typename T>
 __global__ __launch_bounds__(256) void sht_lon_inv_kernel(const double* __restrict__ G, ShtGeom s, const double2* __restrict__ tab_g, T* __restrict__ dst) {
   extern __shared__ double2 sht_lds[];
-  const int W = s.nlon, M = s.np * s.nlat, N = 2 * s.mmax;
-  perturb_stage_table(sht_lds, tab_g, W);
+  const int W = s.nlon, M = s.np * s.nlat;
+  dft_stage_table(sht_lds, tab_g, W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int m0 = ((int)blockIdx.y * 4 + wave) * 16, n0 = (int)blockIdx.x * 64;
   if (m0 >= M) return;
@@ -556,34 +514,9 @@ __global__ __launch_bounds__(256) void sht_lon_inv_kernel(const double* __restri
   const int rpl = row_ok ? row / s.nlat : 0, rk = row_ok ? row - rpl * s.nlat : 0;
   const double* zrow = G + (int64_t)rk * s.nb + 2 * rpl;  // bin m of the row at zrow + m * nlat * nb: (re, im)
   const int64_t bin = (int64_t)s.nlat * s.nb;
-  int idx[4], step1[4], step8[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int x = (n0 + 16 * t + c) % W;                 // columns beyond nlon are computed and never stored
-    idx[t] = (int)(((int64_t)x * (2 * g)) % W);
-    step1[t] = x;
-    step8[t] = (int)(((int64_t)x * 8) % W);
-  }
   f64x4_t acc[4] = {};
-  for (int kc = 0; kc < N; kc += 16) {
-    const int m_a = (kc >> 1) + 2 * g;                   // the lane's two bins: m_a, m_a + 1
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int m = m_a + b;
-      const bool ok = row_ok && m < s.mmax;
-      const double2 z = ok ? *(const double2*)(zrow + (int64_t)m * bin) : make_double2(0.0, 0.0);
-      const bool once = m == 0 || 2 * m == W;            // bin 0 and the Nyquist bin: weight 1, imaginary part ignored
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int i = b ? perturb_wrap(idx[t] + step1[t], W) : idx[t];
-        const double2 cs = sht_lds[i];
-        acc[t] = perturb_mfma(z.x, once ? cs.x : 2.0 * cs.x, acc[t]);
-        acc[t] = perturb_mfma(z.y, once ? 0.0 : -2.0 * cs.y, acc[t]);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) idx[t] = perturb_wrap(idx[t] + step8[t], W);
-  }
+  dft_rows_inverse([&](int m) { return (row_ok && m < s.mmax) ? *(const double2*)(zrow + (int64_t)m * bin) : make_double2(0.0, 0.0); }, s.mmax, W,
+                   n0, sht_lds, acc);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int x = n0 + 16 * t + c;
@@ -607,7 +540,7 @@ __global__ __launch_bounds__(256) void sht_spectra_kernel(const double* __restri
       double acc[1] = {0.0};
       for (int m = lane; m < mmax && m <= l; m += 64) {
         const double2 z = cp[(int64_t)l * mmax + m];
-        acc[0] += (m == 0 ? 1.0 : 2.0) * spectrum_power(z.x, z.y);
+        acc[0] += (m == 0 ? 1.0 : 2.0) * dft_power(z.x, z.y);
       }
       wave_sum<1>(acc);
       if (lane == 0) total[p * lmax + l] = acc[0];
@@ -618,7 +551,7 @@ __global__ __launch_bounds__(256) void sht_spectra_kernel(const double* __restri
       double acc = 0.0;
       for (int l = m; l < lmax; ++l) {
         const double2 z = cp[(int64_t)l * mmax + m];
-        acc += (m == 0 ? 1.0 : 2.0) * spectrum_power(z.x, z.y);
+        acc += (m == 0 ? 1.0 : 2.0) * dft_power(z.x, z.y);
       }
       zonal[p * mmax + m] = acc;
     }
@@ -633,7 +566,7 @@ class Sht {
     fold = sht_folds(nlat, theta_host, w_host);
     kk = fold ? (nlat + 1) / 2 : nlat;
     std::vector<double2> t;
-    perturb_table(nlon, t);
+    dft_table(nlon, t);
     twiddle = mem.upload(t.data(), t.size());
     w = mem.upload(w_host, (size_t)nlat);
     std::vector<int2> tl;
@@ -691,7 +624,7 @@ class Sht {
                          c + (int64_t)p0 * lmax * mmax * 2, s, ktiles, buf[0]);
       WX_HIP(hipGetLastError());
       const dim3 grid((unsigned)cdiv(nlon, 64), (unsigned)cdiv((int64_t)s.np * nlat, 64));
-      const size_t lds = (size_t)nlon * sizeof(double2);
+      const size_t lds = dft_lds_bytes(nlon);
       const int64_t off = (int64_t)p0 * nlat * nlon;
       if (dtype == kShtF64) hipLaunchKernelGGL(sht_lon_inv_kernel<double>, grid, dim3(256), lds, stream, buf[0], s, twiddle, (double*)x + off);
       else hipLaunchKernelGGL(sht_lon_inv_kernel<float>, grid, dim3(256), lds, stream, buf[0], s, twiddle, (float*)x + off);
@@ -724,7 +657,7 @@ class Sht {
 #undef WX_SHT_VINV
       WX_HIP(hipGetLastError());
       const dim3 grid((unsigned)cdiv(nlon, 64), (unsigned)cdiv((int64_t)s.np * nlat, 64));
-      const size_t lds = (size_t)nlon * sizeof(double2);
+      const size_t lds = dft_lds_bytes(nlon);
       const int64_t off = (int64_t)p0 * nlat * nlon;
       void* dst[2] = {u, v};
       for (int i = 0; i < 2; ++i) {
@@ -762,9 +695,9 @@ class Sht {
     return s;
   }
   void forward_lon(const void* x, int64_t stride, int dtype, int p0, const ShtGeom& s, double* F, hipStream_t stream) {
-    const int col_blocks = cdiv(mmax, kSpecTileCols);
-    const dim3 grid((unsigned)((int64_t)cdiv((int64_t)s.np * nlat, kSpecTileRows) * col_blocks));
-    const size_t lds = (size_t)nlon * sizeof(double2);
+    const int col_blocks = cdiv(mmax, kDftTileCols);
+    const dim3 grid((unsigned)((int64_t)cdiv((int64_t)s.np * nlat, kDftTileRows) * col_blocks));
+    const size_t lds = dft_lds_bytes(nlon);
     if (dtype == kShtF64)
       hipLaunchKernelGGL(sht_lon_kernel<double>, grid, dim3(256), lds, stream, (const double*)x + (int64_t)p0 * stride, stride, s, twiddle, F, col_blocks);
     else

@@ -12,17 +12,11 @@
 //   scores[p][1]      = mean_{k >= k_init} (mean_amp_a[k] - mean_amp_b[k])^2                           SpectralLoss2D per plane
 // The reference's scalar losses are the means of the scores over the planes (every plane has the same element count).
 //
-// Launch 1, spectrum_rows_kernel: the transform, the squares and the row sums; no complex intermediate touches memory.  The operand
-// layout, the LDS twiddle table indexed by (k x) mod W in integer arithmetic and the MFMA (v_mfma_f64_16x16x4_f64) are pass A's of
-// wx_perturb.h (perturb_stage_table, perturb_wrap, perturb_mfma, perturb_table: used from there, nothing restated).  What differs:
-//   tile    a wave owns 16 rows x 32 wavenumbers: two accumulators hold the cos sums and two the sin sums of the SAME 32 k, so the lane
-//           that holds re of (row, k) holds im as well and |X|^2 needs no exchange; a twiddle read from LDS (cos, sin) feeds both.  With
-//           b, four more accumulators transform the matching rows of b with the same twiddles and the log difference is formed in
-//           registers.  A workgroup is four waves on 64 consecutive rows of ONE plane and the same 32 k.
-//   fold    the input is real, so with e[x] = r[x] + r[W - x] and o[x] = r[x] - r[W - x] for x = 1 .. ceil(W / 2) - 1 (the sum of two
-//           float32 is exact in fp64),  re X_k = sum e[x] cos,  -im X_k = sum o[x] sin;  x = 0 and, for even W, x = W / 2 enter
-//           unfolded with zero in the sin sum.  K runs over Wh values of x instead of W: half the MFMAs.  A lane's elements and mirrors
-//           of the next K chunk are fetched before the MFMAs of the current one: at two waves per SIMD that is what hides the loads.
+// Launch 1, spectrum_rows_kernel: the transform, the squares and the row sums; no complex intermediate touches memory.
+//   dft     the folded forward transform of wx_dft.h (dft_rows_folded: tile, fold, LDS twiddle table and sum order are stated there).
+//           The lane that holds re of (row, k) holds im as well, so |X|^2 needs no exchange.  With b, four more accumulators transform
+//           the matching rows of b with the same twiddles and the log difference is formed in registers; the prefetch of the next K
+//           chunk is what hides the loads at two waves per SIMD.  A workgroup is four waves on 64 consecutive rows of ONE plane.
 //   sums    per (plane, k) five sums over the workgroup's rows, fp64: w psd_a, w psd_b, w |X_a|, w |X_b|, w (log difference)^2 -- in a
 //           thread over its four rows ascending, in a wave over the four lane groups (wave_sum_groups of wx_reduce.h), in the workgroup
 //           over the waves 0, 1, 2, 3 -- written to the workgroup's own slot.  No atomics.
@@ -37,17 +31,14 @@
 #include <vector>
 
 #include "wx_common.h"
-#include "wx_perturb.h"
+#include "wx_dft.h"
 #include "wx_reduce.h"
 
 namespace wx {
 
-constexpr int kSpecWaveRows = 16;
-constexpr int kSpecTileRows = 64;     // a workgroup: four waves
-constexpr int kSpecTileCols = 32;     // wavenumbers of a workgroup: two MFMA column blocks
 constexpr int kSpecSums = 5;          // w psd_a, w psd_b, w |X_a|, w |X_b|, w (log psd_a - log psd_b)^2
 constexpr double kSpecLogEps = 1e-8;  // PSDLoss.forward
-constexpr size_t kSpecReduceBytes = (size_t)(kSpecTileRows / kSpecWaveRows) * 2 * kSpecSums * 16 * sizeof(double);
+constexpr size_t kSpecReduceBytes = (size_t)(kDftTileRows / kDftWaveRows) * 2 * kSpecSums * 16 * sizeof(double);
 
 struct SpecTiles {
   int Wh, row_tiles, col_blocks;
@@ -56,31 +47,18 @@ struct SpecTiles {
 // ---- host-only helpers (no HIP call) ---------------------------------------------------------------------------------------------
 inline SpecTiles spectrum_tiles(int H, int W) {
   const int Wh = W / 2 + 1;
-  return {Wh, (H + kSpecTileRows - 1) / kSpecTileRows, (Wh + kSpecTileCols - 1) / kSpecTileCols};
+  return {Wh, (H + kDftTileRows - 1) / kDftTileRows, (Wh + kDftTileCols - 1) / kDftTileCols};
 }
 inline int64_t spectrum_slot_doubles(int H, int W, int64_t n_planes) {
   const SpecTiles t = spectrum_tiles(H, W);
   return n_planes * t.row_tiles * kSpecSums * t.Wh;
 }
-inline size_t spectrum_lds_bytes(int W) { return std::max((size_t)W * sizeof(double2), kSpecReduceBytes); }
-
-// The fold of column x: v = r[x], m = its mirror r[W - x] (0 where x has none: x = 0 and, for even W, x = W / 2); e enters the cos sum,
-// o the sin sum.  The kernel's and the host's.
-__host__ __device__ inline bool spectrum_has_mirror(int W, int x) { return x != 0 && 2 * x != W; }
-__host__ __device__ inline void spectrum_fold_pair(float v, float m, bool pair, double& e, double& o) {
-  e = (double)v + (double)m;
-  o = pair ? (double)v - (double)m : 0.0;
-}
-// The folded operand of column x (0 <= x < Wh) of a row r[W].
-inline void spectrum_fold(const float* r, int W, int x, double& e, double& o) {
-  const bool pair = spectrum_has_mirror(W, x);
-  spectrum_fold_pair(r[x], pair ? r[W - x] : 0.f, pair, e, o);
-}
+inline size_t spectrum_lds_bytes(int W) { return std::max(dft_lds_bytes(W), kSpecReduceBytes); }
 
 // "" or the reason wx_spectrum_create refuses.
 inline std::string spectrum_check_create(int H, int W, const float* lat_w) {
   if (H < 2 || W < 2) return "H and W must be >= 2, got " + std::to_string(H) + " x " + std::to_string(W);
-  if (W > kPerturbMaxN) return "W must be <= " + std::to_string(kPerturbMaxN) + " (the twiddle table lies in LDS), got " + std::to_string(W);
+  if (W > kDftMaxN) return "W must be <= " + std::to_string(kDftMaxN) + " (the twiddle table lies in LDS), got " + std::to_string(W);
   if ((int64_t)H * W > 2147483647LL) return "H * W is beyond 2^31 - 1";
   if (lat_w) {
     double sum = 0.0;
@@ -91,11 +69,6 @@ inline std::string spectrum_check_create(int H, int W, const float* lat_w) {
     if (!(sum > 0.0)) return "the latitude weights sum to zero";
   }
   return "";
-}
-
-inline bool spectrum_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = (uintptr_t)a, a1 = a0 + (uintptr_t)a_bytes, b0 = (uintptr_t)b, b1 = b0 + (uintptr_t)b_bytes;
-  return a0 < b1 && b0 < a1;
 }
 
 // "" or the reason wx_spectrum_apply refuses, decided on the host before anything is launched.
@@ -125,9 +98,9 @@ inline std::string spectrum_check_apply(int H, int W, int n_planes, const float*
   for (int i = 0; i < 7; ++i) {
     if (!out[i].p) continue;
     for (int j = 0; j < 2; ++j)
-      if (in[j].p && spectrum_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes)) return "an output overlaps an input field";
+      if (in[j].p && bytes_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes)) return "an output overlaps an input field";
     for (int j = 0; j < i; ++j)
-      if (out[j].p && spectrum_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return "two outputs overlap";
+      if (out[j].p && bytes_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) return "two outputs overlap";
   }
   return "";
 }
@@ -144,78 +117,29 @@ struct SpecRowsArgs {
   int H, W, row_tiles, col_blocks;
 };
 
-__device__ inline double spectrum_power(double re, double im) { return fma(re, re, im * im); }
-
 // Launch 1.  grid = P * row_tiles * col_blocks (column block fastest), LDS spectrum_lds_bytes(W): the table, then the waves' sums.
 template <bool HAS_B>
 __global__ __launch_bounds__(256) void spectrum_rows_kernel(SpecRowsArgs s, const double2* __restrict__ tab_g) {
   extern __shared__ double2 spectrum_lds[];
   const int H = s.H, W = s.W, Wh = W / 2 + 1;
-  perturb_stage_table(spectrum_lds, tab_g, W);
+  dft_stage_table(spectrum_lds, tab_g, W);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
   const int cb = (int)(blockIdx.x % (unsigned)s.col_blocks);
   const int tile = (int)(blockIdx.x / (unsigned)s.col_blocks);
   const int rt = tile % s.row_tiles;
   const int64_t p = tile / s.row_tiles;
-  const int h0 = rt * kSpecTileRows + wave * kSpecWaveRows, k0 = cb * kSpecTileCols;
+  const int h0 = rt * kDftTileRows + wave * kDftWaveRows, k0 = cb * kDftTileCols;
   const bool live = h0 < H;                              // wave-uniform; a wave past the plane keeps zeros and meets the barriers
-  f64x4_t re_a[2] = {}, im_a[2] = {}, re_b[2] = {}, im_b[2] = {};
+  constexpr int NF = HAS_B ? 2 : 1;                      // the fields: a, then b
+  f64x4_t re[NF][2] = {}, im[NF][2] = {};
+  const auto &re_a = re[0], &im_a = im[0], &re_b = re[NF - 1], &im_b = im[NF - 1];
   if (live) {
     const int row = h0 + c;
     const bool row_ok = row < H;
-    const float* arow = s.a + p * s.a_stride + (int64_t)(row_ok ? row : 0) * W;
-    const float* brow = HAS_B ? s.b + p * s.b_stride + (int64_t)(row_ok ? row : 0) * W : nullptr;
-    int idx[2], step1[2], step12[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int k = (k0 + 16 * t + c) % W;               // columns beyond Wh are computed and never stored
-      idx[t] = (int)(((int64_t)k * (4 * g)) % W);
-      step1[t] = k;
-      step12[t] = (int)(((int64_t)k * 12) % W);
-    }
-    // a chunk's elements r[x] and their mirrors r[W - x] (0 where there is none) are fetched one chunk ahead of the MFMAs that use them
-    float va[4], ma[4], vb[4], mb[4];
-    const auto fetch = [&](int kc) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int x = kc + 4 * g + j;
-        const bool ok = row_ok && x < Wh;
-        const bool pair = ok && spectrum_has_mirror(W, x);   // W - x > x: every element of the row enters once
-        va[j] = ok ? arow[x] : 0.f;
-        ma[j] = pair ? arow[W - x] : 0.f;
-        if (HAS_B) {
-          vb[j] = ok ? brow[x] : 0.f;
-          mb[j] = pair ? brow[W - x] : 0.f;
-        }
-      }
-    };
-    fetch(0);
-    for (int kc = 0; kc < Wh; kc += 16) {
-      double ea[4], oa[4], eb[4], ob[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {                      // past the row v = m = 0: both sums get 0
-        const bool pair = spectrum_has_mirror(W, kc + 4 * g + j);
-        spectrum_fold_pair(va[j], ma[j], pair, ea[j], oa[j]);
-        if (HAS_B) spectrum_fold_pair(vb[j], mb[j], pair, eb[j], ob[j]);
-      }
-      fetch(kc + 16);                                    // past the row: every guard is false, nothing is read
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const double2 cs = spectrum_lds[idx[t]];
-          re_a[t] = perturb_mfma(ea[j], cs.x, re_a[t]);
-          im_a[t] = perturb_mfma(oa[j], cs.y, im_a[t]);
-          if (HAS_B) {
-            re_b[t] = perturb_mfma(eb[j], cs.x, re_b[t]);
-            im_b[t] = perturb_mfma(ob[j], cs.y, im_b[t]);
-          }
-          idx[t] = perturb_wrap(idx[t] + step1[t], W);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) idx[t] = perturb_wrap(idx[t] + step12[t], W);
-    }
+    const float* rows[NF];
+    rows[0] = s.a + p * s.a_stride + (int64_t)(row_ok ? row : 0) * W;
+    if (HAS_B) rows[NF - 1] = s.b + p * s.b_stride + (int64_t)(row_ok ? row : 0) * W;
+    dft_rows_folded<NF, float>(rows, row_ok, W, k0, spectrum_lds, re, im);
   }
   // the lane's elements: rows h0 + g + 4 r, wavenumbers k0 + 16 t + c
   double sums[2][kSpecSums] = {};
@@ -231,13 +155,13 @@ __global__ __launch_bounds__(256) void spectrum_rows_kernel(SpecRowsArgs s, cons
         if (h < H && k < Wh) {
           const double wv = s.w ? (double)s.w[h] : 1.0;
           const int64_t o = (p * H + h) * Wh + k;
-          const double pa = spectrum_power(re_a[t][r], im_a[t][r]);
+          const double pa = dft_power(re_a[t][r], im_a[t][r]);
           const double psda = mult * pa / w2;
           if (s.psd_a) s.psd_a[o] = (float)psda;
           sums[t][0] += wv * psda;
           sums[t][2] += wv * sqrt(pa);
           if (HAS_B) {
-            const double pb = spectrum_power(re_b[t][r], im_b[t][r]);
+            const double pb = dft_power(re_b[t][r], im_b[t][r]);
             const double psdb = mult * pb / w2;
             if (s.psd_b) s.psd_b[o] = (float)psdb;
             const double d = log(psda + kSpecLogEps) - log(psdb + kSpecLogEps);
@@ -266,7 +190,7 @@ __global__ __launch_bounds__(256) void spectrum_rows_kernel(SpecRowsArgs s, cons
     const int k = k0 + 16 * t + cc;
     if (k < Wh && (HAS_B || i == 0 || i == 2)) {
       double v = red[((0 * 2 + t) * kSpecSums + i) * 16 + cc];
-      for (int wv = 1; wv < kSpecTileRows / kSpecWaveRows; ++wv) v += red[((wv * 2 + t) * kSpecSums + i) * 16 + cc];
+      for (int wv = 1; wv < kDftTileRows / kDftWaveRows; ++wv) v += red[((wv * 2 + t) * kSpecSums + i) * 16 + cc];
       s.slots[(((p * s.row_tiles + rt) * kSpecSums) + i) * Wh + k] = v;
     }
   }
@@ -326,7 +250,7 @@ class Spectrum {
   Spectrum(int H_, int W_, const float* lat_w_host, int dev) : H(H_), W(W_), device(dev), mem(dev) {
     WX_HIP(hipSetDevice(device));
     std::vector<double2> t;
-    perturb_table(W, t);
+    dft_table(W, t);
     tab = mem.upload(t.data(), t.size());
     wsum = (double)H;
     if (lat_w_host) {

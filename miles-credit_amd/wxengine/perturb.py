@@ -18,7 +18,7 @@ from .native import HandleCache, WXEngineError, _check, _f32, _stream_ptr, requi
 from .noise import SLOT_PERTURB  # noqa: F401  (the generator's slot of these draws)
 
 KIND_WHITE, KIND_COLOUR = 0, 1
-MAX_SIDE = 4096              # kPerturbMaxN: the colour filter keeps a pass's twiddle table in LDS
+MAX_SIDE = 4096              # kDftMaxN (csrc/wx_dft.h): the colour filter keeps a pass's twiddle table in LDS
 MAX_ELEMENTS = 1 << 34       # kPerturbMaxElems: the generator's counter
 
 

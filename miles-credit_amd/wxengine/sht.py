@@ -39,7 +39,7 @@ import numpy as np
 
 from .native import HandleCache, WXEngineError, _check, _f64, _stream_ptr, require_gpu
 
-MAX_NLON = 4096                 # kPerturbMaxN: the twiddle table lies in LDS
+MAX_NLON = 4096                 # kDftMaxN (csrc/wx_dft.h): the twiddle table lies in LDS
 MAX_DEGREE = 32768
 GRIDS = ("equiangular", "legendre-gauss")
 NORM_REASON = ('only norm="ortho" is supported: the meaning of torch_harmonics\' "backward" and "schmidt" cannot be pinned without the '

@@ -29,7 +29,7 @@ import numpy as np
 from .native import NativeHandle, PendingResult, WXEngineError, _check, _f32, _stream_ptr, copy_out, require_gpu
 from .native import flatten_named as _flatten_named
 
-MAX_W = 4096            # kPerturbMaxN: the twiddle table lies in LDS
+MAX_W = 4096            # kDftMaxN (csrc/wx_dft.h): the twiddle table lies in LDS
 PARTS = ("mean_psd_pred", "mean_psd_target", "mean_amp_pred", "mean_amp_target")     # the [P][Wh] blocks of a variable's table, then [P][2]
 
 

@@ -28,6 +28,9 @@ GRID_CASES = {
     "g64x128": (64, 128, "legendre-gauss", 64, None), "g64x128p": (64, 128, "legendre-gauss", 65, None),
     "e181x360": (181, 360, "equiangular", 181, None), "e181x360p": (181, 360, "equiangular", 182, None),   # indexing beyond small tiles
     "e33x64r": (33, 64, "equiangular", 20, 7),                                                         # a rectangular truncation
+    # odd nlon: no Nyquist bin and no fold midpoint.  9 x 15: below one MFMA tile, mmax = 8; 37 x 75: Wh = 38 leaves the K loop a tail,
+    # mmax = 37 two column blocks with the second partial
+    "e9x15": (9, 15, "equiangular", 9, None), "e37x75": (37, 75, "equiangular", 37, None),
 }
 WIND_CASE = "g16x32w"                                       # the scipy-built wind of tests/golden/sht_wind.npz: not among the swept grids
 ALL_CASES = dict(GRID_CASES, **{WIND_CASE: (16, 32, "legendre-gauss", 12, None)})

@@ -1,8 +1,9 @@
 // Stand-alone host check of the host-only helpers of csrc/wx_perturb.h -- perturb_check_create and perturb_check_apply (what the
-// C ABI refuses), perturb_batch_planes and perturb_table -- meant for AddressSanitizer / UBSan.  The index arithmetic of the three DFT
-// kernels is replayed on the host for every lane of every workgroup over exactly-sized heap arrays: the running table index
-// (k x) mod N must stay inside the table and equal the 64-bit modulo, and every guarded load and store must stay inside its buffer, so
-// an index past an array is caught here and not on a GPU.  It calls no HIP function, so it runs on a machine without a GPU:
+// C ABI refuses) and perturb_batch_planes -- meant for AddressSanitizer / UBSan.  The index arithmetic of the three DFT kernels is
+// replayed on the host for every lane of every workgroup over exactly-sized heap arrays, the table index taken from the kernels' own
+// DftPhase (checked by itself in tools/dft_host_check.hip): every guarded load and store must stay inside its buffer and every output
+// is written exactly once, so an index past an array is caught here and not on a GPU.  It calls no HIP function, so it runs on a
+// machine without a GPU:
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all \
 //         tools/perturb_host_check.hip -o perturb_host_check && ./perturb_host_check
 #include <cstdio>
@@ -21,13 +22,12 @@
   } while (0)
 
 static bool has(const std::string& s, const char* what) { return s.find(what) != std::string::npos; }
-static int wrap(int i, int N) { return i >= N ? i - N : i; }
 
 // passes A and C: M rows, the table of W entries; touches src / in and out as the kernels do
 static void replay_rows(int nb, int H, int W) {
   const int Wh = W / 2 + 1, N = 2 * Wh, M = nb * H;
   std::vector<double2> tab;
-  wx::perturb_table(W, tab);
+  wx::dft_table(W, tab);
   std::vector<float> src((size_t)M * W, 1.f);
   std::vector<double> spec((size_t)M * N, 0.0);
   std::vector<char> seen_a((size_t)M * N, 0), seen_c((size_t)M * W, 0);
@@ -39,18 +39,17 @@ static void replay_rows(int nb, int H, int W) {
         const int c = lane & 15, g = lane >> 4, row = m0 + c;
         for (int bx = 0; bx < wx::cdiv(N, 64); ++bx)          // pass A
           for (int t = 0; t < 4; ++t) {
-            const int n = bx * 64 + 16 * t + c, k = (n >> 1) % W;
-            int idx = (int)(((int64_t)k * (4 * g)) % W);
-            const int step12 = (int)(((int64_t)k * 12) % W);
+            const int n = bx * 64 + 16 * t + c;
+            wx::DftPhase ph;
+            ph.init(n >> 1, 4 * g, 12, W);
             for (int kc = 0; kc < W; kc += 16) {
               for (int j = 0; j < 4; ++j) {
                 const int x = kc + 4 * g + j;
-                EXPECT(idx >= 0 && idx < W && idx == (int)(((int64_t)k * x) % W));
-                (void)tab.at(idx);
+                (void)tab.at(ph.idx);
                 if (row < M && x < W) (void)src.at((size_t)row * W + x);
-                idx = wrap(idx + k, W);
+                ph.step(W);
               }
-              idx = wrap(idx + step12, W);
+              ph.skip(W);
             }
             for (int r = 0; r < 4; ++r) {
               const int m = m0 + g + 4 * r;
@@ -59,19 +58,16 @@ static void replay_rows(int nb, int H, int W) {
           }
         for (int bx = 0; bx < wx::cdiv(W, 64); ++bx)          // pass C
           for (int t = 0; t < 4; ++t) {
-            const int xo = bx * 64 + 16 * t + c, x = xo % W;
-            int idx = (int)(((int64_t)x * (2 * g)) % W);
-            const int step8 = (int)(((int64_t)x * 8) % W);
-            for (int kc = 0; kc < N; kc += 16) {
-              const int kk0 = kc + 4 * g;
+            const int xo = bx * 64 + 16 * t + c;
+            wx::DftPhase ph;
+            ph.init(xo, 2 * g, 8, W);
+            for (int k0 = 0; k0 < Wh; k0 += 8) {
               for (int b = 0; b < 2; ++b) {
-                const int k = (kk0 >> 1) + b, i = b ? wrap(idx + x, W) : idx;
-                EXPECT(i >= 0 && i < W && i == (int)(((int64_t)k * x) % W));
-                (void)tab.at(i);
-                for (int j = 2 * b; j < 2 * b + 2; ++j)
-                  if (row < M && kk0 + j < N) (void)spec.at((size_t)row * N + kk0 + j);
+                const int k = k0 + 2 * g + b;
+                (void)tab.at(b ? ph.ahead(W) : ph.idx);
+                if (row < M && k < Wh) { (void)spec.at((size_t)row * N + 2 * k); (void)spec.at((size_t)row * N + 2 * k + 1); }
               }
-              idx = wrap(idx + step8, W);
+              ph.skip(W);
             }
             for (int r = 0; r < 4; ++r) {
               const int m = m0 + g + 4 * r;
@@ -88,7 +84,7 @@ static void replay_rows(int nb, int H, int W) {
 static void replay_cols(int H, int W) {
   const int N = 2 * (W / 2 + 1);
   std::vector<double2> tab;
-  wx::perturb_table(H, tab);
+  wx::dft_table(H, tab);
   std::vector<double> X((size_t)H * N, 1.0);
   std::vector<float> S((size_t)H * (N / 2), 1.f);
   std::vector<char> seen((size_t)H * N, 0);
@@ -98,21 +94,20 @@ static void replay_cols(int H, int W) {
       if (m0 >= H) continue;
       for (int bx = 0; bx < wx::cdiv(N, 64); ++bx)
         for (int lane = 0; lane < 64; ++lane) {
-          const int c = lane & 15, g = lane >> 4, l = (m0 + c) % H;
-          int idx = (int)(((int64_t)l * (4 * g)) % H);
-          const int step12 = (int)(((int64_t)l * 12) % H);
+          const int c = lane & 15, g = lane >> 4;
+          wx::DftPhase ph;
+          ph.init(m0 + c, 4 * g, 12, H);
           for (int kc = 0; kc < H; kc += 16) {
             for (int j = 0; j < 4; ++j) {
               const int h = kc + 4 * g + j;
-              EXPECT(idx >= 0 && idx < H && idx == (int)(((int64_t)l * h) % H));
-              (void)tab.at(idx);
-              idx = wrap(idx + l, H);
+              (void)tab.at(ph.idx);
+              ph.step(H);
               for (int t = 0; t < 4; ++t) {
                 const int n = bx * 64 + 16 * t + c;
                 if (h < H && n < N) { (void)X.at((size_t)h * N + n); (void)X.at((size_t)h * N + (n ^ 1)); }
               }
             }
-            idx = wrap(idx + step12, H);
+            ph.skip(H);
           }
           for (int t = 0; t < 4; ++t)
             for (int r = 0; r < 4; ++r) {
@@ -150,12 +145,9 @@ int main() {
   EXPECT(has(perturb_check_apply(5, 8, 2, nullptr, nullptr, hw, a.data(), hw, nullptr, hw, a.data() + 8, hw), "same view"));
   EXPECT(has(perturb_check_apply(5, 8, 2, nullptr, nullptr, hw, a.data(), hw, b.data(), hw, b.data() + 40, hw), "outputs overlap"));
   EXPECT(perturb_check_apply(5, 8, 2, nullptr, b.data(), hw, a.data(), hw, b.data(), hw, a.data(), hw).empty());          // delta_out = prev, x_out = x
-  // batch and table
+  // batch
   EXPECT(perturb_batch_planes(721, 1440) == 16 && perturb_batch_planes(19, 37) == 64 && perturb_batch_planes(4096, 4096) == 1);
   EXPECT((int64_t)perturb_batch_planes(721, 1440) * perturb_plane_bytes(721, 1440) <= kPerturbScratchBytes);
-  std::vector<double2> t;
-  perturb_table(1440, t);
-  EXPECT(t.size() == 1440 && t[0].x == 1.0 && t[0].y == 0.0 && t[720].x == -1.0 && std::fabs(t[360].y - 1.0) < 1e-15);
   // the kernels' indexing on the cases of tests/perturb_cases.py, two planes where a row tile straddles planes
   const int grids[][3] = {{3, 5, 8}, {2, 7, 9}, {4, 19, 37}, {1, 33, 64}, {4, 37, 72}, {1, 181, 360}, {2, 1, 2}, {1, 721, 1440}};
   for (const auto& gr : grids) {

@@ -78,7 +78,7 @@ int main() {
     EXPECT(!sht_check_create(nlat, nlon, lmax, mmax, theta.data(), w.data(), nullptr).empty());
     EXPECT(!sht_check_create(nlat, nlon, 0, mmax, theta.data(), w.data(), "ortho").empty());
     EXPECT(!sht_check_create(nlat, nlon, lmax, lmax + 1, theta.data(), w.data(), "ortho").empty());
-    EXPECT(!sht_check_create(nlat, kPerturbMaxN + 2, lmax, mmax, theta.data(), w.data(), "ortho").empty());
+    EXPECT(!sht_check_create(nlat, kDftMaxN + 2, lmax, mmax, theta.data(), w.data(), "ortho").empty());
     std::vector<double> bad = theta;
     bad[nlat - 1] = bad[0];
     EXPECT(!sht_check_create(nlat, nlon, lmax, mmax, bad.data(), w.data(), "ortho").empty());

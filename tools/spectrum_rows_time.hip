@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../miles-credit_amd/csrc/wx_perturb.h"
 #include "../miles-credit_amd/csrc/wx_spectrum.h"
 
 #define CHECK(expr)                                                                              \
@@ -73,7 +74,7 @@ int main(int argc, char** argv) {
   for (size_t i = 0; i < n; ++i) host[i] += (float)(i % 7) * 0.1f;
   CHECK(hipMemcpy(b, host.data(), n * 4, hipMemcpyHostToDevice));
   std::vector<double2> tw;
-  wx::perturb_table(W, tw);
+  wx::dft_table(W, tw);
   CHECK(hipMalloc(&tab, tw.size() * sizeof(double2)));
   CHECK(hipMemcpy(tab, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
 
@@ -88,8 +89,8 @@ int main(int argc, char** argv) {
   CHECK(hipGetLastError());
   timed(
       [&] {
-        hipLaunchKernelGGL(wx::perturb_rows_fwd_kernel, rows_grid, dim3(256), (size_t)W * sizeof(double2), nullptr, a, M, W, tab, half);
-        hipLaunchKernelGGL(wx::perturb_rows_fwd_kernel, rows_grid, dim3(256), (size_t)W * sizeof(double2), nullptr, b, M, W, tab, half);
+        hipLaunchKernelGGL(wx::perturb_rows_fwd_kernel, rows_grid, dim3(256), wx::dft_lds_bytes(W), nullptr, a, M, W, tab, half);
+        hipLaunchKernelGGL(wx::perturb_rows_fwd_kernel, rows_grid, dim3(256), wx::dft_lds_bytes(W), nullptr, b, M, W, tab, half);
       },
       warmup, reps, plain);
   CHECK(hipGetLastError());
